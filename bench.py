@@ -6,7 +6,11 @@ read set, starting from cleared filters: forward (left) file, then the reverse-c
 file, every k-mer through graph.add and every read-paired k-mer through rpkbf.add.  Reads are
 generated on the device before the timed region and stay resident in HBM (packed 2-bit format).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--genome G] [--nk NK]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--genome G] [--nk NK] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (with the stage times and the roofline object, taken from
+those same steps).  --full adds the measurements that take runs of their own: the host-resident leg (`host_resident`) and the
+CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 N>1: one rank per GPU.  Launched as `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the
 script is a rank (RANK / WORLD_SIZE in the environment); launched plainly as `python bench.py --gpus N` it starts
@@ -222,7 +226,12 @@ def parse():
     ap.add_argument("--force-sharded", action="store_true", help="use the sharded engine + RCCL collectives even on 1 GPU")
     ap.add_argument("--no-host-leg", action="store_true", help="skip the host-resident leg (packed reads in pinned host memory, uploaded inside the timed region)")
     ap.add_argument("--host-piece-reads", type=int, default=0, help="reads per uploaded piece of the host-resident leg (0: 2^20, doubling up to 2^23)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the measurements that take runs of their own: the host-resident leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (single-GPU engine)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(a):
@@ -264,6 +273,8 @@ def main():
                          % (rank, local, torch.cuda.device_count()))
     torch.cuda.set_device(local)
     sharded_mode = world > 1 or a.force_sharded
+    if sharded_mode and a.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs reads the filters of the single-GPU engine; it does not take --gpus N > 1 or --force-sharded")
     if sharded_mode:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29511")
@@ -357,6 +368,7 @@ def main():
     kmers = pairs_ins = distinct = conflict = n_sorted = 0
     for _ in range(a.steps):
         s1, s2 = step()
+        last = (s1, s2)
         kmers += s1.kmers + s2.kmers
         pairs_ins += s1.pairs + s2.pairs
         distinct += s1.distinct + s2.distinct
@@ -375,6 +387,8 @@ def main():
     else:
         kmers_all = kmers
     prof = g.profileGet(reset=True)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, g, batch, last)
 
     if rank == 0:
         ms_step = dt / a.steps * 1e3
@@ -446,9 +460,9 @@ def main():
         }
         if sharded_mode and sharded.TRACE is not None:
             out["shard_phase_ms_per_step"] = {kk: round(v / a.steps, 1) for kk, v in sorted(sharded.TRACE.items(), key=lambda kv: -kv[1])}
-        if not sharded_mode and not a.no_host_leg:
+        if a.full and not sharded_mode and not a.no_host_leg:
             out["host_resident"] = host_resident_leg(a, g, batch, pairs_total, kmers_all // a.steps)
-        if not a.no_cpu_baseline and world == 1:       # the CPU baseline is timed on rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:       # the CPU baseline is timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(a, batch, dbg_bits, cbf_bytes, pk_bits, dist_pk)
     if sharded_mode:
         dist.barrier()
@@ -462,6 +476,39 @@ def main():
             pass
         sys.stdout.flush()
         print(json.dumps(out), flush=True)
+
+
+DUMP_BLOCKS, DUMP_BLOCK_READS = 16, 1024       # the read sample of cbf_counts_sample.npy: 16 x 1024 reads x 126 windows x 4 B = 8.3 MB
+
+
+def dump_outputs(path, g, batch, stats):
+    """What the timed path computed in its last step, as float64 / float32 .npy files (about 8 MB in all), so that two builds can be
+    compared output for output on the same arguments (the reads are seeded, so the inputs are the same from run to run):
+      add_stats.npy           [2, 3] reads, k-mers and read pairs of the AddStats each addBatch call returned (left file, right file);
+                              its other fields (distinct, conflict_ops, sorted_kmers) count the pipeline's work, which depends on what the
+                              no-op prefilter cache holds when a window arrives, and are left out
+      filter_summary.npy      [3, 6] per filter (dbgbf, cbf, rpkbf): rb_filter_fold of the whole filter as its low and high 32 bits,
+                              popcount (set bits; cbf: non-zero counters), size, bytes, hash functions
+      cbf_counts_sample.npy   [DUMP_BLOCKS, DUMP_BLOCK_READS * windows] getKmers' count profile (rb_graph_batch_counts) of a fixed, seeded
+                              sample of read blocks
+      cbf_counts_sample_first.npy  [DUMP_BLOCKS] the first read of each block"""
+    import numpy as np
+    from rnabloom import _native as N
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "add_stats.npy"), np.array([[s.reads, s.kmers, s.pairs] for s in stats], np.float64))
+    summary = []
+    for which in (N.DBGBF, N.CBF, N.RPKBF):
+        fold = _fold(g, which)
+        size, nbytes, h = g.filterSize(which)
+        summary.append([fold & 0xFFFFFFFF, fold >> 32, g.popcount(which), size, nbytes, h])
+    np.save(os.path.join(path, "filter_summary.npy"), np.array(summary, np.float64))
+    block = min(DUMP_BLOCK_READS, batch.n_reads)
+    n_blocks = batch.n_reads // block
+    rng = np.random.default_rng(0x5EED)
+    firsts = np.sort(rng.choice(n_blocks, min(DUMP_BLOCKS, n_blocks), replace=False)) * block
+    counts = np.stack([g.batchCounts(batch, int(f), block) for f in firsts])
+    np.save(os.path.join(path, "cbf_counts_sample.npy"), counts.astype(np.float32))
+    np.save(os.path.join(path, "cbf_counts_sample_first.npy"), firsts.astype(np.float64))
 
 
 def host_resident_leg(a, g, batch, pairs_total, kmers_per_step):

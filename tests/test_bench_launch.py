@@ -43,3 +43,19 @@ def test_a_rank_refuses_a_world_size_that_is_not_gpus():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "4"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr and "{" not in r.stdout
+
+
+def test_plain_arguments_leave_the_extra_legs_off(monkeypatch):
+    """--full is off by default (the host-resident leg and the CPU baseline run only with it), --dump-outputs takes a directory, and --steps
+    below 1 is refused before anything starts"""
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = b.parse()
+    assert a.steps == 5 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out_dir"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        b.parse()
+    assert e.value.code != 0

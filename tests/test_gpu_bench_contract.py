@@ -1,4 +1,5 @@
-"""bench.py's one-line contract on a small workload: the single-GPU line (with roofline and cpu_baseline objects) and the line
+"""bench.py's one-line contract on a small workload: the single-GPU line of --full (with roofline, host_resident and cpu_baseline objects), the
+lean plain line with its --dump-outputs files, and the line
 of a 2-rank run launched the way the driver launches it (torch.distributed.run; the two ranks share the test box's GPU, so the
 exchange goes over gloo — RCCL refuses two ranks on one device)."""
 import json
@@ -29,7 +30,7 @@ def free_port():
 
 def test_single_gpu_line_and_two_rank_line():
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, "bench.py", "--cpu-sample-pairs", "40000", "--host-piece-reads", "70000"] + SMALL,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--cpu-sample-pairs", "40000", "--host-piece-reads", "70000"] + SMALL,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = last_json(r.stdout)
@@ -66,6 +67,31 @@ def test_single_gpu_line_and_two_rank_line():
     j3 = last_json(r3.stdout)
     assert r3.stdout.strip().splitlines()[-1].startswith("{"), "the JSON line must be the last line"
     assert j3["n_gpus"] == 2 and j3["scaling"] == "strong" and j3["config"]["kmers_per_step"] == j["config"]["kmers_per_step"]
+
+
+def test_plain_line_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """a plain run (no --full) times its steps and prints the line without the legs that take runs of their own; --dump-outputs writes
+    what the last timed step computed, float32 / float64 only, and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, "bench.py", "--dump-outputs", str(d)] + SMALL, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = last_json(r.stdout)
+        assert j["steps"] == 1 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["dtype"] == "u64"
+        assert "host_resident" not in j and "cpu_baseline" not in j and isinstance(j["roofline"], dict)
+        files = {p.name: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert set(files) == {"add_stats.npy", "filter_summary.npy", "cbf_counts_sample.npy", "cbf_counts_sample_first.npy"}, sorted(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        st = files["add_stats.npy"]
+        assert st.shape == (2, 3) and st[:, 1].sum() == j["config"]["kmers_per_step"] and st[:, 2].sum() == j["config"]["read_pairs_per_step"]
+        assert files["filter_summary.npy"].shape == (3, 6) and (files["filter_summary.npy"][:, 2] > 0).all()
+        assert files["cbf_counts_sample.npy"].max() > 0
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
 
 
 def test_force_sharded_line_goes_through_the_native_rccl_driver_by_default():
