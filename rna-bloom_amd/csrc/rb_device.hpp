@@ -168,7 +168,7 @@ struct Npf {
 };
 // What an entry remembers: the exponent (min counter >> 3) - 1 = 1..14 of the k-mer's counting-Bloom minimum — or that the minimum
 // stands at 127, where MiniFloat.increment changes nothing any more (R/util/MiniFloat.java:32): EVERY further occurrence of such a
-// k-mer is a no-op.  (Config 2's most expressed transcripts get there within the first pass; capped at exponent 7 their k-mers
+// k-mer is a no-op.  (Config 2's most expressed transcripts end at 123, the top exponent; capped at exponent 7 their k-mers
 // kept 1/128 of their occurrences: up to 29 000 records per k-mer and sub-batch, 7 % of all sorted records.)
 constexpr uint32_t RB_EXP_SATURATED = 15u;
 __host__ __device__ __forceinline__ uint32_t cache_exp(uint32_t mn) { return mn >= 127u ? RB_EXP_SATURATED : (mn >> 3) - 1u; }

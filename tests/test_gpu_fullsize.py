@@ -58,6 +58,12 @@ def test_config2_full_size_properties(monkeypatch):
     ref = {w: ga.exportFilter(w) for w in (N.DBGBF, N.CBF, N.RPKBF)}
     pop = {w: ga.popcount(w) for w in (N.DBGBF, N.CBF, N.RPKBF)}
 
+    # the top of the counting filter: no byte above 127 (bit 7 is the sub-batch claim mark and must be gone), and the most
+    # expressed transcripts end at 123 after the two files (measured; the engine is exact, so this is the oracle's maximum too —
+    # tests/test_gpu_counter_ceiling.py takes counters to 127 itself)
+    top = int(ref[N.CBF].max())
+    assert top == 123, "counting-filter maximum %d" % top
+
     # occupancy
     assert 0 < ga.getDbgbfFPR() < FPR and 0 < ga.getCbfFPR() < FPR and 0 < ga.getRpkbfFPR() < FPR
 
@@ -95,4 +101,5 @@ def test_config2_full_size_properties(monkeypatch):
     assert np.array_equal(ga.exportFilter(N.RPKBF), ref[N.RPKBF])
     cbf2 = ga.exportFilter(N.CBF)
     assert bool(np.all(cbf2 >= ref[N.CBF])) and int((cbf2 > ref[N.CBF]).sum()) > 100_000_000
+    assert int(cbf2.max()) <= 127
     ga.destroy()

@@ -132,6 +132,70 @@ def test_minifloat():
     assert L.rbo_rng31(5, 3, 4) == L.rbo_rng31(5, 3, 4) != L.rbo_rng31(6, 3, 4)
 
 
+def test_cbf_increment_past_the_ceiling_matches_a_restatement():
+    """rbo_cbf_increment_and_get from 0 past 127 against a plain restatement of MiniFloat.increment / toFloat
+    (R/util/MiniFloat.java:31-45) and CountingBloomFilter.increment (R/bloom/CountingBloomFilter.java:170-194): the minimum
+    over the counters, one MiniFloat step on it with Java's `draw % (1 << s) == 0`, then only the counters that EQUAL the
+    minimum move; at 127 nothing moves.  One single-counter key, and a two-counter key whose counters start unequal (a second
+    key shares one of them and is driven first), both with the same rbo_rng31 draws the graph uses."""
+    import ctypes as C
+    L = rbo.lib()
+
+    def inc(b, draw):                                               # MiniFloat.increment on a signed byte
+        if b <= 7:
+            return b + 1
+        if b < 127 and draw % (1 << ((b >> 3) - 1)) == 0:
+            return b + 1
+        return b
+
+    def to_float(b):
+        return float(b) if b <= 7 else float(((b & 7) | 8) * 2.0 ** ((b >> 3) - 1))
+
+    size = 101
+    idx = lambda h: (h >> 1) % size                                 # (hashVal >>> 1) % size
+    hv = lambda *xs: np.array(xs, np.uint64)
+    keys = {"single": hv(2 * 7), "shared": hv(2 * 3, 2 * 40), "pair": hv(2 * 3, 2 * 55)}
+    assert idx(2 * 3) == 3 and idx(2 * 40) == 40 and idx(2 * 55) == 55
+
+    for nh, schedule in ((1, [("single", 300_000)]), (2, [("shared", 20_000), ("pair", 300_000), ("shared", 300_000)])):
+        oc = L.rbo_cbf_new(size, nh)
+        mine = [0] * size
+        ordinal = 0
+        reached = {}
+        for name, n in schedule:
+            h = keys[name]
+            ptr = rbo._p(h)
+            cells = [idx(int(x)) for x in h[:nh]]
+            for _ in range(n):
+                draw = L.rbo_rng31(11, ordinal, 0)
+                mn = min(mine[c] for c in cells)
+                up = inc(mn, draw)
+                if up != mn:
+                    for c in cells:
+                        if mine[c] == mn:
+                            mine[c] = up
+                got = L.rbo_cbf_increment_and_get(oc, ptr, draw)
+                assert got == to_float(up), (name, ordinal, mn, got)
+                if up == 127 and name not in reached:
+                    reached[name] = ordinal
+                ordinal += 1
+            n_ = C.c_int64()
+            raw = np.ctypeslib.as_array(C.cast(L.rbo_cbf_bytes(oc, C.byref(n_)), C.POINTER(C.c_uint8)), (n_.value,)).copy()
+            assert raw.tolist() == mine, (name, [(i, raw[i], mine[i]) for i in range(size) if raw[i] != mine[i]][:4])
+            assert L.rbo_cbf_get_count(oc, ptr) == to_float(min(mine[c] for c in cells))
+        if nh == 1:
+            assert mine[7] == 127 and sum(mine) == 127 and 50_000 < reached["single"] < 300_000
+        else:
+            # the shared counter ran ahead, the pair's own counter caught up with it, both stopped at 127 and the
+            # shared key's other counter followed them there
+            assert mine[3] == mine[55] == mine[40] == 127 and sum(mine) == 3 * 127
+            assert reached["pair"] < reached["shared"]
+        L.rbo_cbf_free(oc)
+    # the graph's counting-filter adds use the same step: a saturated k-mer's count stays at toFloat(127)
+    assert L.rbo_minifloat_to_float(127) == to_float(127) == 245760.0
+    assert L.rbo_minifloat_to_float(126) == to_float(126) == 229376.0 and L.rbo_minifloat_to_float(120) == 131072.0
+
+
 def test_expected_size():
     L = rbo.lib()
     assert L.rbo_expected_size(1000000, 0.01, 2) == int(np.ceil(1000000 * 18.982443385784062))
