@@ -200,6 +200,44 @@ int rb_graph_kmers(rb_graph *g, const char *seq, const int64_t *offsets, int64_t
  * oracle's (tests/test_gpu_queries.py). */
 int rb_graph_batch_counts(rb_graph *g, const rb_batch *b, int64_t first, int64_t n, const int64_t *koffsets, float *out,
                           int out_on_device, int64_t *stride_out);
+
+/* Coverage statistics of segments of the count profile of resident reads — what stage 2 reduces every read's sorted getKmers counts
+ * to before it decides whether the read needs the corrector (R/RNABloom.java:1980-2015 single-end worker, :2097-2170 FragmentAssembler,
+ * :3788-3800 long reads).  The counts are rb_graph_batch_counts' (0 for a window with an unusable base; create the batch without a
+ * quality threshold).  A segment is a range of consecutive windows of one read; with covs its n counts sorted ascending:
+ *   n_solid          windows with count >= min_kmer_cov                                  (R/util/GraphUtils.java:3099-3108)
+ *   min q1 median q3 max, dropoff   getCoverageStats(..., calcDropOff = true)            (GraphUtils.java:1799-1845)
+ *   se_threshold, RB_COV_SE_FOUND   the threshold search of correctErrorsSE: nFP = Math.round(n * cov_fpr), start n-1-nFP, strict
+ *                    `>`; not found: covs[0], or 0 when start < 0                       (GraphUtils.java:4007-4034)
+ *   pe_threshold, RB_COV_PE_FOUND   mates only: first-round threshold search of correctErrorsPE for this mate, nFP from
+ *                    max(n, n of the other mate), `>=`; not found: covs[0].  The caller combines the two mates as :4126-4142 do
+ *   n_complex        reads mode only: usable windows whose k bases are not SeqUtils.isRepeat (SeqUtils.java:458-497, U as T)
+ * An empty segment (n = 0) has every float 0, no flag and n_complex 0.  Arithmetic is the Java float32 arithmetic, ties included.
+ * Segmentations: RB_COV_READS, one segment per read (seg_offsets[i] = i); RB_COV_WINDOWS, the first pass of
+ * correctLongSequenceWindowed (GraphUtils.java:3110-3140): i = 0; end = min(i + window, n); if end + window/2 >= n then end = n;
+ * next i = end.  A window's threshold there is `dropoff > 0 ? max(dropoff, min_kmer_cov) : median`, used only when the window has at
+ * least `lookahead` k-mers.  seg_offsets (host, n + 1 entries, required for windows): the records of read first + i are
+ * [seg_offsets[i], seg_offsets[i+1]).  out == NULL: only seg_offsets is filled (a size query).  mates != NULL (reads mode only):
+ * read mate_first + i of `mates` is read first + i's mate, its record is out[n + i].  out_on_device != 0: `out` is device memory of
+ * the graph's device.  The call works in pieces of bounded device scratch; a host `out` is pinned for the call and each piece's
+ * copy overlaps the next piece's kernels.  Refused like rb_graph_batch_counts: shard handles, batches on another device, a
+ * destroyed counting filter, ranges outside a batch, parameters out of range. */
+enum { RB_COV_READS = 0, RB_COV_WINDOWS = 1 };
+#define RB_COV_SE_FOUND 1u
+#define RB_COV_PE_FOUND 2u
+typedef struct rb_cov_params {          /* the reference's worker fields */
+    int32_t segments;                   /* RB_COV_READS | RB_COV_WINDOWS */
+    int32_t window;                     /* windowSize (RB_COV_WINDOWS), >= 1 */
+    int32_t lookahead;                  /* >= 1 */
+    float max_cov_gradient, cov_fpr, min_kmer_cov;   /* finite; max_cov_gradient >= 0, 0 <= cov_fpr <= 1 */
+} rb_cov_params;
+typedef struct rb_cov_stats {           /* 48 bytes, one per segment */
+    int32_t n, n_solid, n_complex;
+    uint32_t flags;                     /* RB_COV_SE_FOUND | RB_COV_PE_FOUND */
+    float min, q1, median, q3, max, dropoff, se_threshold, pe_threshold;
+} rb_cov_stats;
+int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_t n, const rb_batch *mates, int64_t mate_first,
+                           const rb_cov_params *p, int64_t *seg_offsets, rb_cov_stats *out, int out_on_device);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

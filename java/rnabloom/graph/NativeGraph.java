@@ -87,6 +87,12 @@ public final class NativeGraph {
      *  (koffsets[n + 1], koffsets[0] = 0), or — koffsets == null — rows of the returned stride (longest read - k + 1), zero-padded.
      *  Call with n = 0 to learn the stride before allocating `out`. */
     public static native long batchCounts(long h, long batch, long first, long n, long[] koffsets, float[] out);
+    /** Coverage statistics of the count profile of reads [first, first + n) of a resident batch (rb_graph_read_coverage): segments READS (0)
+     *  or WINDOWS (1, windowSize = window); mates != 0 (READS only): a batch whose read mateFirst + i is read first + i's mate.  out holds
+     *  12 ints per record (n, nSolid, nComplex, flags, then min q1 median q3 max dropoff seThreshold peThreshold as raw float bits);
+     *  out == null fills segOffsets[n + 1] only.  Returns the number of records. */
+    public static native long readCoverage(long h, long batch, long first, long n, long mates, long mateFirst, int segments, int window,
+                                           int lookahead, float maxCovGradient, float covFPR, float minKmerCov, long[] segOffsets, int[] out);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

@@ -336,6 +336,22 @@ jlong FN(batchCounts)(JNIEnv *e, jclass c, jlong h, jlong batch, jlong first, jl
     if (rc) throw_rc(e, rc);
     return (jlong)stride;
 }
+/* rb_graph_read_coverage: 12 ints per record in `out` (the rb_cov_stats fields in order, floats as Float.floatToRawIntBits); out == null
+ * fills segOffsets only.  Returns the number of records (segments, plus n with mates). */
+jlong FN(readCoverage)(JNIEnv *e, jclass c, jlong h, jlong batch, jlong first, jlong n, jlong mates, jlong mateFirst, jint segments, jint window,
+                       jint lookahead, jfloat maxCovGradient, jfloat covFPR, jfloat minKmerCov, jlongArray segOffsets, jintArray out) {
+    rb_cov_params p;
+    jlong *so = la(e, segOffsets);
+    jint *po = ia(e, out);
+    (void)c;
+    p.segments = segments; p.window = window; p.lookahead = lookahead;
+    p.max_cov_gradient = maxCovGradient; p.cov_fpr = covFPR; p.min_kmer_cov = minKmerCov;
+    int rc = rb_graph_read_coverage(G(h), B(batch), first, n, mates ? B(mates) : NULL, mateFirst, &p, (int64_t *)so, (rb_cov_stats *)po, 0);
+    const jlong records = rc == 0 && so && n >= 0 ? so[n] + (mates ? n : 0) : 0;
+    lr(e, segOffsets, so, 0); ir(e, out, po, 0);
+    if (rc) throw_rc(e, rc);
+    return records;
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

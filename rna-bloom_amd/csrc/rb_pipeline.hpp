@@ -538,6 +538,8 @@ void shard_query_make_dev(rb_graph *g, int what, int which_bits, size_t n, int64
 const void *shard_query_combine_dev(rb_graph *g, int which_bits, const void *breply_dev, const void *creply_dev);
 void trav_free(rb_graph *g);    // rb_query.hip: state of a traversal on a sharded graph
 void cbf_counts_device(rb_graph *g, const uint64_t *d_h0, size_t n, float *d_out);   // rb_query.hip
+void launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, uint32_t r_first, const int64_t *koff,   // rb_query.hip: k_batch_counts
+                         int64_t row_base, float *dst, hipStream_t s);                                                   // with packed rows
 void launch_pairs(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, int mode_hash, const uint32_t *chunk_off,
                   uint64_t *out_idx, unsigned long long *n_pairs_dev, hipStream_t st = nullptr, const BitFilter *into = nullptr /* another bit array of the pair filter's geometry (the sharded engine's accumulation copy) */);
 }  // namespace rb

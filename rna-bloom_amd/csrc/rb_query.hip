@@ -684,6 +684,16 @@ __global__ void k_lta_resolve(Mod mod, int num_hash, uint64_t kmul, const uint64
 
 }  // namespace
 
+// the count profile of reads [r_first, r_first + ...) of b whose words are [w0, w0 + nw), as rb_graph_batch_counts launches it with
+// packed rows: count of window p of read r at dst[koff[r - r_first] + p - row_base] (rb_coverage.hip fills its pieces through this)
+void rb::launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, uint32_t r_first, const int64_t *koff,
+                             int64_t row_base, float *dst, hipStream_t s) {
+    if (nw > 0)
+        hipLaunchKernelGGL(k_batch_counts, dim3(blocks_for(nw, 256)), dim3(256), 0, s, g->view(0, 0), (int)g->stranded, b->codes, b->valid,
+                           b->word_read, b->woff, b->len, w0, nw, r_first, g->k, koff, (int64_t)0, row_base, dst);
+    RB_HIP(hipGetLastError());
+}
+
 using rb::HostPin;
 extern "C" {
 int rb_filter_lookup(rb_graph *g, int which, const uint64_t *h0, size_t n, uint8_t *out) {

@@ -41,6 +41,24 @@ class SynthParams(C.Structure):
                 ("tx_min", C.c_int32), ("tx_max", C.c_int32), ("pair_offset", C.c_int64), ("total_pairs", C.c_int64)]
 
 
+COV_READS, COV_WINDOWS = 0, 1
+COV_SE_FOUND, COV_PE_FOUND = 1, 2
+
+
+class CovParams(C.Structure):
+    _fields_ = [("segments", C.c_int32), ("window", C.c_int32), ("lookahead", C.c_int32),
+                ("max_cov_gradient", C.c_float), ("cov_fpr", C.c_float), ("min_kmer_cov", C.c_float)]
+
+
+class CovStats(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_solid", C.c_int32), ("n_complex", C.c_int32), ("flags", C.c_uint32),
+                ("min", C.c_float), ("q1", C.c_float), ("median", C.c_float), ("q3", C.c_float), ("max", C.c_float),
+                ("dropoff", C.c_float), ("se_threshold", C.c_float), ("pe_threshold", C.c_float)]
+
+
+assert C.sizeof(CovParams) == 24 and C.sizeof(CovStats) == 48
+
+
 class Profile(C.Structure):
     _fields_ = [("n", C.c_int32), ("name", C.c_char_p * PROF_MAX), ("ms", C.c_double * PROF_MAX),
                 ("launches", C.c_int64 * PROF_MAX)]
@@ -78,6 +96,7 @@ SYMBOLS = [
     ("rb_filter_get_count", _i32, [_vp, _vp, _sz, _vp]),
     ("rb_graph_kmers", _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("rb_graph_batch_counts", _i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
+    ("rb_graph_read_coverage", _i32, [_vp, _vp, _i64, _i64, _vp, _i64, C.POINTER(CovParams), _vp, _vp, _i32]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

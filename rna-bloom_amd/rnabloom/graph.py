@@ -434,6 +434,35 @@ class BloomFilterDeBruijnGraph:
         check(lib.rb_graph_batch_counts(self.h, batch.h, first, n, _ptr(ko) if ko is not None else None, C.c_void_p(out.data_ptr()), 1, None))
         return out
 
+    COV_DTYPE = np.dtype([("n", "<i4"), ("n_solid", "<i4"), ("n_complex", "<i4"), ("flags", "<u4"), ("min", "<f4"), ("q1", "<f4"),
+                          ("median", "<f4"), ("q3", "<f4"), ("max", "<f4"), ("dropoff", "<f4"), ("se_threshold", "<f4"), ("pe_threshold", "<f4")])
+
+    def coverageStats(self, batch, first=0, n=None, mates=None, mate_first=0, window=0, lookahead=3, maxCovGradient=0.5, covFPR=0.0,
+                      minKmerCov=1.0, to_host=True):
+        """Coverage statistics of the count profile of reads [first, first + n) of a resident ReadBatch (rb_graph_read_coverage): one
+        record (COV_DTYPE) per segment — per read, or with window > 0 per window of correctLongSequenceWindowed's first pass.
+        Returns (records, seg_offsets): the records of read first + i are records[seg_offsets[i]:seg_offsets[i + 1]].  With mates (a
+        ReadBatch whose read mate_first + i is read first + i's mate; reads mode only) the mates' records follow at records[n + i], and a
+        third value is returned: the pair's threshold as correctErrorsPE combines the two mates (R/util/GraphUtils.java:4126-4142), -1
+        where there is none.  to_host False: the records stay on the device, a torch uint8 tensor of 48 bytes per record."""
+        n = batch.n_reads - first if n is None else n
+        p = N.CovParams(N.COV_WINDOWS if window else N.COV_READS, window, lookahead, maxCovGradient, covFPR, minKmerCov)
+        mh = mates.h if mates is not None else None
+        so = np.zeros(n + 1, np.int64)
+        check(lib.rb_graph_read_coverage(self.h, batch.h, first, n, mh, mate_first, C.byref(p), _ptr(so), None, 0))
+        n_rec = int(so[-1]) + (n if mates is not None else 0)
+        if to_host:
+            rec = np.zeros(n_rec, self.COV_DTYPE)
+            check(lib.rb_graph_read_coverage(self.h, batch.h, first, n, mh, mate_first, C.byref(p), _ptr(so), _ptr(rec), 0))
+        else:
+            import torch
+            rec = torch.zeros(n_rec * self.COV_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % self.device)
+            check(lib.rb_graph_read_coverage(self.h, batch.h, first, n, mh, mate_first, C.byref(p), _ptr(so), C.c_void_p(rec.data_ptr()), 1))
+        if mates is None:
+            return rec, so
+        h = rec if to_host else rec.cpu().numpy().view(self.COV_DTYPE)
+        return rec, so, pair_threshold(h[:n], h[n:])
+
     def getNeighbors(self, f, r, charOut, direction):
         """4 successors (direction 0) / predecessors (1) of each k-mer: (f4, r4, count4) shaped [n,4]."""
         f = _u64(np.atleast_1d(f)); r = _u64(np.atleast_1d(r))
@@ -747,6 +776,17 @@ class _FilterOfGraph:
 
 
 # ---- sketching (BASELINE config 5): hash-only, no graph needed ----
+def pair_threshold(left, right):
+    """correctErrorsPE's threshold for a pair from its two mates' first-round searches (R/util/GraphUtils.java:4126-4142): both found ->
+    the smaller; one found -> its threshold if it is <= the other mate's; else -1.  left / right: coverageStats records (numpy)."""
+    lf = (left["flags"] & N.COV_PE_FOUND) != 0
+    rf = (right["flags"] & N.COV_PE_FOUND) != 0
+    lt, rt = left["pe_threshold"], right["pe_threshold"]
+    none = np.float32(-1)
+    return np.where(lf & rf, np.minimum(lt, rt),
+                    np.where(lf, np.where(lt <= rt, lt, none), np.where(rf & (rt <= lt), rt, none))).astype(np.float32)
+
+
 def _pack(reads):
     lens = np.fromiter((len(r) for r in reads), np.int64, len(reads))
     off = np.zeros(len(reads) + 1, np.int64)
