@@ -238,6 +238,36 @@ typedef struct rb_cov_stats {           /* 48 bytes, one per segment */
 } rb_cov_stats;
 int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_t n, const rb_batch *mates, int64_t mate_first,
                            const rb_cov_params *p, int64_t *seg_offsets, rb_cov_stats *out, int out_on_device);
+
+/* Paired-k-mer segmentation of host sequences — GraphUtils.breakWithReadPairedKmers (R/util/GraphUtils.java:4184-4310, the range form and
+ * the whole-list form) and breakWithFragPairedKmers (:4312-4405, with and without numPairsRequired), which FragmentAssembler runs on every
+ * connected fragment (R/RNABloom.java:2185-2200, 2215-2232) and transcript assembly on every fragment (:1855-1890).
+ *   Input: sequence i is seq[offsets[i], offsets[i+1]); its k-mer list is getKmers' (every window, nk = max(0, len - k + 1); a letter
+ *   outside ACGTU hashes as seed 0 forward and with the `ch & 7` seed on the reverse strand, as rb_graph_kmers).
+ *   Pair key of position p (d = the graph's read- or fragment-paired k-mer distance): Kmer.getKmerPairHashValue (R/graph/Kmer.java:65-67,
+ *   CanonicalKmer.java:61-72): stranded combine(f[p], f[p+d]), canonical the signed min(combine(f[p], f[p+d]), combine(r[p+d], r[p]));
+ *   support[p] = the pair filter's lookup of that key (lookupReadKmerPair / lookupFragmentKmerPair, BloomFilterDeBruijnGraph.java:526-532).
+ *   Segments: the reference's loop with interlockDistance = 0 over p in [rangeStart, lastIndex], lastIndex = rangeEnd - 1 - d.  A run of
+ *   num_pairs_required consecutive supported positions ending at p opens a segment at p - num_pairs_required + 1 (if none is open), and
+ *   every such p sets end = p + d; any unsupported p resets the run and closes the open segment only when p >= end.  A segment still open
+ *   after the loop is emitted too.  Segments are [start, end + 1) in k-mer indices, in the reference's order.  num_pairs_required = 1 is
+ *   the reference's first branch; breakWithFragPairedKmers(kmers, graph) is num_pairs_required = 1 on RB_FPKBF.
+ *   ranges: NULL = [0, nk) for every sequence (the whole-list forms), else 2n ints [rangeStart, rangeEnd), 0 <= start <= end <= nk.
+ *   seg_offsets (host, n + 1): capacity layout from the lengths alone.  Consecutive segment starts are at least d + 1 apart, so sequence i
+ *   gets max(0, floor((rangeEnd - 1 - d - rangeStart) / (d + 1)) + 1) slots of 2 ints at segs + 2 * seg_offsets[i]; n_segs[i] = how many
+ *   it filled.  koffsets (host, n + 1, optional): getKmers' k-mer offsets.  support (optional, requires koffsets): one byte per k-mer of
+ *   sequence i at support[koffsets[i] + p], 1 where position p is supported, 0 where it is not or p + d >= nk (rows of the whole list,
+ *   whatever the range).  segs == NULL: only seg_offsets (and koffsets) are filled and nothing is launched (a size query).
+ * The call works in pieces of bounded device scratch (RB_QUERY_PIECE k-mers, as rb_graph_kmers); results do not depend on the cuts.  Without
+ * `support`, pair positions outside every range are not probed (64 at a time).  With rb_graph_profile_enable on, the kernels' device time
+ * is added to the profile entry "pair_segments".  RB_ERR_STATE: a sequence produced more segments than its slots (an internal error; the
+ * bound above makes it impossible).
+ * Refused (RB_ERR_INVALID, nothing launched): a shard handle; `which` not RB_RPKBF / RB_FPKBF, or a pair filter the graph does not have
+ * (useReadPairedKmers off; rb_graph_init_fragment_pairs never called); a distance < 1; num_pairs_required < 1; a range outside [0, nk] or
+ * with start > end; null arrays. */
+int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const int64_t *offsets, int64_t n, int num_pairs_required,
+                                  const int32_t *ranges, int64_t *seg_offsets, int32_t *segs, int32_t *n_segs, uint8_t *support,
+                                  int64_t *koffsets);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

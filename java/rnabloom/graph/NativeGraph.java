@@ -93,6 +93,13 @@ public final class NativeGraph {
      *  out == null fills segOffsets[n + 1] only.  Returns the number of records. */
     public static native long readCoverage(long h, long batch, long first, long n, long mates, long mateFirst, int segments, int window,
                                            int lookahead, float maxCovGradient, float covFPR, float minKmerCov, long[] segOffsets, int[] out);
+    /** Paired-k-mer segments of n sequences (rb_graph_paired_kmer_segments; GraphUtils.breakWithReadPairedKmers / breakWithFragPairedKmers,
+     *  R/util/GraphUtils.java:4184-4405): which = RPKBF (2) or FPKBF (3); ranges = null for whole k-mer lists, else 2n ints [rangeStart,
+     *  rangeEnd).  segOffsets[n + 1] is filled from the lengths alone; segment j of sequence i is segs[2 * (segOffsets[i] + j)] .. + 1
+     *  ([start, end) in k-mer indices) for j < nSegs[i].  segs == null sizes the outputs only.  support (with koffsets[n + 1]): one byte per
+     *  k-mer, 1 where the pair at that position is in the filter.  Returns the number of segment slots. */
+    public static native long pairedKmerSegments(long h, int which, ByteBuffer seq, long[] offsets, int n, int numPairsRequired, int[] ranges,
+                                                 long[] segOffsets, int[] segs, int[] nSegs, byte[] support, long[] koffsets);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

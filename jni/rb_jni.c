@@ -352,6 +352,22 @@ jlong FN(readCoverage)(JNIEnv *e, jclass c, jlong h, jlong batch, jlong first, j
     if (rc) throw_rc(e, rc);
     return records;
 }
+/* rb_graph_paired_kmer_segments: segs holds 2 ints per slot at 2 * segOffsets[i], nSegs[i] of them filled; ranges == null = whole lists;
+ * segs == null fills segOffsets (and koffsets) only; support (with koffsets) gets one byte per k-mer.  Returns the number of slots. */
+jlong FN(pairedKmerSegments)(JNIEnv *e, jclass c, jlong h, jint which, jobject seq, jlongArray offsets, jint n, jint numPairsRequired,
+                             jintArray ranges, jlongArray segOffsets, jintArray segs, jintArray nSegs, jbyteArray support, jlongArray koffsets) {
+    jlong *off = la(e, offsets), *so = la(e, segOffsets), *ko = la(e, koffsets);
+    jint *rg = ia(e, ranges), *ps = ia(e, segs), *pn = ia(e, nSegs);
+    jbyte *sup = ba(e, support);
+    (void)c;
+    int rc = rb_graph_paired_kmer_segments(G(h), which, (const char *)direct(e, seq), (const int64_t *)off, n, numPairsRequired, (const int32_t *)rg,
+                                           (int64_t *)so, (int32_t *)ps, (int32_t *)pn, (uint8_t *)sup, (int64_t *)ko);
+    const jlong slots = rc == 0 && so && n >= 0 ? so[n] : 0;
+    lr(e, offsets, off, JNI_ABORT); ir(e, ranges, rg, JNI_ABORT); lr(e, segOffsets, so, 0); ir(e, segs, ps, 0); ir(e, nSegs, pn, 0);
+    br(e, support, sup, 0); lr(e, koffsets, ko, 0);
+    if (rc) throw_rc(e, rc);
+    return slots;
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

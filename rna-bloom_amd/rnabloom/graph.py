@@ -463,6 +463,48 @@ class BloomFilterDeBruijnGraph:
         h = rec if to_host else rec.cpu().numpy().view(self.COV_DTYPE)
         return rec, so, pair_threshold(h[:n], h[n:])
 
+    def pairedKmerSegmentsFlat(self, which, seq, offsets, numPairsRequired=1, ranges=None, support=False):
+        """rb_graph_paired_kmer_segments on flat host text: sequence i is seq[offsets[i]:offsets[i + 1]] (uint8).  ranges: None (whole
+        k-mer lists) or an [n, 2] int array of [rangeStart, rangeEnd).  Returns (seg_offsets, segs, n_segs, koffsets, support_bytes): the
+        segments of sequence i are segs[seg_offsets[i]:seg_offsets[i] + n_segs[i]] ([n, 2] int32, [start, end) in k-mer indices);
+        support_bytes (None unless asked for) holds one byte per k-mer at koffsets[i] + p."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        rg = None if ranges is None else np.ascontiguousarray(ranges, dtype=np.int32).reshape(n * 2)
+        so = np.zeros(n + 1, np.int64); ko = np.zeros(n + 1, np.int64)
+        args = (self.h, which, _ptr(seq), _ptr(off), n, numPairsRequired, _ptr(rg), _ptr(so))
+        check(lib.rb_graph_paired_kmer_segments(*args, None, None, None, _ptr(ko)))
+        segs = np.zeros((int(so[-1]), 2), np.int32); ns = np.zeros(n, np.int32)
+        sup = np.zeros(int(ko[-1]), np.uint8) if support else None
+        check(lib.rb_graph_paired_kmer_segments(*args, _ptr(segs), _ptr(ns), _ptr(sup), _ptr(ko)))
+        return so, segs, ns, ko, sup
+
+    def _paired_segments(self, which, seqs, numPairsRequired, ranges):
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        so, segs, ns, _, _ = self.pairedKmerSegmentsFlat(which, seq, off, numPairsRequired, ranges)
+        return [[(int(a), int(b)) for a, b in segs[so[i]:so[i] + ns[i]]] for i in range(len(seqs))]
+
+    def breakWithReadPairedKmers(self, seqs, numPairsRequired, ranges=None):
+        """GraphUtils.breakWithReadPairedKmers (R/util/GraphUtils.java:4184-4310) of each sequence's getKmers list: per sequence the
+        [(start, end)] of the ranges read-paired k-mers support, in the reference's order.  ranges: None (the whole-list form) or one
+        (rangeStart, rangeEnd) per sequence (the range form)."""
+        return self._paired_segments(N.RPKBF, seqs, numPairsRequired, ranges)
+
+    def breakWithFragPairedKmers(self, seqs, numPairsRequired=1):
+        """GraphUtils.breakWithFragPairedKmers (:4312-4405): the same on the fragment-paired k-mer filter; numPairsRequired = 1 is the
+        two-argument form"""
+        return self._paired_segments(N.FPKBF, seqs, numPairsRequired, None)
+
+    def pairedKmerSupport(self, seqs, which=N.RPKBF):
+        """per sequence a bool array over its getKmers list: position p is True where lookupReadKmerPair (which = RPKBF) or
+        lookupFragmentKmerPair (FPKBF) of k-mers p and p + d holds — what printPairedKmersPositions prints; False where p + d is past the end"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        _, _, _, ko, sup = self.pairedKmerSegmentsFlat(which, seq, off, 1, None, support=True)
+        return [sup[ko[i]:ko[i + 1]].astype(bool) for i in range(len(seqs))]
+
     def getNeighbors(self, f, r, charOut, direction):
         """4 successors (direction 0) / predecessors (1) of each k-mer: (f4, r4, count4) shaped [n,4]."""
         f = _u64(np.atleast_1d(f)); r = _u64(np.atleast_1d(r))
