@@ -183,11 +183,6 @@ __global__ void k_synth_reads(const uint64_t *__restrict__ genome, const int64_t
     word_read[w] = (uint32_t)r;
 }
 
-struct HostGuard {   // frees partially built batches on exceptions
-    rb_batch *b;
-    ~HostGuard() { if (b) rb_batch_destroy(b); }
-};
-
 void alloc_batch_arrays(rb_batch *b) {
     size_t nw = (size_t)std::max<int64_t>(b->n_words, 1), nr = (size_t)std::max<int64_t>(b->n_reads, 1);
     if (b->pool) {
@@ -1370,32 +1365,31 @@ void launch_filter_windows(const rb_batch *b, int64_t w0, int64_t nw, int k, int
                     // in an image that is not the window's bucket misses, the window is kept, every filter byte still matches the oracle — so parity tests
                     // cannot see a broken fetch.  Here the one-step walker (and, for k <= 31, the unpipelined one) decides the same words into scratch
                     // arrays and every count, mask and resume state is compared; a difference fails the call.
-                    struct Scratch { uint32_t *c = nullptr, *m = nullptr, *t = nullptr; ulonglong2 *ws = nullptr;
-                                     ~Scratch() { (void)hipFree(c); (void)hipFree(m); (void)hipFree(t); (void)hipFree(ws); } } A, B;
+                    struct Scratch { DevBuf c, m, t, ws; } A, B;
                     const size_t nb = (size_t)nw * 4;
                     for (Scratch *x : {&A, &B}) {
-                        RB_HIP(hipMalloc(&x->c, nb)); RB_HIP(hipMalloc(&x->m, nb)); RB_HIP(hipMalloc(&x->t, 4096)); RB_HIP(hipMemsetAsync(x->t, 0, 4096, s));
-                        RB_HIP(hipMemsetAsync(x->c, 0xEE, nb, s)); RB_HIP(hipMemsetAsync(x->m, 0xEE, nb, s));
-                        if (wstate) { RB_HIP(hipMalloc(&x->ws, nb * 4)); RB_HIP(hipMemsetAsync(x->ws, 0xEE, nb * 4, s)); }
+                        x->c.reserve(nb); x->m.reserve(nb); x->t.reserve(4096); RB_HIP(hipMemsetAsync(x->t.p, 0, 4096, s));
+                        RB_HIP(hipMemsetAsync(x->c.p, 0xEE, nb, s)); RB_HIP(hipMemsetAsync(x->m.p, 0xEE, nb, s));
+                        if (wstate) { x->ws.reserve(nb * 4); RB_HIP(hipMemsetAsync(x->ws.p, 0xEE, nb * 4, s)); }
                     }
                     ulonglong2 *const ws_coop = reinterpret_cast<ulonglong2 *>(wstate);
                     {   // the one-step walker
-                        uint32_t *cnt = A.c, *keepmask = A.m, *total_spread = A.t; void *wstate = A.ws;
+                        uint32_t *cnt = A.c.as<uint32_t>(), *keepmask = A.m.as<uint32_t>(), *total_spread = A.t.as<uint32_t>(); void *wstate = A.ws.p;
                         if (wide) { if (mode == 0) RB_LAUNCH_FW(0); else if (mode == 2) RB_LAUNCH_FW(2); else RB_LAUNCH_FW(1); }
                         else { if (mode == 0) RB_LAUNCH_FN(0); else if (mode == 2) RB_LAUNCH_FN(2); else RB_LAUNCH_FN(1); }
                     }
                     if (!wide) {   // the walker that fetches in place
-                        uint32_t *cnt = B.c, *keepmask = B.m, *total_spread = B.t; void *wstate = B.ws;
+                        uint32_t *cnt = B.c.as<uint32_t>(), *keepmask = B.m.as<uint32_t>(), *total_spread = B.t.as<uint32_t>(); void *wstate = B.ws.p;
                         if (mode == 0) RB_LAUNCH_FC(0, true); else if (mode == 2) RB_LAUNCH_FC(2, true); else RB_LAUNCH_FC(1, true);
                     }
                     std::vector<uint32_t> hc(nw), hm(nw), ac(nw), am(nw), bc(nw), bm(nw);
                     std::vector<unsigned long long> hw, aw;
                     RB_HIP(hipMemcpyAsync(hc.data(), cnt, nb, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(hm.data(), keepmask, nb, hipMemcpyDeviceToHost, s));
-                    RB_HIP(hipMemcpyAsync(ac.data(), A.c, nb, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(am.data(), A.m, nb, hipMemcpyDeviceToHost, s));
-                    RB_HIP(hipMemcpyAsync(bc.data(), B.c, nb, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(bm.data(), B.m, nb, hipMemcpyDeviceToHost, s));
+                    RB_HIP(hipMemcpyAsync(ac.data(), A.c.p, nb, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(am.data(), A.m.p, nb, hipMemcpyDeviceToHost, s));
+                    RB_HIP(hipMemcpyAsync(bc.data(), B.c.p, nb, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(bm.data(), B.m.p, nb, hipMemcpyDeviceToHost, s));
                     if (wstate) {
                         hw.resize((size_t)nw * 2); aw.resize((size_t)nw * 2);
-                        RB_HIP(hipMemcpyAsync(hw.data(), ws_coop, nb * 4, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(aw.data(), A.ws, nb * 4, hipMemcpyDeviceToHost, s));
+                        RB_HIP(hipMemcpyAsync(hw.data(), ws_coop, nb * 4, hipMemcpyDeviceToHost, s)); RB_HIP(hipMemcpyAsync(aw.data(), A.ws.p, nb * 4, hipMemcpyDeviceToHost, s));
                     }
                     RB_HIP(hipStreamSynchronize(s));
                     int64_t bad = 0, first = -1;
@@ -1656,8 +1650,8 @@ int rb_batch_create_synthetic(int device, const rb_synth_params *p, rb_batch **o
         for (size_t i = 0; i < tlen.size(); ++i) { acc += wgt[i] / tot; cdf[i] = (float)acc; }
         cdf.back() = 2.0f;
 
-        rb_batch *b = new rb_batch();
-        HostGuard guard{b};
+        rb::BatchPtr owner(new rb_batch());   // frees a partially built batch on exceptions
+        rb_batch *b = owner.get();
         b->device = device;
         b->n_reads = 2 * p->n_pairs;
         int wpr = (p->read_len + 31) / 32;
@@ -1708,8 +1702,7 @@ int rb_batch_create_synthetic(int device, const rb_synth_params *p, rb_batch **o
         if (d_tl) (void)hipFree(d_tl);
         if (d_cdf) (void)hipFree(d_cdf);
         RB_HIP(err);
-        guard.b = nullptr;
-        *out = b;
+        *out = owner.release();
         return RB_OK;
     } catch (const HipError &e) { return e.code; }
     catch (const std::bad_alloc &) { set_error("host allocation failed"); return RB_ERR_NOMEM; }
@@ -1729,7 +1722,6 @@ int rb_nthash_batch(const rb_batch *b, int k, int mode, int64_t first, int64_t n
         int64_t w0 = wo[0], nw = (int64_t)wo[1] - wo[0];
         if (nw == 0) return RB_OK;
         DevBuf cnt, off, tmp, keys, rd, ps;
-        struct Rel { DevBuf *b[6]; ~Rel() { for (auto x : b) x->release(); } } rel{{&cnt, &off, &tmp, &keys, &rd, &ps}};
         cnt.reserve(((size_t)nw + 1) * 4); off.reserve(((size_t)nw + 1) * 4);
         RB_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)nw + 1) * 4, 0));
         launch_count_windows(b, w0, nw, k, cnt.as<uint32_t>(), 0);

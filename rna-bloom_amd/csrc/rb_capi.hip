@@ -133,24 +133,24 @@ int rb_graph_create(const rb_graph_params *p, rb_graph **out) {
         if (const char *e = getenv("RB_SMALL_COMPONENT_OPS")) g->small_ops = (uint32_t)std::max(1, atoi(e));
         if (const char *e = getenv("RB_SORT_BEGIN_BIT")) g->sort_begin_bit = std::max(0, std::min(63, atoi(e)));
         RB_REQUIRE(g->max_batch_kmers <= ((int64_t)1 << 31), "rb_graph_create: max_batch_kmers above 2^31");
-        if (const char *e = getenv("RB_CONSUMER_PRIORITY")) RB_HIP(hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, atoi(e)));
-        else RB_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+        if (const char *e = getenv("RB_CONSUMER_PRIORITY")) RB_HIP(hipStreamCreateWithPriority(&g->stream.s, hipStreamNonBlocking, atoi(e)));
+        else RB_HIP(hipStreamCreateWithFlags(&g->stream.s, hipStreamNonBlocking));
         {   // the producer (hash + sort of the next sub-batch) is the critical path: give it priority
             int lo_p = 0, hi_p = 0;
             RB_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
             int pr = hi_p;
             if (const char *e = getenv("RB_PRODUCER_PRIORITY")) pr = atoi(e);
-            RB_HIP(hipStreamCreateWithPriority(&g->stream2, hipStreamNonBlocking, pr));
-            RB_HIP(hipStreamCreateWithPriority(&g->stream3, hipStreamNonBlocking, pr));
+            RB_HIP(hipStreamCreateWithPriority(&g->stream2.s, hipStreamNonBlocking, pr));
+            RB_HIP(hipStreamCreateWithPriority(&g->stream3.s, hipStreamNonBlocking, pr));
         }
         // the packed ingest's copy stream (rb_packed.hip) is created HERE, not at the first upload: HIP hands its streams to a few hardware queues in the
         // order they are made, and a copy stream made after a query context's stream (rb_filter_fold before the first rb_graph_add_packed was enough)
         // shared a queue with the insert's kernels — its pieces queued behind them, 10 ms of every 300 ms step (tools/host_gap.py, HISTORY "Round 6")
-        RB_HIP(hipStreamCreateWithFlags(&g->pk_stream, hipStreamNonBlocking));
-        RB_HIP(hipEventCreate(&g->ev0));
-        RB_HIP(hipEventCreate(&g->ev1));
-        RB_HIP(hipEventCreateWithFlags(&g->ev2, hipEventDisableTiming));
-        RB_HIP(hipEventCreateWithFlags(&g->ev3, hipEventDisableTiming));
+        RB_HIP(hipStreamCreateWithFlags(&g->pk_stream.s, hipStreamNonBlocking));
+        RB_HIP(hipEventCreate(&g->ev0.e));
+        RB_HIP(hipEventCreate(&g->ev1.e));
+        RB_HIP(hipEventCreateWithFlags(&g->ev2.e, hipEventDisableTiming));
+        RB_HIP(hipEventCreateWithFlags(&g->ev3.e, hipEventDisableTiming));
         alloc_bits(g->dbg, p->dbgbf_bits, p->dbgbf_num_hash, 0, p->dbgbf_bits);
         g->cbf_size = p->cbf_bytes; g->cbf_lo = 0; g->cbf_hi = p->cbf_bytes;
         g->cbf_alloc = (((size_t)p->cbf_bytes + 3) / 4 + 1) * 4;
@@ -191,47 +191,21 @@ int rb_graph_create(const rb_graph_params *p, rb_graph **out) {
 int rb_graph_destroy(rb_graph *g) {
     if (!g) return RB_OK;
     (void)hipSetDevice(g->p.device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->stream2) (void)hipStreamSynchronize(g->stream2);
-    if (g->stream3) (void)hipStreamSynchronize(g->stream3);
+    // every stream of the handle is idle before anything is freed (rb_pipeline.hpp: the order the handle's members rely on)
+    for (hipStream_t st : {(hipStream_t)g->stream, (hipStream_t)g->stream2, (hipStream_t)g->stream3, (hipStream_t)g->pk_stream})
+        if (st) (void)hipStreamSynchronize(st);
     rb::trav_free(g);
-    rb::shard_free(g);
-    free_bits(g->dbg); free_bits(g->rpk); free_bits(g->fpk);
-    if (g->cbf) (void)hipFree(g->cbf);
-    DevBuf *bufs[] = {&g->chunk_cnt, &g->chunk_off, &g->keys0,  &g->vals0,   
-                       &g->status, &g->nops, &g->temp, &g->ftable, &g->ctable, &g->heavy, &g->confk,
-                      &g->conf_sizes, &g->conf_off, &g->opk0, &g->opk1, &g->opv0, &g->opv1, &g->label, &g->kk0, &g->kk1, &g->biglist, &g->cvals, &g->foreign,  &g->devctr, &g->cwriters, &g->cshared, &g->comm_keep, &g->comm_dreply, &g->comm_creply, &g->qbuf0,
-                      &g->qbuf1, &g->qbuf2, &g->qbuf3};
-    for (auto *b : bufs) b->release();
-    for (rb_query_ctx *c : g->qfree) {
-        c->b0.release(); c->b1.release(); c->b2.release(); c->b3.release();
-        if (c->st) (void)hipStreamDestroy(c->st);
-        delete c;
-    }
-    g->qfree.clear();
-    if (g->pk_stream) (void)hipStreamSynchronize(g->pk_stream);
-    for (auto &K : g->pk) {
-        for (DevBuf *d : {&K.codes, &K.valid, &K.word_read, &K.woff, &K.len, &K.wc, &K.temp, &K.stats}) d->release();
-        if (K.h_woff) (void)hipHostFree(K.h_woff);
-        if (K.h_stats) (void)hipHostFree(K.h_stats);
-        for (auto e : K.ev) (void)hipEventDestroy(e);
-        if (K.ev_woff) (void)hipEventDestroy(K.ev_woff);
-        for (void *p : K.pins) (void)hipHostUnregister(p);
-    }
-    if (g->pk_stream) (void)hipStreamDestroy(g->pk_stream);
-    if (g->ev0) (void)hipEventDestroy(g->ev0);
-    if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->ev2) (void)hipEventDestroy(g->ev2);
-    if (g->ev3) (void)hipEventDestroy(g->ev3);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    if (g->stream2) (void)hipStreamDestroy(g->stream2);
-    if (g->stream3) (void)hipStreamDestroy(g->stream3);
-    for (auto e : g->prof_pool) (void)hipEventDestroy(e);
-    for (auto &sl : g->slots) { sl.keys1.release(); sl.valsT.release(); sl.vals1.release(); sl.tz.release(); sl.uniq.release(); sl.counts.release(); sl.starts.release(); }
-    g->temp2.release(); g->devctr2.release(); g->pairs_ctr.release(); g->npf.release(); g->mpf.release(); g->chunk_mask.release(); g->npf_tot.release(); g->wstate.release();
     delete g;
     return RB_OK;
 }
+}  // extern "C"
+// what the members do not own themselves: the shard state (defined in rb_shard.hip) and the filters, which kernels take by value
+rb_graph::~rb_graph() {
+    rb::shard_free(this);
+    free_bits(dbg); free_bits(rpk); free_bits(fpk);
+    if (cbf) (void)hipFree(cbf);
+}
+extern "C" {
 
 int rb_graph_clear(rb_graph *g, unsigned which_mask) {
     return guarded([&] {
@@ -380,7 +354,7 @@ int rb_graph_add_reads(rb_graph *g, const char *seq, const char *qual, const int
     rb::AsciiUpload up;
     if (!getenv("RB_NO_INGEST_POOL")) up.pool = &g->ingest_pool;
     hipStream_t st = nullptr;
-    bool own_stream = false;
+    rb::Stream own_stream;                                           // RB_INGEST_OWN_STREAM: this call's own instead of the handle's copy stream
     const char *pin_seq = nullptr, *pin_qual = nullptr;
     WriteLock wl(g->rw);
     int rc = guarded([&] {
@@ -404,7 +378,7 @@ int rb_graph_add_reads(rb_graph *g, const char *seq, const char *qual, const int
         }
         if (tdbg0) fprintf(stderr, "[rb] add_reads: pinning %.1f ms (seq %s, qual %s)\n", now0() - t_pin0, pin_seq ? "registered" : "not registered", pin_qual ? "registered" : "not registered");
         st = getenv("RB_INGEST_OWN_STREAM") ? nullptr : g->pk_stream;      // the handle's copy stream (made with the graph: a hardware queue of its own, rb_graph_create)
-        if (!st) { RB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); own_stream = true; }
+        if (!st) { RB_HIP(hipStreamCreateWithFlags(&own_stream.s, hipStreamNonBlocking)); st = own_stream; }
         const int64_t chunk_bases = (int64_t)256 << 20;
         auto chunk_end = [&](int64_t a) {   // largest e > a with bases(a..e) <= chunk_bases (at least one read)
             int64_t lo = a + 1, hi = n_reads;
@@ -443,7 +417,7 @@ int rb_graph_add_reads(rb_graph *g, const char *seq, const char *qual, const int
             double t2 = now(); t_beg += t2 - t1;
             int add_rc = RB_OK;
             {
-                struct G { rb_batch *b; ~G() { rb_batch_destroy(b); } } guard{b};
+                rb::BatchPtr guard(b);
                 add_rc = guarded([&] { add_range(g, b, 0, b->n_reads, flags, stats); });
                 t_add += now() - t2;
                 t2 = now();
@@ -458,7 +432,7 @@ int rb_graph_add_reads(rb_graph *g, const char *seq, const char *qual, const int
         if (tdbg) fprintf(stderr, "[rb] add_reads: wait upload %.1f ms, begin next %.1f ms, insert %.1f ms, destroy %.1f ms\n", t_fin, t_beg, t_add, t_des);
     });
     if (rc != RB_OK) rb::ascii_batch_abort(up);
-    if (st && !own_stream && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
+    if (st && !own_stream.s && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
     {
         timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
         if (pin_seq) (void)hipHostUnregister(const_cast<char *>(pin_seq));
@@ -466,7 +440,6 @@ int rb_graph_add_reads(rb_graph *g, const char *seq, const char *qual, const int
         timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
         if (getenv("RB_HOST_TIMING")) fprintf(stderr, "[rb] add_reads: unpinning %.1f ms\n", (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6);
     }
-    if (st && own_stream) (void)hipStreamDestroy(st);
     return rc;
 }
 
@@ -474,14 +447,14 @@ int rb_graph_add_fastq(rb_graph *g, const char *text, size_t len, int min_base_q
     if (!g) { set_error("rb_graph_add_fastq: null graph"); return RB_ERR_INVALID; }
     if (!text && len) { set_error("rb_graph_add_fastq: null text"); return RB_ERR_INVALID; }
     hipStream_t st = nullptr;
-    bool own_stream = false;
+    rb::Stream own_stream;                                           // RB_INGEST_OWN_STREAM: this call's own instead of the handle's copy stream
     SlabPin slabs;
     WriteLock wl(g->rw);
     int rc = guarded([&] {
         RB_HIP(hipSetDevice(g->p.device));
         slabs.begin(text, len);                                      // registered slab by slab as the pieces advance (best effort)
         st = getenv("RB_INGEST_OWN_STREAM") ? nullptr : g->pk_stream;      // the handle's copy stream (made with the graph: a hardware queue of its own, rb_graph_create)
-        if (!st) { RB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); own_stream = true; }
+        if (!st) { RB_HIP(hipStreamCreateWithFlags(&own_stream.s, hipStreamNonBlocking)); st = own_stream; }
         // pieces of 1 GiB of text; a piece starts where the complete records of the one before ended.  The next piece is
         // uploaded and parsed (helper thread, own stream) while the insert pipeline works on the current one.
         const size_t piece_bytes = getenv("RB_FASTQ_PIECE") ? (size_t)std::max(64, atoi(getenv("RB_FASTQ_PIECE"))) : (size_t)1 << 30;
@@ -494,7 +467,7 @@ int rb_graph_add_fastq(rb_graph *g, const char *text, size_t len, int min_base_q
         int64_t recs = 0;
         rb::FastqChunk cur = piece(0);
         for (;;) {
-            struct G { rb_batch *b; ~G() { if (b) rb_batch_destroy(b); } } guard{cur.b};
+            rb::BatchPtr guard(cur.b);
             recs += cur.records;
             const bool last = a + piece_bytes >= len;
             const size_t next = a + cur.consumed;
@@ -516,9 +489,8 @@ int rb_graph_add_fastq(rb_graph *g, const char *text, size_t len, int min_base_q
         }
         if (n_records) *n_records = recs;
     });
-    if (st && !own_stream && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
+    if (st && !own_stream.s && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
     slabs.end();
-    if (st && own_stream) (void)hipStreamDestroy(st);
     return rc;
 }
 
@@ -526,14 +498,14 @@ int rb_graph_add_fasta(rb_graph *g, const char *text, size_t len, unsigned flags
     if (!g) { set_error("rb_graph_add_fasta: null graph"); return RB_ERR_INVALID; }
     if (!text && len) { set_error("rb_graph_add_fasta: null text"); return RB_ERR_INVALID; }
     hipStream_t st = nullptr;
-    bool own_stream = false;
+    rb::Stream own_stream;                                           // RB_INGEST_OWN_STREAM: this call's own instead of the handle's copy stream
     SlabPin slabs;
     WriteLock wl(g->rw);
     int rc = guarded([&] {
         RB_HIP(hipSetDevice(g->p.device));
         slabs.begin(text, len);                                      // registered slab by slab as the pieces advance (best effort)
         st = getenv("RB_INGEST_OWN_STREAM") ? nullptr : g->pk_stream;      // the handle's copy stream (made with the graph: a hardware queue of its own, rb_graph_create)
-        if (!st) { RB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); own_stream = true; }
+        if (!st) { RB_HIP(hipStreamCreateWithFlags(&own_stream.s, hipStreamNonBlocking)); st = own_stream; }
         // pieces of 1 GiB of text; a piece starts where the complete records of the one before ended.  The next piece is
         // uploaded and parsed (helper thread, own stream) while the insert pipeline works on the current one.
         const size_t piece_bytes = getenv("RB_FASTQ_PIECE") ? (size_t)std::max(64, atoi(getenv("RB_FASTQ_PIECE"))) : (size_t)1 << 30;
@@ -550,7 +522,7 @@ int rb_graph_add_fasta(rb_graph *g, const char *text, size_t len, unsigned flags
         int64_t recs = 0;
         rb::FastqChunk cur = piece(0);
         for (;;) {
-            struct G { rb_batch *b; ~G() { if (b) rb_batch_destroy(b); } } guard{cur.b};
+            rb::BatchPtr guard(cur.b);
             recs += cur.records;
             const bool last = a + piece_bytes >= len || ended;
             const size_t next = a + cur.consumed;
@@ -572,9 +544,8 @@ int rb_graph_add_fasta(rb_graph *g, const char *text, size_t len, unsigned flags
         }
         if (n_records) *n_records = recs;
     });
-    if (st && !own_stream && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
+    if (st && !own_stream.s && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
     slabs.end();
-    if (st && own_stream) (void)hipStreamDestroy(st);
     return rc;
 }
 
@@ -655,16 +626,16 @@ struct TextSource {
 int add_text_file(rb_graph *g, const char *path, bool fasta, int min_base_qual, unsigned flags, rb_add_stats *stats, int64_t *n_records) {
     if (!g || !path) { set_error("rb_graph_add_%s_file: null argument", fasta ? "fasta" : "fastq"); return RB_ERR_INVALID; }
     hipStream_t st = nullptr;
-    bool own_stream = false;
-    char *buf[2] = {nullptr, nullptr};
+    rb::Stream own_stream;                                           // RB_INGEST_OWN_STREAM: this call's own instead of the handle's copy stream
+    rb::HostBuf<char> buf[2];
     WriteLock wl(g->rw);
     int rc = guarded([&] {
         RB_HIP(hipSetDevice(g->p.device));
         st = getenv("RB_INGEST_OWN_STREAM") ? nullptr : g->pk_stream;
-        if (!st) { RB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); own_stream = true; }
+        if (!st) { RB_HIP(hipStreamCreateWithFlags(&own_stream.s, hipStreamNonBlocking)); st = own_stream; }
         TextSource src(path);
         const size_t piece_bytes = getenv("RB_FASTQ_PIECE") ? (size_t)std::max(64, atoi(getenv("RB_FASTQ_PIECE"))) : (size_t)256 << 20;
-        for (auto &b : buf) RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&b), piece_bytes, hipHostMallocDefault));
+        for (auto &b : buf) b.alloc(piece_bytes);
         bool ended = false, src_done = false;
         // piece into buf[w]: `carry` bytes of the piece before (already at the front of buf[w]) + fresh text
         auto make = [&](int w, size_t carry, size_t *len_out) {
@@ -685,7 +656,7 @@ int add_text_file(rb_graph *g, const char *path, bool fasta, int min_base_qual, 
         int64_t recs = 0;
         rb::FastqChunk cur = make(0, 0, &len);
         for (;;) {
-            struct G { rb_batch *b; ~G() { if (b) rb_batch_destroy(b); } } guard{cur.b};
+            rb::BatchPtr guard(cur.b);
             recs += cur.records;
             const bool last = src_done || ended;
             RB_REQUIRE(last || cur.consumed > 0, "a record longer than %zu bytes", piece_bytes);
@@ -711,9 +682,7 @@ int add_text_file(rb_graph *g, const char *path, bool fasta, int min_base_qual, 
         }
         if (n_records) *n_records = recs;
     });
-    if (st && !own_stream && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
-    for (auto b : buf) if (b) (void)hipHostFree(b);
-    if (st && own_stream) (void)hipStreamDestroy(st);
+    if (st && !own_stream.s && rc != RB_OK) (void)hipStreamSynchronize(st);      // (a failed call leaves nothing of its own in flight on the shared stream)
     return rc;
 }
 }  // namespace
@@ -787,8 +756,8 @@ int rb_debug_probe_cbf(rb_graph *g, int mode, float *ms_out) {
         RB_HIP(hipSetDevice(g->p.device));
         hipStream_t s = g->stream;
         g->devctr.reserve(DEVCTR_BYTES);
-        hipEvent_t e0, e1;
-        RB_HIP(hipEventCreate(&e0)); RB_HIP(hipEventCreate(&e1));
+        rb::Event e0, e1;
+        RB_HIP(hipEventCreate(&e0.e)); RB_HIP(hipEventCreate(&e1.e));
         RB_HIP(hipStreamSynchronize(s));
         RB_HIP(hipEventRecord(e0, s));
         // the same places twice: the second pass undoes the first (mode 1)
@@ -797,13 +766,11 @@ int rb_debug_probe_cbf(rb_graph *g, int mode, float *ms_out) {
         RB_HIP(hipEventRecord(e1, s));
         RB_HIP(hipEventSynchronize(e1));
         RB_HIP(hipEventElapsedTime(ms_out, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     });
 }
 
 int rb_debug_scan_u32(int device, const uint32_t *in, size_t n, uint32_t *out, int misalign) {
     DevBuf a, b, t;
-    struct Rel { DevBuf &a, &b, &t; ~Rel() { a.release(); b.release(); t.release(); } } rel{a, b, t};
     return guarded([&] {
         RB_REQUIRE((in && out) || n == 0, "rb_debug_scan_u32: null array");
         RB_REQUIRE(misalign >= 0 && misalign < 16, "rb_debug_scan_u32: misalign in 0..15");
@@ -819,7 +786,6 @@ int rb_debug_scan_u32(int device, const uint32_t *in, size_t n, uint32_t *out, i
 }
 int rb_debug_sort_pairs(int device, uint64_t *keys, void *vals, int vals64, size_t n, int lo_begin, int lo_end, int hi_begin, int hi_end) {
     DevBuf k0, k1, v0, v1, t;
-    struct Rel { DevBuf &a, &b, &c, &d, &t; ~Rel() { a.release(); b.release(); c.release(); d.release(); t.release(); } } rel{k0, k1, v0, v1, t};
     return guarded([&] {
         RB_REQUIRE(keys || n == 0, "rb_debug_sort_pairs: null keys");
         RB_REQUIRE(!(vals64 && hi_begin >= 0), "rb_debug_sort_pairs: two ranges with 32-bit values only");

@@ -118,7 +118,7 @@ struct rb_shard_comm {
     struct Pool {
         DevBuf buf[MAX_PARTS];
         DevBuf cnt_dev;
-        int64_t *cnt_host = nullptr;    // pinned, 2 * MAX_PARTS * MAX_WORLD
+        rb::HostBuf<int64_t> cnt_host;  // pinned, 2 * MAX_PARTS * MAX_WORLD
     } pool[MAX_WORLD];
 };
 
@@ -160,7 +160,7 @@ struct InCall {
 };
 rb_shard_comm::Pool &pool_of(rb_shard_comm *c, int me) {
     rb_shard_comm::Pool &p = c->pool[c->is_rccl ? 0 : me];
-    if (!p.cnt_host) RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&p.cnt_host), sizeof(int64_t) * 2 * MAX_PARTS * MAX_WORLD, hipHostMallocDefault));
+    if (!p.cnt_host) p.cnt_host.alloc(sizeof(int64_t) * 2 * MAX_PARTS * MAX_WORLD);
     return p;
 }
 
@@ -492,14 +492,12 @@ int rb_shard_comm_selftest(rb_shard_comm *c, int me, int device, int64_t big_byt
     const bool fail_late = big_bytes == -2;
     if (fail_late) big_bytes = 0;
     DevBuf sendbuf;
-    struct Rel { DevBuf &b; ~Rel() { b.release(); } } rel{sendbuf};
     InCall in_call(c, me);
     int rc = guarded([&] {
         RB_REQUIRE(c && me >= 0 && me < c->world && big_bytes >= 0, "rb_shard_comm_selftest: bad argument");
         RB_HIP(hipSetDevice(device));
-        hipStream_t st = nullptr;
-        RB_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        struct StreamDrop { hipStream_t s; ~StreamDrop() { (void)hipStreamDestroy(s); } } drop{st};
+        rb::Stream st;
+        RB_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
         const int G = c->world;
         auto len = [&](int from, int to) { return (int64_t)(from * 7 + to * 3 + 1) * 1000 + big_bytes; };
         Part pa[1];
@@ -551,11 +549,6 @@ int rb_shard_comm_selftest(rb_shard_comm *c, int me, int device, int64_t big_byt
 int rb_shard_comm_destroy(rb_shard_comm *c) {
     if (!c) return RB_OK;
     if (c->is_rccl && c->nc && rccl().CommDestroy) (void)rccl().CommDestroy(c->nc);
-    for (auto &p : c->pool) {
-        for (auto &b : p.buf) b.release();
-        p.cnt_dev.release();
-        if (p.cnt_host) (void)hipHostFree(p.cnt_host);
-    }
     delete c;
     return RB_OK;
 }

@@ -347,10 +347,9 @@ int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_
         int64_t *dtab = q.c->b0.as<int64_t>();
         float *prof = q.c->b1.as<float>();
         rb_cov_stats *buf[2] = {q.c->b2.as<rb_cov_stats>(), q.c->b2.as<rb_cov_stats>() + max_rec};
-        hipStream_t s2 = nullptr;
-        std::vector<hipEvent_t> ev;
-        struct Cleanup { hipStream_t &s2; std::vector<hipEvent_t> &ev; ~Cleanup() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); if (s2) (void)hipStreamDestroy(s2); } } cleanup{s2, ev};
-        if (!out_on_device) RB_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+        rb::Stream s2;
+        std::vector<rb::Event> ev;
+        if (!out_on_device) RB_HIP(hipStreamCreateWithFlags(&s2.s, hipStreamNonBlocking));
         std::vector<hipEvent_t> copied;                     // per piece: its records are on the host (its buffer is free again)
         for (size_t c = 0; c < pcs.size(); ++c) {
             const Piece &pc = pcs[c];
@@ -388,9 +387,8 @@ int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_
             }
             RB_HIP(hipGetLastError());
             if (out_on_device) continue;
-            hipEvent_t e, e2;
-            RB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev.push_back(e);
-            RB_HIP(hipEventCreateWithFlags(&e2, hipEventDisableTiming)); ev.push_back(e2);
+            ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&ev.back().e, hipEventDisableTiming)); const hipEvent_t e = ev.back();
+            ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&ev.back().e, hipEventDisableTiming)); const hipEvent_t e2 = ev.back();
             RB_HIP(hipEventRecord(e, s));
             RB_HIP(hipStreamWaitEvent(s2, e, 0));
             const size_t rs = sizeof(rb_cov_stats);

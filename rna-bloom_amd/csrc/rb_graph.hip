@@ -1408,7 +1408,9 @@ void *rb::alloc_best_placed(size_t bytes, const char *what) {
         void *best = nullptr, *cand = nullptr;
         unsigned long long *sink = nullptr;
         hipEvent_t e0 = nullptr, e1 = nullptr;
+        std::vector<void *> losers;                           // held while later candidates are drawn (so that they get other pages)
         ~Held() {
+            for (void *p : losers) (void)hipFree(p);
             if (best) (void)hipFree(best);
             if (cand) (void)hipFree(cand);
             if (sink) (void)hipFree(sink);
@@ -1416,8 +1418,6 @@ void *rb::alloc_best_placed(size_t bytes, const char *what) {
             if (e1) (void)hipEventDestroy(e1);
         }
     } H;
-    std::vector<void *> losers;                               // held while later candidates are drawn (so that they get other pages)
-    struct Losers { std::vector<void *> &v; ~Losers() { for (void *p : v) (void)hipFree(p); } } losers_guard{losers};
     float best_ms = 0;
     if (tries > 1) { RB_HIP(hipMalloc(&H.sink, 64)); RB_HIP(hipEventCreate(&H.e0)); RB_HIP(hipEventCreate(&H.e1)); }
     for (int t = 0; t < tries; ++t) {
@@ -1439,8 +1439,8 @@ void *rb::alloc_best_placed(size_t bytes, const char *what) {
             RB_HIP(hipEventElapsedTime(&ms, H.e0, H.e1));
         }
         if (getenv("RB_ALLOC_DEBUG")) fprintf(stderr, "[rb] %s allocation %d: %.3f ms for 2 x 2^26 random XORs\n", what, t, ms);
-        if (!H.best || ms < best_ms) { if (H.best) losers.push_back(H.best); H.best = H.cand; best_ms = ms; }
-        else losers.push_back(H.cand);
+        if (!H.best || ms < best_ms) { if (H.best) H.losers.push_back(H.best); H.best = H.cand; best_ms = ms; }
+        else H.losers.push_back(H.cand);
         H.cand = nullptr;
     }
     RB_HIP(hipDeviceSynchronize());

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -64,10 +65,17 @@ struct HipError {
         }                                              \
     } while (0)
 
-// grow-only device buffer
+// grow-only device buffer; owns its memory (move-only).  release() frees early, the destructor frees what is left.  Like the other owners below it
+// must not have static storage: a hipFree after the runtime has shut down at process exit is a crash.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     void reserve(size_t bytes) {
         if (bytes <= cap) return;
         if (p) RB_HIP(hipFree(p));
@@ -81,6 +89,36 @@ struct DevBuf {
         p = nullptr; cap = 0;
     }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Owners of a stream, an event and a hipHostMalloc block: empty until the create call fills the raw handle in (RB_HIP(hipStreamCreate...(&x.s, ...))),
+// destroyed with their scope or struct, converting to the raw handle wherever one is expected.  Move-only; a moved-into owner hands its old handle
+// to the source, which destroys it.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+template <typename T> struct HostBuf {
+    T *p = nullptr;
+    HostBuf() = default;
+    HostBuf(HostBuf &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    HostBuf &operator=(HostBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~HostBuf() { release(); }
+    void alloc(size_t bytes) { release(); RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), bytes, hipHostMallocDefault)); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
+    operator T *() const { return p; }
 };
 
 }  // namespace rb
@@ -236,6 +274,11 @@ struct rb_batch {
     size_t device_bytes = 0;
     HostWoff h_woff;               // host copy of woff (sub-batch splitting)
 };
+namespace rb {
+// owner of a batch: rb_batch_destroy at scope end (its arrays go back to the batch's pool, or to hipFree); null-safe
+struct BatchDestroy { void operator()(rb_batch *p) const { (void)rb_batch_destroy(p); } };
+using BatchPtr = std::unique_ptr<rb_batch, BatchDestroy>;
+}  // namespace rb
 
 namespace rb {
 

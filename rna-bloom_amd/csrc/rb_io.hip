@@ -248,7 +248,7 @@ FastqChunk fastq_batch_create(int device, const char *text, size_t n, bool final
     if (!final && n && text[n - 1] == '\r') --n;                     // its \n may be the first byte of the next piece
     FastqChunk out;
     rb_batch *b = new rb_batch();
-    struct Guard { rb_batch *b; ~Guard() { if (b) rb_batch_destroy(b); } } guard{b};
+    rb::BatchPtr guard(b);
     b->device = device;
     const uint32_t un = (uint32_t)n, ntiles = (uint32_t)(((uint64_t)n + FQ_TILE - 1) / FQ_TILE);   // 64-bit: n + FQ_TILE - 1 wraps in 32 bits just below 4 GiB
     TmpBuf d_text, d_cnt, d_base, d_tmp, d_ls, d_sp, d_qp, d_len, d_nw, d_woff, d_err;
@@ -309,7 +309,7 @@ FastqChunk fastq_batch_create(int device, const char *text, size_t n, bool final
                            min_base_qual, b->codes, b->valid, b->word_read);
     RB_HIP(hipGetLastError());
     RB_HIP(hipStreamSynchronize(st));
-    out.b = b; guard.b = nullptr;
+    out.b = guard.release();
     return out;
 }
 // FASTA text -> packed batch on the GPU.  final = false: the text is a piece of a longer input; the last record then stays
@@ -322,7 +322,7 @@ FastqChunk fasta_batch_create(int device, const char *text, size_t n, bool final
     FastqChunk out;
     if (ended) *ended = false;
     rb_batch *b = new rb_batch();
-    struct Guard { rb_batch *b; ~Guard() { if (b) rb_batch_destroy(b); } } guard{b};
+    rb::BatchPtr guard(b);
     b->device = device;
     const uint32_t un = (uint32_t)n, ntiles = (uint32_t)(((uint64_t)n + FQ_TILE - 1) / FQ_TILE);   // 64-bit: n + FQ_TILE - 1 wraps in 32 bits just below 4 GiB
     TmpBuf d_text, d_cnt, d_base, d_tmp, d_ls, d_ts, d_tl, d_ish, d_kind, d_cum, d_hidx, d_hl, d_len, d_nw, d_woff, d_err;
@@ -416,7 +416,7 @@ FastqChunk fasta_batch_create(int device, const char *text, size_t n, bool final
                            b->word_read);
     RB_HIP(hipGetLastError());
     RB_HIP(hipStreamSynchronize(st));
-    out.b = b; guard.b = nullptr;
+    out.b = guard.release();
     return out;
 }
 }  // namespace rb

@@ -76,14 +76,14 @@ __global__ void k_packed_word_read(const uint32_t *__restrict__ woff, int64_t n,
 struct rb_packed_stream {
     int device = 0;
     int64_t max_reads = 0, max_words = 0;
-    hipStream_t st = nullptr;
+    rb::Stream st;                                // (declared before the buffers: destroyed after them)
     struct Buf {
         rb_batch b;                               // its arrays point into the DevBufs below (never rb_batch_destroy'ed)
         DevBuf codes, valid, word_read, woff, len, wc, temp, stats;
-        uint32_t *h_woff = nullptr;               // pinned host copy of woff, (max_reads + 1) entries
+        rb::HostBuf<uint32_t> h_woff;             // pinned host copy of woff, (max_reads + 1) entries
         int64_t h_woff_cap = -1;
     } buf[2];
-    uint32_t *h_stats = nullptr;                  // pinned, 8 words
+    rb::HostBuf<uint32_t> h_stats;                // pinned, 8 words
     int fill = 0;                                 // the buffer the next begin() fills
     bool pending = false;
     // ONE helper thread for the stream's lifetime (a thread's first HIP call sets up its context: milliseconds — per chunk, had every begin()
@@ -212,14 +212,14 @@ int rb_packed_stream_create(int device, int64_t max_reads, int64_t max_words, rb
         RB_HIP(hipSetDevice(device));
         s = new rb_packed_stream();
         s->device = device; s->max_reads = max_reads; s->max_words = max_words;
-        RB_HIP(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-        RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_stats), 64, hipHostMallocDefault));
+        RB_HIP(hipStreamCreateWithFlags(&s->st.s, hipStreamNonBlocking));
+        s->h_stats.alloc(64);
         for (auto &B : s->buf) {                   // both buffers at their full size now: growing one later frees memory, and hipFree waits for the device
             const size_t nw = (size_t)std::max<int64_t>(max_words, 1), nr = (size_t)std::max<int64_t>(max_reads, 1);
             B.codes.reserve(nw * 8); B.valid.reserve(nw * 4); B.word_read.reserve(nw * 4);
             B.woff.reserve((nr + 1) * 4); B.len.reserve(nr * 4); B.wc.reserve((nr + 1) * 4); B.stats.reserve(64);
             B.temp.reserve(scan_temp_bytes(nr + 1));
-            RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&B.h_woff), (nr + 1) * 4, hipHostMallocDefault));
+            B.h_woff.alloc((nr + 1) * 4);
             B.h_woff_cap = max_reads;
         }
         *out = s;
@@ -260,13 +260,7 @@ int rb_packed_stream_destroy(rb_packed_stream *s) {
     if (!s) return RB_OK;
     s->stop();
     (void)hipSetDevice(s->device);
-    if (s->st) { (void)hipStreamSynchronize(s->st); (void)hipStreamDestroy(s->st); }
-    for (auto &B : s->buf) {
-        for (DevBuf *d : {&B.codes, &B.valid, &B.word_read, &B.woff, &B.len, &B.wc, &B.temp, &B.stats}) d->release();
-        if (B.h_woff) (void)hipHostFree(B.h_woff);
-        B.b.codes = nullptr; B.b.valid = nullptr; B.b.word_read = nullptr; B.b.woff = nullptr; B.b.len = nullptr;
-    }
-    if (s->h_stats) (void)hipHostFree(s->h_stats);
+    if (s->st) (void)hipStreamSynchronize(s->st);
     delete s;
     return RB_OK;
 }
@@ -278,18 +272,17 @@ namespace {
 // that turn them into word offsets and word owners, the offsets' way back into pinned memory (event ev_woff), then codes and valid in pieces cut
 // at WORD boundaries (no offset is needed to cut them), an event behind each.
 void ingest_begin(rb_graph *g, rb_graph::PackedIngest &K, const uint64_t *codes, const uint32_t *valid, const uint32_t *len, int64_t n_reads, int64_t n_words, int64_t piece_reads) {
-    if (!g->pk_stream) RB_HIP(hipStreamCreateWithFlags(&g->pk_stream, hipStreamNonBlocking));
+    if (!g->pk_stream) RB_HIP(hipStreamCreateWithFlags(&g->pk_stream.s, hipStreamNonBlocking));
     hipStream_t st = g->pk_stream;
-    if (!K.h_stats) RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&K.h_stats), 64, hipHostMallocDefault));
-    if (!K.ev_woff) RB_HIP(hipEventCreateWithFlags(&K.ev_woff, hipEventDisableTiming));
+    if (!K.h_stats) K.h_stats.alloc(64);
+    if (!K.ev_woff) RB_HIP(hipEventCreateWithFlags(&K.ev_woff.e, hipEventDisableTiming));
     const size_t nw = (size_t)std::max<int64_t>(n_words, 1), nr = (size_t)n_reads;
     K.codes.reserve(nw * 8); K.valid.reserve(nw * 4); K.word_read.reserve(nw * 4);
     K.woff.reserve((nr + 1) * 4); K.len.reserve(nr * 4); K.wc.reserve((nr + 1) * 4); K.stats.reserve(64); K.temp.reserve(scan_temp_bytes(nr + 1));
     if (K.h_woff_cap < nr + 1) {
-        if (K.h_woff) (void)hipHostFree(K.h_woff);
-        K.h_woff = nullptr; K.h_woff_cap = 0;
+        K.h_woff_cap = 0;
         const size_t want = nr + 1 + (nr >> 3);
-        RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&K.h_woff), want * 4, hipHostMallocDefault));
+        K.h_woff.alloc(want * 4);
         K.h_woff_cap = want;
     }
     // the caller's arrays: registered for the upload unless they are pinned already (best effort; pageable memory makes every copy below a blocking one)
@@ -321,7 +314,7 @@ void ingest_begin(rb_graph *g, rb_graph::PackedIngest &K, const uint64_t *codes,
             if (!piece_reads) step = std::min<int64_t>(step * 2, (int64_t)1 << 25);
         }
     }
-    while (K.ev.size() < K.wend.size()) { hipEvent_t e; RB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); K.ev.push_back(e); }
+    while (K.ev.size() < K.wend.size()) { K.ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&K.ev.back().e, hipEventDisableTiming)); }
     int64_t w0 = 0;
     for (size_t p = 0; p < K.wend.size(); ++p) {
         const int64_t w1 = K.wend[p];
@@ -357,10 +350,10 @@ namespace {
 // qualities of <= piece_bases bases into one of two staging buffers and the encode kernel of that piece (k_encode_ascii_t<true>, rb_batch.hip)
 // behind it, an event behind each.  The stream is in order: the copy into a staging buffer queues behind the encode that last read it.
 void ingest_begin_ascii(rb_graph *g, rb_graph::PackedIngest &K, const char *seq, const char *qual, const int64_t *offsets, int64_t n_reads, int min_q, int64_t piece_bases) {
-    if (!g->pk_stream) RB_HIP(hipStreamCreateWithFlags(&g->pk_stream, hipStreamNonBlocking));
+    if (!g->pk_stream) RB_HIP(hipStreamCreateWithFlags(&g->pk_stream.s, hipStreamNonBlocking));
     hipStream_t st = g->pk_stream;
-    if (!K.h_stats) RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&K.h_stats), 64, hipHostMallocDefault));
-    if (!K.ev_woff) RB_HIP(hipEventCreateWithFlags(&K.ev_woff, hipEventDisableTiming));
+    if (!K.h_stats) K.h_stats.alloc(64);
+    if (!K.ev_woff) RB_HIP(hipEventCreateWithFlags(&K.ev_woff.e, hipEventDisableTiming));
     const size_t nr = (size_t)n_reads;
     const int64_t base0 = offsets[0], nbases = offsets[n_reads] - base0;
     RB_REQUIRE(nbases >= 0, "rb_graph_add_reads: the offsets run backwards");
@@ -370,10 +363,9 @@ void ingest_begin_ascii(rb_graph *g, rb_graph::PackedIngest &K, const char *seq,
     K.woff.reserve((nr + 1) * 4); K.len.reserve(nr * 4); K.wc.reserve((nr + 1) * 4); K.stats.reserve(64); K.temp.reserve(scan_temp_bytes(nr + 1));
     K.off.reserve((nr + 1) * 8);
     if (K.h_woff_cap < nr + 1) {
-        if (K.h_woff) (void)hipHostFree(K.h_woff);
-        K.h_woff = nullptr; K.h_woff_cap = 0;
+        K.h_woff_cap = 0;
         const size_t want = nr + 1 + (nr >> 3);
-        RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&K.h_woff), want * 4, hipHostMallocDefault));
+        K.h_woff.alloc(want * 4);
         K.h_woff_cap = want;
     }
     // the pieces: reads [rend[p - 1], rend[p]) of at most piece_bases bases (at least one read)
@@ -388,7 +380,7 @@ void ingest_begin_ascii(rb_graph *g, rb_graph::PackedIngest &K, const char *seq,
         a = lo;
     }
     for (int q = 0; q < 2; ++q) { K.stage_seq[q].reserve((size_t)std::max<int64_t>(max_piece, 1)); if (qual) K.stage_qual[q].reserve((size_t)std::max<int64_t>(max_piece, 1)); }
-    while (K.ev.size() < K.rend.size()) { hipEvent_t e; RB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); K.ev.push_back(e); }
+    while (K.ev.size() < K.rend.size()) { K.ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&K.ev.back().e, hipEventDisableTiming)); }
     // the caller's offsets are registered here (they go up first); bases and qualities are registered slab by slab by the feeder below, ahead of the copies
     if ((nr + 1) * 8 > ((size_t)16 << 20) && !getenv("RB_NO_PIN") && !HostPin::pinned_already(offsets)) {
         if (hipHostRegister(const_cast<int64_t *>(offsets), (nr + 1) * 8, hipHostRegisterDefault) == hipSuccess) K.pins.push_back(const_cast<int64_t *>(offsets));

@@ -208,9 +208,8 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
         hipStream_t s = q.c->st;
         // with profiling on (rb_graph_profile_enable) the two kernels of every piece are timed by events on the query stream: entry "pair_segments"
         const bool prof = g->prof_on;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        struct Events { hipEvent_t *e; ~Events() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-        if (prof) { RB_HIP(hipEventCreate(&ev[0])); RB_HIP(hipEventCreate(&ev[1])); }
+        rb::Event ev[2];
+        if (prof) { RB_HIP(hipEventCreate(&ev[0].e)); RB_HIP(hipEventCreate(&ev[1].e)); }
         double prof_ms = 0;
         int64_t prof_n = 0;
         // pieces of <= 16 M k-mers, as rb_graph_kmers: the piece's batch (≈ 0.3 B a base) and 1 bit a position are all the scratch there is
@@ -244,7 +243,7 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
                 rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
                 b = rb::ascii_batch_finish(up);
             } catch (...) { rb::ascii_batch_abort(up); throw; }
-            struct Guard { rb_batch *b; ~Guard() { rb_batch_destroy(b); } } guard{b};
+            rb::BatchPtr guard(b);
             q.c->b0.reserve(tab.size() * 8);
             q.c->b1.reserve((size_t)nw * 8);
             q.c->b2.reserve((size_t)nc * 8 + (size_t)pn * 4 + 4);

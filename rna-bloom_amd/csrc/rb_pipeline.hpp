@@ -9,6 +9,7 @@
 #include <new>
 #include <shared_mutex>
 #include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -331,15 +332,22 @@ using rb::BitFilter; using rb::FilterView; using rb::Mod; using rb::DevBuf; usin
 // getSuccessors on ONE graph from T threads (R/RNABloom.java, e.g. :1984-2114), so every query call leases a context of
 // its own; inserts and everything else that changes a filter take the handle exclusively (rb_graph::rw).
 struct rb_query_ctx {
-    hipStream_t st = nullptr;
+    rb::Stream st;                   // (declared first: destroyed after the buffers)
     rb::DevBuf b0, b1, b2, b3;
 };
+// Ownership: the handle owns its buffers, streams, events and pinned blocks through its members, and rb_graph_destroy synchronises every stream of
+// the handle BEFORE `delete g`, so nothing below is freed under work in flight.  Members are destroyed in reverse order of declaration; what is relied
+// on: the streams and events are declared before (so outlive) every buffer, query context and ingest slot, and ingest_pool is declared before the
+// ingest slots.  Only call-local batches hand blocks back to ingest_pool, and they are gone before a handle can be destroyed.  The bit filters, cbf,
+// the shard state and a traversal are plain pointers (views that kernels take by value, or types other translation units define): ~rb_graph and
+// rb_graph_destroy free those.
 struct rb_graph {
+    ~rb_graph();                     // rb_capi.hip
     // one handle, many threads: queries share the handle (shared lock + a leased context each), mutators own it
     std::shared_mutex rw;
     std::mutex qm;
     std::condition_variable qcv;
-    std::vector<rb_query_ctx *> qfree;
+    std::vector<std::unique_ptr<rb_query_ctx>> qfree;
     int qmade = 0;
     static constexpr int kMaxQueryCtx = 32;
     // sharded mode (rb_shard.hip): this handle owns index range [lo,hi) of every filter
@@ -362,9 +370,12 @@ struct rb_graph {
     int sort_begin_bit = 28;
     uint32_t light_ops = 96;
     uint32_t small_ops = 32;             // a component of at most this many ops is replayed by one lane (k_conf_replay_small), a larger one by a wavefront; RB_SMALL_COMPONENT_OPS
-    hipStream_t stream = nullptr;    // consumer stream: everything that touches the filters
-    hipStream_t stream2 = nullptr;   // producer stream: hashing + grouping of the NEXT sub-batch (scratch only)
-    hipStream_t stream3 = nullptr;   // side stream of the producer: the paired-k-mer walker (rpkbf only) beside the window walk
+    rb::Stream stream;               // consumer stream: everything that touches the filters
+    rb::Stream stream2;              // producer stream: hashing + grouping of the NEXT sub-batch (scratch only)
+    rb::Stream stream3;              // side stream of the producer: the paired-k-mer walker (rpkbf only) beside the window walk
+    rb::Stream pk_stream;            // the copy stream both packed-ingest slots upload on (in order: a prefetch queues behind the batch before it)
+    rb::Event ev0, ev1, ev2, ev3;
+    DevPool ingest_pool;             // device blocks of the chunked text ingests (rb_graph_add_reads): handed from chunk to chunk and call to call, freed with the graph
     // grouped sub-batch, double buffered so that grouping of sub-batch i+1 overlaps the filter stages of i
     struct GroupSlot { DevBuf keys1, valsT, vals1, tz, uniq, counts, starts, brun, bnr /* swept stage: run slots per index range */; uint32_t sweep_T = 0, n_main = 0; size_t N = 0; uint32_t D = 0; int flags = 0; uint32_t live = 0; int bucket_target = 0; /* what group_enqueue planned with */ };
     GroupSlot slots[2];
@@ -404,9 +415,9 @@ struct rb_graph {
     std::vector<ProfEntry> prof;
     struct ProfPending { const char *name; hipEvent_t e0, e1; };
     std::vector<ProfPending> prof_pending;
+    std::vector<rb::Event> prof_made;            // every profiling event of the handle; the three below refer to them
     std::vector<hipEvent_t> prof_pool;
     hipEvent_t prof_open[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     // rb_graph_add_packed: the batch being inserted is still arriving from host memory, piece by piece on a copy stream.  add_range calls this
     // before it enqueues anything that reads words [0, w_end) of the batch on `st`; the hook makes `st` wait for the pieces that hold them.
     std::function<void(int64_t w_end, hipStream_t st)> await_words;
@@ -414,10 +425,10 @@ struct rb_graph {
     // offsets, the copy stream and one event per uploaded piece
     struct PackedIngest {
         DevBuf codes, valid, word_read, woff, len, wc, temp, stats;
-        uint32_t *h_woff = nullptr, *h_stats = nullptr;
+        rb::HostBuf<uint32_t> h_woff, h_stats;
         size_t h_woff_cap = 0;
-        std::vector<hipEvent_t> ev;              // one behind every uploaded piece
-        hipEvent_t ev_woff = nullptr;            // the word offsets are back in h_woff
+        std::vector<rb::Event> ev;               // one behind every uploaded piece
+        rb::Event ev_woff;                       // the word offsets are back in h_woff
         std::vector<int64_t> wend;               // piece p holds words [wend[p - 1], wend[p])
         // the upload in flight (rb_graph_prefetch_packed, or the add call itself): whose arrays, how many
         const void *src = nullptr;
@@ -437,15 +448,23 @@ struct rb_graph {
         bool cancel = false;
         int feeder_rc = 0;
         std::string feeder_err;
+        ~PackedIngest() {                        // (a feeder still running stops at its next piece; the buffers, events and pinned blocks free themselves after it)
+            if (feeder.joinable()) {
+                { std::lock_guard<std::mutex> lk(fm); cancel = true; }
+                fcv.notify_all();
+                feeder.join();
+            }
+            for (void *p : pins) (void)hipHostUnregister(p);
+        }
     } pk[2];
     IngestHost ingest_host[2];                   // pinned host scratch of the chunked text ingests' preparation, taking turns
-    DevPool ingest_pool;                         // device blocks of the chunked text ingests (rb_graph_add_reads): handed from chunk to chunk and call to call, freed with the graph
-    hipStream_t pk_stream = nullptr;             // the copy stream both slots upload on (in order: a prefetch queues behind the batch before it)
     std::mutex pk_mutex;                         // slots are handed out under it (a prefetch may come from another thread than the insert)
     int pk_busy = -1;                            // the slot the running rb_graph_add_packed reads
     hipEvent_t prof_event() {
         if (!prof_pool.empty()) { hipEvent_t e = prof_pool.back(); prof_pool.pop_back(); return e; }
-        hipEvent_t e; RB_HIP(hipEventCreate(&e)); return e;
+        prof_made.emplace_back();
+        RB_HIP(hipEventCreate(&prof_made.back().e));
+        return prof_made.back();
     }
 
     // need_all: the call works on dbgbf AND cbf (a filter freed by rb_graph_destroy_filter makes it fail loudly)
@@ -496,19 +515,19 @@ namespace rb {
 // RAII: shared ownership of the handle + a query context (created on demand, at most kMaxQueryCtx per handle)
 struct QueryLease {
     rb_graph *g;
-    rb_query_ctx *c = nullptr;
+    std::unique_ptr<rb_query_ctx> c;
     std::shared_lock<std::shared_mutex> lk;
     explicit QueryLease(rb_graph *g_) : g(g_), lk(g_->rw) {
         RB_HIP(hipSetDevice(g->p.device));
         std::unique_lock<std::mutex> q(g->qm);
         for (;;) {
-            if (!g->qfree.empty()) { c = g->qfree.back(); g->qfree.pop_back(); return; }
+            if (!g->qfree.empty()) { c = std::move(g->qfree.back()); g->qfree.pop_back(); return; }
             if (g->qmade < rb_graph::kMaxQueryCtx) {
                 ++g->qmade;
                 q.unlock();
-                c = new rb_query_ctx();
-                hipError_t e = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking);
-                if (e != hipSuccess) { delete c; c = nullptr; q.lock(); --g->qmade; q.unlock(); RB_HIP(e); }
+                c.reset(new rb_query_ctx());
+                hipError_t e = hipStreamCreateWithFlags(&c->st.s, hipStreamNonBlocking);
+                if (e != hipSuccess) { c.reset(); q.lock(); --g->qmade; q.unlock(); RB_HIP(e); }
                 return;
             }
             g->qcv.wait(q);
@@ -516,7 +535,7 @@ struct QueryLease {
     }
     ~QueryLease() {
         if (!c) return;
-        { std::lock_guard<std::mutex> q(g->qm); g->qfree.push_back(c); }
+        { std::lock_guard<std::mutex> q(g->qm); g->qfree.push_back(std::move(c)); }
         g->qcv.notify_one();
     }
     QueryLease(const QueryLease &) = delete;

@@ -807,7 +807,7 @@ int rb_graph_kmers(rb_graph *g, const char *seq, const int64_t *offsets, int64_t
                     rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
                     b = rb::ascii_batch_finish(up);
                 } catch (...) { rb::ascii_batch_abort(up); throw; }
-                struct G { rb_batch *b; ~G() { rb_batch_destroy(b); } } guard{b};
+                rb::BatchPtr guard(b);
                 rel.resize((size_t)pn + 1);
                 for (int64_t i = 0; i <= pn; ++i) rel[(size_t)i] = koffsets[ra + i] - koffsets[ra];
                 q.c->b0.reserve(((size_t)pn + 1) * 8); q.c->b1.reserve((size_t)pt * 8); q.c->b2.reserve((size_t)pt * 8); q.c->b3.reserve((size_t)pt * 4);
@@ -885,10 +885,9 @@ int rb_graph_batch_counts(rb_graph *g, const rb_batch *b, int64_t first, int64_t
         }
         q.c->b3.reserve((size_t)largest * 4 * 2);
         float *buf[2] = {q.c->b3.as<float>(), q.c->b3.as<float>() + largest};
-        hipStream_t s2 = nullptr;
-        std::vector<hipEvent_t> ev;
-        struct Cleanup { hipStream_t &s2; std::vector<hipEvent_t> &ev; ~Cleanup() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); if (s2) (void)hipStreamDestroy(s2); } } cleanup{s2, ev};
-        RB_HIP(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+        rb::Stream s2;
+        std::vector<rb::Event> ev;
+        RB_HIP(hipStreamCreateWithFlags(&s2.s, hipStreamNonBlocking));
         std::vector<hipEvent_t> copied;                           // per piece: its copy to the host is done (its buffer is free again)
         for (size_t c = 0; c + 1 < cut.size(); ++c) {
             const int64_t ra = cut[c], rb_ = cut[c + 1], oa = row_of(ra), ob = row_of(rb_);
@@ -898,9 +897,8 @@ int rb_graph_batch_counts(rb_graph *g, const rb_batch *b, int64_t first, int64_t
                 if (!koffsets) RB_HIP(hipMemsetAsync(dst, 0, (size_t)(ob - oa) * 4, s));
                 launch(ra, rb_, oa, dst);
             }
-            hipEvent_t e, e2;
-            RB_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev.push_back(e);
-            RB_HIP(hipEventCreateWithFlags(&e2, hipEventDisableTiming)); ev.push_back(e2);
+            ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&ev.back().e, hipEventDisableTiming)); const hipEvent_t e = ev.back();
+            ev.emplace_back(); RB_HIP(hipEventCreateWithFlags(&ev.back().e, hipEventDisableTiming)); const hipEvent_t e2 = ev.back();
             RB_HIP(hipEventRecord(e, s));
             RB_HIP(hipStreamWaitEvent(s2, e, 0));
             if (ob > oa) RB_HIP(hipMemcpyAsync(out + oa, dst, (size_t)(ob - oa) * 4, hipMemcpyDeviceToHost, s2));
@@ -1115,7 +1113,6 @@ namespace rb {
 void trav_free(rb_graph *g) {
     if (!g->trav) return;
     rb_trav *t = g->trav;
-    t->text.release(); t->hashes.release(); t->misc.release(); t->state.release(); t->reqw.release();
     delete t;
     g->trav = nullptr;
 }

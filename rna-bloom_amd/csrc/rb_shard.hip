@@ -76,7 +76,7 @@ struct ShardState {
     bool pairs_direct = false;                  // one rank: its shard IS the filter — the walker ORs straight into g->rpk (round 5; the routed path cost 85 ms per pass there)
     bool replicate_cache = false;               // split-reads mode: cache updates are broadcast to every rank
     DevBuf cache_upd;                           // [D] exponent to broadcast per run (0 = none)
-    uint32_t *pinned = nullptr;                 // [0] = kept records, [16 + 16 q] = owned windows (32 spread counters)
+    rb::HostBuf<uint32_t> pinned;               // [0] = kept records, [16 + 16 q] = owned windows (32 spread counters)
     // queries
     DevBuf q_h0, q_bpos, q_cpos, q_out;
     size_t q_n = 0;
@@ -1129,7 +1129,7 @@ void prep_filter(rb_graph *g, const rb_batch *b, int64_t first, int64_t n, uint6
     P.w0 = b->h_woff[(size_t)r0]; P.nw = (int64_t)b->h_woff[(size_t)(r0 + rn)] - P.w0;
     P.slot = 1 - g->cur;
     P.stage = 1;
-    if (!S->pinned) RB_HIP(hipHostMalloc(reinterpret_cast<void **>(&S->pinned), 4096, hipHostMallocDefault));
+    if (!S->pinned) S->pinned.alloc(4096);
     memset(S->pinned, 0, 4096);
     if (P.nw <= 0) return;
     const int mode_hash = g->stranded ? ((flags & RB_ADD_REVCOMP) ? 2 : 0) : 1;
@@ -1149,8 +1149,8 @@ void prep_filter(rb_graph *g, const rb_batch *b, int64_t first, int64_t n, uint6
                           g->chunk_cnt.as<uint32_t>(), g->chunk_mask.as<uint32_t>(), g->npf_tot.as<uint32_t>(), st,
                           split ? OwnRange{Mod{1, 0, 0}, 0, 0} : own_range(g), fv.mpf, wstate);
     exclusive_scan_u32(g->temp2.p, g->temp2.cap, g->chunk_cnt.as<uint32_t>(), g->chunk_off.as<uint32_t>(), nw + 1, st);
-    RB_HIP(hipMemcpyAsync(&S->pinned[0], g->chunk_off.as<uint32_t>() + nw, 4, hipMemcpyDeviceToHost, st));
-    RB_HIP(hipMemcpyAsync(&S->pinned[16], g->npf_tot.p, 2048, hipMemcpyDeviceToHost, st));
+    RB_HIP(hipMemcpyAsync(S->pinned + 0, g->chunk_off.as<uint32_t>() + nw, 4, hipMemcpyDeviceToHost, st));
+    RB_HIP(hipMemcpyAsync(S->pinned + 16, g->npf_tot.p, 2048, hipMemcpyDeviceToHost, st));
 }
 // runs of the grouped sub-batch in slot g->cur -> Bloom-bit requests (index + probe id) and counter claims,
 // bucketed by filter owner
@@ -1233,10 +1233,10 @@ int rb_graph_create_shard(const rb_graph_params *p, int shard_rank, int shard_co
         g->shard_rank = shard_rank; g->shard_count = shard_count;
         ShardState *S = g->shard = new ShardState();
         S->G = shard_count; S->log2G = (int)log2_ceil((uint64_t)shard_count);
-        RB_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        RB_HIP(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
-        RB_HIP(hipEventCreate(&g->ev0));
-        RB_HIP(hipEventCreate(&g->ev1));
+        RB_HIP(hipStreamCreateWithFlags(&g->stream.s, hipStreamNonBlocking));
+        RB_HIP(hipStreamCreateWithFlags(&g->stream2.s, hipStreamNonBlocking));
+        RB_HIP(hipEventCreate(&g->ev0.e));
+        RB_HIP(hipEventCreate(&g->ev1.e));
         Geometry gd = geom(p->dbgbf_bits, shard_rank, shard_count);
         S->span[RB_DBGBF] = gd.span;
         alloc_bits(g->dbg, p->dbgbf_bits, p->dbgbf_num_hash, gd.lo, gd.hi);
@@ -2216,14 +2216,8 @@ void shard_clear_pairs_acc(rb_graph *g) {       // rb_graph_clear of the pair fi
 void shard_free(rb_graph *g) {
     ShardState *S = g->shard;
     if (!S) return;
-    for (auto &b : S->slot) b.release();
-    DevBuf *bufs[] = {&S->dreq_pos, &S->creq_pos, &S->creq_dup, &S->cfinal, &S->conf_list, &S->oinfo, &S->ord_pos, &S->conf2, &S->deferred, &S->heavy2, &S->stage0, &S->stage1, &S->stage2, &S->stage3,
-                      &S->rhist, &S->roffs, &S->bounds, &S->rcnt, &S->own_f, &S->own_cs, &S->esz, &S->eoff, &S->etab, &S->eslot, &S->elabel, &S->cdesc,
-                      &S->cpos, &S->cnops, &S->cnoff, &S->rk0, &S->rk1, &S->ok0, &S->ok1, &S->ov0, &S->ov1, &S->rtab, &S->rslot, &S->rbig, &S->q_h0, &S->q_bpos, &S->q_cpos, &S->q_out, &S->cache_upd, &S->lmask, &S->lcoll, &S->lcv, &S->lctr};
-    for (auto *b : bufs) b->release();
-    free_bits(S->rpk_acc);
-    if (S->pinned) (void)hipHostFree(S->pinned);
-    delete S;
+    free_bits(S->rpk_acc);                      // (a BitFilter is a view that launches copy by value: no destructor)
+    delete S;                                   // its buffers and pinned block free themselves
     g->shard = nullptr;
 }
 }  // namespace rb

@@ -505,8 +505,6 @@ __global__ void k_unique_compact(const uint64_t *__restrict__ read, const uint64
     atomicAdd(&per_read[read[t]], 1ull);
 }
 
-struct BatchGuard { rb_batch *b; ~BatchGuard() { if (b) rb_batch_destroy(b); } };
-
 // tile list of the tile kernels: read r with c = off[r+1] - off[r] outputs gets ceil(c / SK_TILE) tiles
 void make_tiles(const int64_t *off, int64_t n_reads, DevBuf &d_tiles, uint32_t *n_tiles) {
     std::vector<SkTile> tiles;
@@ -530,7 +528,6 @@ void launch_minimizers(const uint64_t *d_h, const int64_t *d_koff, const int64_t
         return;
     }
     DevBuf d_tiles, d_tie;
-    struct Rel { DevBuf *a, *b; ~Rel() { a->release(); b->release(); } } rel{&d_tiles, &d_tie};
     uint32_t nt = 0;
     make_tiles(moff, n_reads, d_tiles, &nt);
     d_tie.reserve((size_t)total + 8);
@@ -550,13 +547,12 @@ void hash_all(int device, const char *seq, const int64_t *offsets, int64_t n_rea
     }
     const int64_t total = koff[(size_t)n_reads];
     if (!total) return;
-    rb_batch *b = nullptr;
+    rb::BatchPtr b;
     {
         rb::AsciiUpload up;
-        try { rb::ascii_batch_begin(up, device, seq, nullptr, offsets, 0, n_reads, 0, nullptr, true); b = rb::ascii_batch_finish(up); }
+        try { rb::ascii_batch_begin(up, device, seq, nullptr, offsets, 0, n_reads, 0, nullptr, true); b.reset(rb::ascii_batch_finish(up)); }
         catch (...) { rb::ascii_batch_abort(up); throw; }
     }
-    BatchGuard guard{b};
     d_koff.reserve(((size_t)n_reads + 1) * 8);
     d_h.reserve((size_t)total * 8);
     RB_HIP(hipMemcpy(d_koff.p, koff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice));
@@ -573,7 +569,6 @@ extern "C" {
 int rb_minimizers(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int w, int mode, int64_t *moffsets,
                   uint64_t *out_hash, int64_t *out_pos) {
     DevBuf d_koff, d_h, d_moff, d_oh, d_op;
-    struct Rel { DevBuf *b[5]; ~Rel() { for (auto x : b) x->release(); } } rel{{&d_koff, &d_h, &d_moff, &d_oh, &d_op}};
     return guarded([&] {
         RB_REQUIRE(offsets && moffsets && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && w >= 1 && mode >= 0 && mode <= 2, "rb_minimizers: bad argument");
         RB_HIP(hipSetDevice(device));
@@ -598,7 +593,6 @@ int rb_minimizers(int device, const char *seq, const int64_t *offsets, int64_t n
 int rb_strobemers(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int n, int wmin, int wmax, int64_t *soffsets,
                   uint64_t *out_hash, int32_t *out_start, int32_t *out_end) {
     DevBuf d_koff, d_h, d_soff, d_oh, d_os, d_oe, d_tiles;
-    struct Rel { DevBuf *b[7]; ~Rel() { for (auto x : b) x->release(); } } rel{{&d_koff, &d_h, &d_soff, &d_oh, &d_os, &d_oe, &d_tiles}};
     return guarded([&] {
         RB_REQUIRE(offsets && soffsets && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && n >= 2 && wmin >= 1 && wmax >= wmin, "rb_strobemers: bad argument");
         RB_HIP(hipSetDevice(device));
@@ -635,12 +629,11 @@ int rb_strobemers(int device, const char *seq, const int64_t *offsets, int64_t n
 }  // extern "C"
 
 namespace {
-struct Bufs { std::vector<DevBuf *> v; ~Bufs() { for (auto b : v) b->release(); } };
 // forward (and reverse) all-window hashes
 void hash_fr(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, bool need_r, std::vector<int64_t> &koff,
              DevBuf &d_koff, DevBuf &d_f, DevBuf &d_r) {
     hash_all(device, seq, offsets, n_reads, k, 0, koff, d_koff, d_f);
-    if (need_r) { std::vector<int64_t> k2; DevBuf dk2; hash_all(device, seq, offsets, n_reads, k, 2, k2, dk2, d_r); dk2.release(); }
+    if (need_r) { std::vector<int64_t> k2; DevBuf dk2; hash_all(device, seq, offsets, n_reads, k, 2, k2, dk2, d_r); }
 }
 void counts_out(rb_graph *count_in, int device, DevBuf &d_oh, int64_t total, float *out_count, DevBuf &d_cnt) {
     if (!count_in || !out_count || !total) return;
@@ -659,7 +652,6 @@ extern "C" {
 int rb_randstrobes(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int n, int wmin, int wmax, int flags,
                    rb_graph *count_in, int64_t *soffsets, uint64_t *out_hash, int32_t *out_pos, float *out_count) {
     DevBuf d_koff, d_f, d_r, d_soff, d_oh, d_op, d_cnt, d_tiles;
-    Bufs rel{{&d_koff, &d_f, &d_r, &d_soff, &d_oh, &d_op, &d_cnt, &d_tiles}};
     return guarded([&] {
         RB_REQUIRE(offsets && soffsets && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && n >= 2 && n <= RB_MAX_STROBES && wmin >= 1 && wmax >= wmin,
                    "rb_randstrobes: bad argument");
@@ -698,7 +690,6 @@ int rb_randstrobes(int device, const char *seq, const int64_t *offsets, int64_t 
 int rb_strobe3(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int wmin, int wmax, int canonical,
                rb_graph *count_in, int64_t *soffsets, uint64_t *out_hash, int32_t *out_pos, float *out_count) {
     DevBuf d_koff, d_f, d_r, d_soff, d_oh, d_op, d_cnt, d_tiles;
-    Bufs rel{{&d_koff, &d_f, &d_r, &d_soff, &d_oh, &d_op, &d_cnt, &d_tiles}};
     return guarded([&] {
         RB_REQUIRE(offsets && soffsets && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && wmin >= 1 && wmax >= wmin, "rb_strobe3: bad argument");
         RB_HIP(hipSetDevice(device));
@@ -735,7 +726,6 @@ int rb_strobe3(int device, const char *seq, const int64_t *offsets, int64_t n_re
 int rb_kmer_pair_hashes(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int shift, int canonical,
                         rb_graph *count_in, int64_t *poffsets, uint64_t *out_hash, float *out_count) {
     DevBuf d_koff, d_f, d_r, d_poff, d_oh, d_cnt;
-    Bufs rel{{&d_koff, &d_f, &d_r, &d_poff, &d_oh, &d_cnt}};
     return guarded([&] {
         RB_REQUIRE(offsets && poffsets && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && shift >= 1, "rb_kmer_pair_hashes: bad argument");
         RB_HIP(hipSetDevice(device));
@@ -778,7 +768,6 @@ static int64_t window_minimizers(int device, const char *seq, const int64_t *off
 int rb_minimizers_next(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int w, int mode, int64_t *moffsets,
                        uint64_t *out_hash, int64_t *out_pos) {
     DevBuf d_koff, d_h, d_woff, d_mh, d_mp, d_flag, d_slot, d_tmp, d_oh, d_op, d_mo;
-    Bufs rel{{&d_koff, &d_h, &d_woff, &d_mh, &d_mp, &d_flag, &d_slot, &d_tmp, &d_oh, &d_op, &d_mo}};
     return guarded([&] {
         RB_REQUIRE(offsets && moffsets && out_hash && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && w >= 1 && mode >= 0 && mode <= 2, "rb_minimizers_next: bad argument");
         RB_HIP(hipSetDevice(device));
@@ -808,7 +797,6 @@ int rb_minimizers_next(int device, const char *seq, const int64_t *offsets, int6
 int rb_minimizer_set(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int w, int mode, const uint64_t *stale,
                      int64_t *moffsets, uint64_t *out) {
     DevBuf d_koff, d_h, d_woff, d_mh, d_mp, d_flag, d_slot, d_tmp, d_v0, d_v1, d_r0, d_r1, d_eoff, d_kread, d_stale, d_per, d_out;
-    Bufs rel{{&d_koff, &d_h, &d_woff, &d_mh, &d_mp, &d_flag, &d_slot, &d_tmp, &d_v0, &d_v1, &d_r0, &d_r1, &d_eoff, &d_kread, &d_stale, &d_per, &d_out}};
     return guarded([&] {
         RB_REQUIRE(offsets && moffsets && out && n_reads >= 0 && k >= 1 && k <= RB_MAX_K && w >= 1 && mode >= 0 && mode <= 2, "rb_minimizer_set: bad argument");
         RB_HIP(hipSetDevice(device));

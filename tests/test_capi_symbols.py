@@ -49,6 +49,18 @@ def test_product_package_never_imports_oracle():
                 assert "import rbo" not in txt and "from oracle" not in txt, f
 
 
+def test_no_device_resource_owner_has_static_storage():
+    """DevBuf, Stream, Event, HostBuf and BatchPtr (csrc/rb_internal.hpp) release in their destructors; one with static, thread or namespace
+    storage would call hipFree / hip*Destroy after the runtime has shut down at process exit, which crashes.  Owners live in handles and scopes."""
+    owner = r"(?:rb::)?(?:DevBuf|Stream|Event|HostBuf<[^>]*>|BatchPtr)"
+    csrc = os.path.join(ROOT, "rna-bloom_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        txt = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f), errors="replace").read())
+        hits = re.findall(r"^[ \t]*(?:static|thread_local)\b[^;(]*\b%s(?!\w)[^;(]*;" % owner, txt, flags=re.M)      # static / thread_local, any scope
+        hits += re.findall(r"^%s\s+\w+\s*[;={\[,]" % owner, txt, flags=re.M)                                     # column 0: namespace scope
+        assert not hits, (f, hits)
+
+
 def test_expected_size_matches_reference_formula():
     from rnabloom import _native as N
     import math

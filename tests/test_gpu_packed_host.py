@@ -181,3 +181,52 @@ def test_streamed_ascii_ingest_with_random_pieces_and_sub_batches(monkeypatch, s
     assert (gg.exportFilter(N.DBGBF) == og.dbgbf_bytes()).all() and (gg.exportFilter(N.CBF) == og.cbf_bytes()).all()
     if pairs:
         assert (gg.exportFilter(N.RPKBF) == og.rpkbf_bytes()).all()
+
+
+def test_destroying_a_graph_returns_the_streamed_ingests_staging_memory(monkeypatch):
+    """create -> streamed rb_graph_add_reads -> destroy, 16 times: the device's free memory must not drop by as much as ONE cycle's staging
+    footprint.  The streamed path (csrc/rb_packed.hip ingest_begin_ascii) keeps two staging buffers for a piece's bases and two for its qualities
+    on the handle, each grown to the largest piece (within one read of RB_ASCII_PIECE bytes) plus DevBuf's eighth of slack, and 8 B per read of
+    offsets: a handle that forgets them loses 4 x piece and more per cycle, 16 cycles 16 times that.  The bound comes from those sizes, not from a measurement.
+    Free memory is device-wide (other processes move it): it is read through this process's runtime, the window is short, and a miss is read
+    once more after a synchronise before it fails.  Last, a graph is destroyed right after a streamed add that failed (offsets that run
+    backwards in the middle of the first piece, seen by the length kernel after the feeder thread has started): destroy joins what is left."""
+    import torch
+    piece = 8 << 20
+    monkeypatch.setenv("RB_ASCII_PIECE", str(piece))
+    L, n = 150, 200_000                                          # 30 MB of bases: four pieces
+    rng = np.random.default_rng(7)
+    # reads drawn from a genome of 200 000 bases: as many distinct k-mers at the most, a light load for the filters below (random reads would
+    # be 25 M distinct k-mers in 20 M counters, every counter shared, and the ordered replay of that one component takes minutes)
+    genome = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 200_000)]
+    seq = genome[(rng.integers(0, genome.size - L, n)[:, None] + np.arange(L)[None, :]).ravel()].copy()
+    qual = np.full(L * n, ord("I"), np.uint8)
+    off = np.arange(n + 1, dtype=np.int64) * L
+    assert off[-1] > 3 * piece
+    sizes = (20_000_003, 20_000_003, 2_000_003)
+
+    def cycle(offsets=off):
+        g = BloomFilterDeBruijnGraph(*sizes, 2, 2, 2, 25, False, False, rngSeed=5)
+        try:
+            return g.addReads(seq, qual, offsets, 3)
+        finally:
+            g.destroy()
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    assert cycle().reads == n                                    # warm-up: whatever the runtime allocates once is allocated
+    before = free_bytes()
+    for _ in range(16):
+        cycle()
+    lost = before - free_bytes()
+    print("free device memory: %d bytes before, %d bytes lost over 16 cycles; bound %d" % (before, lost, 4 * piece))
+    if lost >= 4 * piece:
+        lost = before - free_bytes()
+        print("read again after a synchronise: %d bytes lost" % lost)
+    assert lost < 4 * piece, "16 create / streamed add / destroy cycles lost %d bytes of device memory (one cycle's staging: %d)" % (lost, 4 * piece)
+    bad = off.copy(); bad[100] = bad[99] - 5
+    with pytest.raises(N.NativeError):
+        cycle(bad)
+    assert cycle().reads == n
