@@ -268,6 +268,33 @@ int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_
 int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const int64_t *offsets, int64_t n, int num_pairs_required,
                                   const int32_t *ranges, int64_t *seg_offsets, int32_t *segs, int32_t *n_segs, uint8_t *support,
                                   int64_t *koffsets);
+/* Mismatch correction of host sequences — GraphUtils.correctMismatches (R/util/GraphUtils.java:3914-3996, the last step of
+ * correctErrorHelper :3904): a low-coverage k-mer between two solid ones is replaced by the substitution whose k windows have the best
+ * median coverage.  The two scans run on the device, a wavefront per sequence; the host gets the corrected text back.
+ *   Input: sequence i is seq[offsets[i], offsets[i+1]) with threshold T = cov_threshold[i] (the reference's covThreshold: e.g.
+ *   rb_cov_stats.se_threshold) and one min_kmer_cov.  Its k-mer list is getKmers(String)'s, as rb_graph_kmers gives it: every window,
+ *   nk = max(0, len - k + 1), count 0 for a window with a letter outside ACGTU.  c[p] = count of window p, s = the sequence's bytes.
+ *   Forward scan, i = 1 .. nk - k - 1 ascending.  Candidate: c[i] < T, c[i-1] >= T, c[i+k] >= T.  best = median of c[i .. i+k-2] — k - 1
+ *   counts, the reference's getMedianKmerCoverage(kmers, i, i+k-1); the median of an even number of counts is (a + b) / 2.0f.  For each
+ *   alternative of base s[i+k-1] in the order of SeqUtils.getAltNucleotides (the other three of A C G T; U as T; any other letter, lower
+ *   case included: all four) whose variant k-mer is in dbgbf (getRightVariants(String): graph.contains, not getCount): the k windows of
+ *   s[i .. i+2k-2] with that base substituted, counted as getKmers counts them; the variant wins if their minimum >= min_kmer_cov and
+ *   their median > best (strictly: the first of equal medians stays), and best becomes that median.  A winner replaces s[i+k-1] and
+ *   c[i .. i+k-1]; the scan goes on at i + 1 on the changed profile.
+ *   Reverse scan over the result, i = nk - 2 .. k descending: c[i] < T, c[i+1] >= T, c[i-k] >= T; best = median of c[i-k+1 .. i-1];
+ *   alternatives of s[i] (getLeftVariants(String)); windows i-k+1 .. i; the same acceptance; s[i] and c[i-k+1 .. i] replaced.
+ *   Output: out_seq[offsets[i], offsets[i+1]) = the corrected sequence (the layout of seq; out_seq may be seq), n_fixed[i] = the number
+ *   of replacements (the reference's `corrected` is n_fixed[i] > 0).  koffsets (host, n + 1, optional): getKmers' k-mer offsets; counts
+ *   (optional, requires koffsets): the final c of sequence i at counts[koffsets[i] + p] — rb_graph_kmers' counts of out_seq.
+ *   Sequences with nk <= k + 1 or T <= 0 come back unchanged.
+ * The call works in pieces of bounded device scratch (RB_QUERY_PIECE k-mers, as rb_graph_kmers); results do not depend on the cuts.  It
+ * leases a query context like the other lookups (re-entrant on one handle).  With rb_graph_profile_enable on, the kernels' device time is
+ * added to the profile entry "mismatches".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle or a null offsets / cov_threshold / out_seq / n_fixed (or seq, where there is
+ * text); a shard handle; a destroyed dbgbf or counting filter; a threshold or min_kmer_cov that is not finite; decreasing offsets; counts
+ * without koffsets; k < 2 (the reference's median of k - 1 counts does not exist). */
+int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, float min_kmer_cov,
+                                char *out_seq, int32_t *n_fixed, int64_t *koffsets, float *counts);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

@@ -430,6 +430,28 @@ public class BloomFilterDeBruijnGraph {
         return stranded ? new Kmer(b, w.count[i], w.f[i]) : new CanonicalKmer(b, w.count[i], w.f[i], w.r[i]);
     }
 
+    /**
+     * GraphUtils.correctMismatches (src/rnabloom/util/GraphUtils.java:3914-3996) for a batch of sequences in ONE native call: the two scans
+     * run on the device, a wavefront per sequence.  covThresholds[i] is sequence i's covThreshold.  Returns the corrected sequences;
+     * nFixed[i] (optional, seqs.length entries) receives the number of replacements — the reference's `corrected` is nFixed[i] > 0.
+     */
+    public String[] correctMismatches(String[] seqs, float[] covThresholds, float minKmerCov, int[] nFixed) {
+        final int n = seqs.length;
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        final int total = (int) off[n];
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max(total, 1)), out = ByteBuffer.allocateDirect(Math.max(total, 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        final int[] fixed = nFixed != null ? nFixed : new int[n];
+        NativeGraph.correctMismatches(handle, text, off, n, covThresholds, minKmerCov, out, fixed, null, null);
+        final String[] res = new String[n];
+        final byte[] b = new byte[total];
+        out.get(b, 0, total);
+        for (int i = 0; i < n; ++i)
+            res[i] = fixed[i] > 0 ? new String(b, (int) off[i], (int) (off[i + 1] - off[i]), java.nio.charset.StandardCharsets.ISO_8859_1) : seqs[i];
+        return res;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

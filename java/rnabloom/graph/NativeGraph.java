@@ -100,6 +100,12 @@ public final class NativeGraph {
      *  k-mer, 1 where the pair at that position is in the filter.  Returns the number of segment slots. */
     public static native long pairedKmerSegments(long h, int which, ByteBuffer seq, long[] offsets, int n, int numPairsRequired, int[] ranges,
                                                  long[] segOffsets, int[] segs, int[] nSegs, byte[] support, long[] koffsets);
+    /** Mismatch correction of n sequences (rb_graph_correct_mismatches; GraphUtils.correctMismatches, R/util/GraphUtils.java:3914-3996):
+     *  covThreshold[n] one threshold per sequence, outSeq a direct buffer with seq's layout that receives the corrected bases, nFixed[n]
+     *  the number of replacements per sequence.  koffsets[n + 1] (optional) and counts (optional, with koffsets: one float per k-mer at
+     *  koffsets[i] + p) return the final count profile — getKmers of the corrected sequences. */
+    public static native void correctMismatches(long h, ByteBuffer seq, long[] offsets, int n, float[] covThreshold, float minKmerCov,
+                                                ByteBuffer outSeq, int[] nFixed, long[] koffsets, float[] counts);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

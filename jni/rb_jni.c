@@ -368,6 +368,18 @@ jlong FN(pairedKmerSegments)(JNIEnv *e, jclass c, jlong h, jint which, jobject s
     if (rc) throw_rc(e, rc);
     return slots;
 }
+/* rb_graph_correct_mismatches: outSeq is a direct buffer laid out like seq; koffsets / counts may be null (counts needs koffsets) */
+void FN(correctMismatches)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jfloatArray covThreshold, jfloat minKmerCov,
+                           jobject outSeq, jintArray nFixed, jlongArray koffsets, jfloatArray counts) {
+    jlong *off = la(e, offsets), *ko = la(e, koffsets);
+    jfloat *thr = fa(e, covThreshold), *pc = fa(e, counts);
+    jint *nf = ia(e, nFixed);
+    (void)c;
+    int rc = rb_graph_correct_mismatches(G(h), (const char *)direct(e, seq), (const int64_t *)off, n, thr, minKmerCov, (char *)direct(e, outSeq),
+                                         (int32_t *)nf, (int64_t *)ko, pc);
+    lr(e, offsets, off, JNI_ABORT); fr(e, covThreshold, thr, JNI_ABORT); ir(e, nFixed, nf, 0); lr(e, koffsets, ko, 0); fr(e, counts, pc, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -1,0 +1,403 @@
+// rb_mismatch.hip — mismatch correction of host sequences (rb_graph_correct_mismatches): GraphUtils.correctMismatches
+// (R/util/GraphUtils.java:3914-3996, the last step of correctErrorHelper :3904) on the device.  Per piece the getKmers kernel leaves the
+// forward / reverse hashes and the count of every window in device scratch; k_mismatch then runs the reference's two scans, a wavefront per
+// sequence, on a row of one count code per window, and rewrites text, hashes and codes in place wherever a variant wins.  Only the
+// sequences and thresholds go in and the corrected sequences, the number of replacements and (on request) the final count rows come out
+// (DESIGN.md §5 "Mismatch correction").
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "rb_kernels.hpp"
+#include "rb_pipeline.hpp"
+
+using namespace rb;
+
+// Java float arithmetic: the median of an even number of counts is one float32 sum and one float32 division
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int MM_TPB = 256;
+constexpr int MM_WAVES = MM_TPB / 64;    // sequences per workgroup: a wavefront each
+constexpr int MM_LDS_ROW = 4096;         // windows of a sequence whose code row lives in LDS; longer ones keep it in device scratch
+constexpr int MM_SLOTS = (RB_MAX_K + 63) / 64;   // windows a lane owns of the k windows of one candidate
+
+// a count as one byte: 0 = absent (or a window with an unusable base), 1 + c = MiniFloat code c — the 129 values getCount can return,
+// in increasing order of value (BloomFilterDeBruijnGraph.getCount :562-570 = MiniFloat.toFloat(code) + 1, or 0)
+__device__ __forceinline__ float mm_value(uint32_t b) { return b == 0u ? 0.0f : minifloat_to_float(b - 1u) + 1.0f; }
+__device__ __forceinline__ uint32_t mm_code_of(float c) {
+    if (!(c > 0.0f)) return 0u;
+    const uint32_t v = (uint32_t)(c - 1.0f);
+    uint32_t code = v;
+    if (v > 7u) {
+        const uint32_t e = 31u - (uint32_t)__clz(v) - 3u;            // v = (8 | m) << e
+        code = ((e + 1u) << 3) | ((v >> e) & 7u);
+    }
+    return code < 128u ? 1u + code : 128u;
+}
+// the smallest code whose value is >= t (129: none): `count >= t` is `code >= mm_threshold_code(t)` for every count there is
+__device__ __forceinline__ uint32_t mm_threshold_code(float t, uint32_t lane) {
+    const unsigned long long m0 = __ballot(mm_value(lane) >= t), m1 = __ballot(mm_value(64u + lane) >= t);
+    if (m0) return (uint32_t)__builtin_ctzll(m0);
+    if (m1) return 64u + (uint32_t)__builtin_ctzll(m1);
+    return mm_value(128u) >= t ? 128u : 129u;
+}
+
+// rotation by a run-time amount out of 32-bit funnel shifts: no 64-bit shift takes its amount from a vector register here
+__device__ __forceinline__ uint64_t rot64(uint64_t v, uint32_t s) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    if (s & 32u) { const uint32_t t = lo; lo = hi; hi = t; }
+    const uint32_t t = s & 31u;
+    const uint32_t nh = t ? __builtin_amdgcn_alignbit(hi, lo, 32u - t) : hi;
+    const uint32_t nl = t ? __builtin_amdgcn_alignbit(lo, hi, 32u - t) : lo;
+    return ((uint64_t)nh << 32) | nl;
+}
+
+// seeds of a raw letter as getKmers(String) hashes it: forward seedTab row of [ACGTU] in either case, else 0; reverse strand
+// seedTab[ch & 7] (NTHash.java:30, 133-166: classes 1 T, 3 G, 4 A, 5 A, 7 C, the others 0) — what the batch's valid / rnz planes encode
+__device__ __forceinline__ void mm_seeds_of_char(uint32_t ch, uint64_t &s, uint64_t &sc) {
+    uint32_t code = 4u;
+    switch (ch) {
+        case 'A': case 'a': code = 0u; break;
+        case 'C': case 'c': code = 1u; break;
+        case 'G': case 'g': code = 2u; break;
+        case 'T': case 't': case 'U': case 'u': code = 3u; break;
+        default: break;
+    }
+    s = code < 4u ? seed_of(code) : 0ull;
+    const uint32_t cls = ch & 7u;
+    const uint32_t rc = cls == 1u ? 0u : cls == 3u ? 1u : cls == 7u ? 2u : 3u;
+    sc = ((0xBAu >> cls) & 1u) ? seed_of(3u - rc) : 0ull;
+}
+// SeqUtils.getAltNucleotides (R/util/SeqUtils.java:147-162) as a mask over A C G T (bit a = base a is tried, in that order): the other
+// three of an upper-case A C G T, U as T, all four for any other letter (lower case included: the switch knows upper case only)
+__device__ __forceinline__ uint32_t mm_alt_mask(uint32_t ch) {
+    switch (ch) {
+        case 'A': return 0xEu;
+        case 'C': return 0xDu;
+        case 'G': return 0xBu;
+        case 'T': case 'U': return 0x7u;
+        default: return 0xFu;
+    }
+}
+
+// are the bases [j, j + k) of the sequence usable, position q (the one being replaced by A C G T) left out?
+__device__ __forceinline__ bool mm_window_clean(const uint32_t *__restrict__ vw, uint32_t j, uint32_t k, uint32_t q) {
+    bool ok = true;
+    for (uint32_t b = j; b < j + k;) {
+        const uint32_t lo = b & 31u, n = min(32u - lo, j + k - b);
+        const uint32_t mask = (n == 32u ? ~0u : ((1u << n) - 1u)) << lo;
+        uint32_t miss = ~vw[b >> 5] & mask;
+        if ((q >> 5) == (b >> 5)) miss &= ~(1u << (q & 31u));
+        ok = ok && miss == 0u;
+        b += n;
+    }
+    return ok;
+}
+
+// One window of a candidate under each of the four substitutions: ntHash is XOR-linear, so with the replaced base at exponent ef on the
+// forward strand and er on the reverse strand the variant's hashes are f ^ rotl(seed(old) ^ seed(new), ef) and the mirrored term — no
+// rolling.  Returns the four count codes (byte a = substitution a; 0 where the window has another unusable base, `clean` false) and in
+// `inmask` bit a = the variant window is in dbgbf (graph.contains: the Bloom bits alone).  With two hash functions per filter — every
+// configuration the reference runs — the 8 Bloom-bit loads and the 8 counter loads of the four variants are issued before any is
+// consumed; a substitution that is not tried (the base itself) probes its neighbour's lines again instead of the window's own.
+__device__ __forceinline__ uint32_t mm_variant_codes(const FilterView &fv, int stranded, uint64_t f, uint64_t r, uint64_t so, uint64_t sco,
+                                                     uint32_t ef, uint32_t er, uint32_t altmask, bool clean, uint32_t &inmask) {
+    uint64_t h[4];
+#pragma unroll
+    for (uint32_t a = 0; a < 4u; ++a) {
+        const uint64_t nf = f ^ rot64(so ^ seed_of(a), ef);
+        const uint64_t nr = r ^ rot64(sco ^ seed_of(3u - a), er);
+        h[a] = stranded ? nf : canonical(nf, nr);
+    }
+#pragma unroll
+    for (uint32_t a = 0; a < 4u; ++a)
+        if (!((altmask >> a) & 1u)) h[a] = h[a ^ 1u];
+    uint32_t codes = 0;
+    inmask = 0;
+    if (fv.dbg_h == 2 && fv.cbf_h == 2) {
+        uint64_t bi[4][2], ci[4][2];
+        uint32_t bw[4][2], cb[4][2];
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; ++a) {
+            const uint64_t h1 = multi_hash(h[a], 1u, fv.kmul);
+            bi[a][0] = index_of(h[a], fv.dbg_mod); bi[a][1] = index_of(h1, fv.dbg_mod);
+            ci[a][0] = index_of(h[a], fv.cbf_mod); ci[a][1] = index_of(h1, fv.cbf_mod);
+        }
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; ++a) { bw[a][0] = fv.dbg[bi[a][0] >> 5]; bw[a][1] = fv.dbg[bi[a][1] >> 5]; }
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; ++a) { cb[a][0] = fv.cbf[ci[a][0]]; cb[a][1] = fv.cbf[ci[a][1]]; }
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; ++a) {
+            const uint32_t in = (bw[a][0] >> (uint32_t)(bi[a][0] & 31u)) & (bw[a][1] >> (uint32_t)(bi[a][1] & 31u)) & 1u;
+            const uint32_t mn = cb[a][0] < cb[a][1] ? cb[a][0] : cb[a][1];
+            inmask |= in << a;
+            codes |= ((in && clean) ? 1u + mn : 0u) << (8u * a);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t a = 0; a < 4u; ++a) {
+            const bool in = bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h[a]);
+            uint32_t mn = 0;
+            if (in && clean) {                       // CountingBloomFilter.getCount(long[]) :235-251
+                mn = fv.cbf[index_of(h[a], fv.cbf_mod)];
+                for (int j = 1; j < fv.cbf_h; ++j) mn = min(mn, (uint32_t)fv.cbf[index_of(multi_hash(h[a], (uint32_t)j, fv.kmul), fv.cbf_mod)]);
+            }
+            inmask |= (in ? 1u : 0u) << a;
+            codes |= ((in && clean) ? 1u + mn : 0u) << (8u * a);
+        }
+    }
+    return codes;
+}
+
+// Common.getMedian (R/util/Common.java:41-50) of the n codes a wavefront holds in c[] (lane l, slot s: element 64 s + l; 255 past the end):
+// sorted[n / 2], or (sorted[n / 2 - 1] + sorted[n / 2]) / 2.0f.  An order statistic is found by bisection over the 129 code values with
+// one ballot per slot and step: no sort, no LDS.
+__device__ __forceinline__ uint32_t mm_kth(const uint32_t (&c)[MM_SLOTS], int n, int rank) {
+    uint32_t lo = 0, hi = 128;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        int cnt = 0;
+#pragma unroll
+        for (int s = 0; s < MM_SLOTS; ++s)
+            if (s * 64 < n) cnt += __popcll(__ballot(c[s] <= mid));
+        if (cnt >= rank + 1) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+__device__ __forceinline__ float mm_median(const uint32_t (&c)[MM_SLOTS], int n) {
+    const float hi = mm_value(mm_kth(c, n, n / 2));
+    if (n & 1) return hi;
+    return (mm_value(mm_kth(c, n, n / 2 - 1)) + hi) / 2.0f;
+}
+
+// A wavefront per sequence: sequence r of the piece has windows [kof[r], kof[r + 1]) of F / R / cnt (what the getKmers kernel left) and
+// text txt[tof[r] ...].  LDS_ROW: workgroup b takes sequences 4 b .. 4 b + 3, the code row of each in LDS, and leaves those with more
+// than MM_LDS_ROW windows to the other instantiation, which takes the sequences listed in ids and keeps the row in grow.
+//   Both scans of the reference are one loop here (dir 0: i = 1 .. nk - k - 1 ascending, dir 1: i = nk - 2 .. k descending): 64 positions
+// are tested at a time (count[i] < T, the neighbour behind >= T, the k-mer k windows on >= T: three code compares), the ballot's first
+// position is handled and the scan resumes right behind it on the changed row.  In both directions the k windows that hold the replaced
+// base are j0 .. j0 + k - 1 with the base q = j0 + k - 1 at offset k - 1 - w of window j0 + w, the baseline is the median of the k - 1
+// codes row[j0 .. j0 + k - 2] (getMedianKmerCoverage(kmers, i, i + k - 1): one short of the k windows — reproduced), and the variant
+// k-mer that has to be in dbgbf is window i itself (w = 0 forward, w = k - 1 in reverse).  Lane w owns window j0 + w (w += 64 while
+// w < k), expands all four substitutions at once (mm_variant_codes) and parks the four codes in LDS; minimum >= min_kmer_cov is one
+// ballot per slot, the median a bisection (mm_median).  A winner rewrites the base, the valid bit, k codes and k hash pairs.
+//   The wavefront's lanes hand values to each other through the code row and its own rows of hashes in device memory: the fence after the
+// row is filled and after every replacement waits for those stores before any lane reads them.
+template <bool LDS_ROW>
+__global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded, int k, float min_cov, int64_t pn, const int64_t *__restrict__ ids,
+                                                     int64_t n_ids, const int64_t *__restrict__ kof, const int64_t *__restrict__ tof,
+                                                     const uint32_t *__restrict__ woff, uint32_t *valid, uint8_t *txt, uint64_t *F, uint64_t *R, float *cnt,
+                                                     uint8_t *grow, const float *__restrict__ thr, int32_t *__restrict__ n_fixed, int write_counts) {
+    __shared__ uint8_t s_row[MM_WAVES][LDS_ROW ? MM_LDS_ROW : 4];
+    __shared__ uint32_t s_vc[MM_WAVES][RB_MAX_K];
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const int64_t slot = (int64_t)blockIdx.x * MM_WAVES + wv;
+    int64_t r;
+    if constexpr (LDS_ROW) { if (slot >= pn) return; r = slot; }
+    else { if (slot >= n_ids) return; r = ids[slot]; }
+    const int64_t k0 = kof[r];
+    const int32_t nk = (int32_t)(kof[r + 1] - k0);
+    if (LDS_ROW && nk > MM_LDS_ROW) return;
+    const float T = thr[r];
+    if (nk <= k + 1 || !(T > 0.0f)) {                    // neither loop of the reference has a position / no count is below T
+        if (lane == 0) n_fixed[r] = 0;
+        return;
+    }
+    uint8_t *row;
+    if constexpr (LDS_ROW) row = s_row[wv]; else row = grow + k0;
+    uint32_t *vc = s_vc[wv];
+    uint32_t *vw = valid + woff[r];
+    uint8_t *tx = txt + tof[r];
+    uint64_t *f_ = F + k0, *r_ = R + k0;
+    float *c_ = cnt + k0;
+    const uint32_t tcode = mm_threshold_code(T, lane), mcode = mm_threshold_code(min_cov, lane);
+    for (int32_t p = (int32_t)lane; p < nk; p += 64) row[p] = (uint8_t)mm_code_of(c_[p]);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    int32_t nfix = 0;
+    for (int dir = 0; dir < 2; ++dir) {
+        const int32_t step = dir ? -1 : 1, lim = dir ? k : nk - k - 1;
+        int32_t base = dir ? nk - 2 : 1;
+        while (dir ? base >= lim : base <= lim) {
+            const int32_t p = base + step * (int32_t)lane;
+            bool cand = false;
+            if (dir ? p >= lim : p <= lim) cand = row[p] < tcode && row[p - step] >= tcode && row[p + step * k] >= tcode;
+            const unsigned long long m = __ballot(cand);
+            if (!m) { base += step * 64; continue; }
+            const int32_t i = base + step * (int32_t)__builtin_ctzll(m);
+            const int32_t j0 = dir ? i - k + 1 : i, gw = dir ? k - 1 : 0, q = j0 + k - 1;
+            const uint32_t ch = tx[q];
+            const uint32_t altmask = mm_alt_mask(ch);
+            uint64_t so, sco;
+            mm_seeds_of_char(ch, so, sco);
+            // the k windows under the four substitutions
+            uint32_t gl = 0;
+            for (int32_t w = (int32_t)lane; w < k; w += 64) {
+                const int32_t j = j0 + w;
+                uint32_t in;
+                const uint32_t pk = mm_variant_codes(fv, stranded, f_[j], stranded ? 0ull : r_[j], so, sco, (uint32_t)w, (uint32_t)(k - 1 - w), altmask,
+                                                     mm_window_clean(vw, (uint32_t)j, (uint32_t)k, (uint32_t)q), in);
+                vc[w] = pk;
+                if (w == gw) gl = in;
+            }
+            const uint32_t gate = (uint32_t)__shfl((int)gl, gw & 63, 64) & altmask;      // getRightVariants / getLeftVariants(String): contains(v)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            uint32_t cc[MM_SLOTS];
+#pragma unroll
+            for (int s = 0; s < MM_SLOTS; ++s) { const int32_t w = s * 64 + (int32_t)lane; cc[s] = w < k - 1 ? row[j0 + w] : 255u; }
+            float best = mm_median(cc, k - 1);
+            int besta = -1;
+            for (int a = 0; a < 4; ++a) {
+                if (!((gate >> a) & 1u)) continue;
+                bool low = false;
+#pragma unroll
+                for (int s = 0; s < MM_SLOTS; ++s) {
+                    const int32_t w = s * 64 + (int32_t)lane;
+                    cc[s] = w < k ? (vc[w] >> (8 * a)) & 255u : 255u;
+                    low = low || cc[s] < mcode;
+                }
+                if (__ballot(low)) continue;                         // getMinMedMaxKmerCoverage: m[0] >= minKmerCov
+                const float med = mm_median(cc, k);
+                if (med > best) { best = med; besta = a; }           // strictly: the first of equal medians stays
+            }
+            if (besta >= 0) {
+                const uint64_t df = so ^ seed_of((uint32_t)besta), dr = sco ^ seed_of(3u - (uint32_t)besta);
+                for (int32_t w = (int32_t)lane; w < k; w += 64) {
+                    const int32_t j = j0 + w;
+                    row[j] = (uint8_t)((vc[w] >> (8 * besta)) & 255u);
+                    f_[j] ^= rot64(df, (uint32_t)w);
+                    if (!stranded) r_[j] ^= rot64(dr, (uint32_t)(k - 1 - w));
+                }
+                if (lane == 0) {
+                    tx[q] = (uint8_t)(besta == 0 ? 'A' : besta == 1 ? 'C' : besta == 2 ? 'G' : 'T');
+                    vw[q >> 5] |= 1u << (q & 31);
+                }
+                ++nfix;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            }
+            base = i + step;
+        }
+    }
+    if (write_counts)
+        for (int32_t p = (int32_t)lane; p < nk; p += 64) c_[p] = mm_value(row[p]);
+    if (lane == 0) n_fixed[r] = nfix;
+}
+
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, float min_kmer_cov,
+                                char *out_seq, int32_t *n_fixed, int64_t *koffsets, float *counts) {
+    return guarded([&] {
+        RB_REQUIRE(g && offsets && cov_threshold && out_seq && n_fixed && n >= 0, "rb_graph_correct_mismatches: null argument");
+        RB_REQUIRE(!g->shard, "rb_graph_correct_mismatches: not available on a shard handle");
+        RB_REQUIRE(g->dbg.bits && g->cbf, "rb_graph_correct_mismatches: dbgbf or the counting filter has been destroyed");
+        RB_REQUIRE(g->k >= 2, "rb_graph_correct_mismatches: k = %d (the reference's median of k - 1 counts needs k >= 2)", g->k);
+        RB_REQUIRE(std::isfinite(min_kmer_cov), "rb_graph_correct_mismatches: min_kmer_cov must be finite");
+        RB_REQUIRE(!counts || koffsets, "rb_graph_correct_mismatches: counts needs koffsets");
+        const int64_t uk = g->k;
+        std::vector<int64_t> ko((size_t)n + 1, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t l = offsets[i + 1] - offsets[i], nk = l >= uk ? l - uk + 1 : 0;
+            RB_REQUIRE(l >= 0, "rb_graph_correct_mismatches: offsets[%lld] > offsets[%lld]", (long long)i, (long long)i + 1);
+            RB_REQUIRE(nk <= INT32_MAX, "rb_graph_correct_mismatches: sequence %lld has more k-mers than an int holds", (long long)i);
+            RB_REQUIRE(std::isfinite(cov_threshold[i]), "rb_graph_correct_mismatches: cov_threshold[%lld] is not finite", (long long)i);
+            ko[(size_t)i + 1] = ko[(size_t)i] + nk;
+        }
+        const int64_t text = n ? offsets[n] - offsets[0] : 0;
+        RB_REQUIRE(text == 0 || seq, "rb_graph_correct_mismatches: null sequence text");
+        if (koffsets) std::copy(ko.begin(), ko.end(), koffsets);
+        if (n == 0) return;
+        // what no kernel touches comes back as it went in: sequences shorter than k, pieces without a k-mer
+        std::fill(n_fixed, n_fixed + n, 0);
+        if (text && out_seq != seq) memmove(out_seq + offsets[0], seq + offsets[0], (size_t)text);
+        const int64_t total = ko[(size_t)n];
+        if (total == 0) return;
+        RB_HIP(hipSetDevice(g->p.device));
+        HostPin pin_seq(seq + offsets[0], (size_t)text), pin_out(out_seq + offsets[0], (size_t)text), pin_thr(cov_threshold, (size_t)n * 4),
+                pin_nf(n_fixed, (size_t)n * 4), pin_cnt(counts, counts ? (size_t)total * 4 : 0);
+        QueryLease q(g);
+        const FilterView fv = g->view(0, 0);
+        hipStream_t s = q.c->st;
+        // with profiling on (rb_graph_profile_enable) the kernels of every piece are timed by events on the query stream: entry "mismatches"
+        const bool prof = g->prof_on;
+        rb::Event ev[2];
+        if (prof) { RB_HIP(hipEventCreate(&ev[0].e)); RB_HIP(hipEventCreate(&ev[1].e)); }
+        double prof_ms = 0;
+        int64_t prof_n = 0;
+        // pieces of <= 16 M k-mers, as rb_graph_kmers: 21 bytes of scratch a k-mer (two hashes, the count, the long sequences' code row),
+        // the text and the piece's batch
+        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)16 << 20;
+        std::vector<int64_t> tab;
+        for (int64_t ra = 0; ra < n;) {
+            int64_t lo = ra + 1, hi = n;
+            while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (ko[(size_t)mid] - ko[(size_t)ra] <= piece_max) lo = mid; else hi = mid - 1; }
+            const int64_t rb_ = lo, pn = rb_ - ra, pt = ko[(size_t)rb_] - ko[(size_t)ra], tb = offsets[rb_] - offsets[ra];
+            if (pt == 0) { ra = rb_; continue; }
+            // the piece's table: k-mer offsets [pn + 1], text offsets [pn + 1], the sequences whose code row does not fit LDS
+            tab.assign((size_t)(2 * pn + 2), 0);
+            for (int64_t i = 0; i <= pn; ++i) {
+                tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
+                tab[(size_t)(pn + 1 + i)] = offsets[ra + i] - offsets[ra];
+            }
+            for (int64_t i = 0; i < pn; ++i)
+                if (tab[(size_t)i + 1] - tab[(size_t)i] > MM_LDS_ROW) tab.push_back(i);
+            const int64_t nlong = (int64_t)tab.size() - (2 * pn + 2);
+            rb::AsciiUpload up;
+            rb_batch *b = nullptr;
+            try {
+                rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
+                b = rb::ascii_batch_finish(up);
+            } catch (...) { rb::ascii_batch_abort(up); throw; }
+            rb::BatchPtr guard(b);
+            // b3: counts [pt] floats, thresholds [pn], replacements [pn], text [tb], code rows of the long sequences [pt]
+            const size_t o_thr = (size_t)pt * 4, o_nf = o_thr + (size_t)pn * 4, o_txt = o_nf + (size_t)pn * 4, o_row = up16(o_txt + (size_t)tb);
+            q.c->b0.reserve(tab.size() * 8);
+            q.c->b1.reserve((size_t)pt * 8);
+            q.c->b2.reserve((size_t)pt * 8);
+            q.c->b3.reserve(o_row + (nlong ? (size_t)pt : 0) + 16);
+            const int64_t *dkof = q.c->b0.as<int64_t>(), *dtof = dkof + pn + 1, *dids = dtof + pn + 1;
+            uint8_t *base3 = q.c->b3.as<uint8_t>();
+            float *dcnt = reinterpret_cast<float *>(base3), *dthr = reinterpret_cast<float *>(base3 + o_thr);
+            int32_t *dnf = reinterpret_cast<int32_t *>(base3 + o_nf);
+            uint8_t *dtxt = base3 + o_txt, *drow = base3 + o_row;
+            RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+            RB_HIP(hipMemcpyAsync(dthr, cov_threshold + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
+            RB_HIP(hipMemcpyAsync(dtxt, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
+            if (prof) RB_HIP(hipEventRecord(ev[0], s));
+            rb::launch_get_kmers(g, b, dkof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, s);
+            hipLaunchKernelGGL((k_mismatch<true>), dim3(blocks_for(pn, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov, pn,
+                               (const int64_t *)nullptr, (int64_t)0, dkof, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(),
+                               dcnt, drow, dthr, dnf, counts ? 1 : 0);
+            RB_HIP(hipGetLastError());
+            if (nlong) {
+                hipLaunchKernelGGL((k_mismatch<false>), dim3(blocks_for(nlong, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov,
+                                   pn, dids, nlong, dkof, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, drow,
+                                   dthr, dnf, counts ? 1 : 0);
+                RB_HIP(hipGetLastError());
+            }
+            if (prof) RB_HIP(hipEventRecord(ev[1], s));
+            RB_HIP(hipMemcpyAsync(out_seq + offsets[ra], dtxt, (size_t)tb, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(n_fixed + ra, dnf, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+            if (counts) RB_HIP(hipMemcpyAsync(counts + ko[(size_t)ra], dcnt, (size_t)pt * 4, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipStreamSynchronize(s));                    // (the table and the piece's batch are released next)
+            if (prof) { float ms = 0; RB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); prof_ms += ms; ++prof_n; }
+            ra = rb_;
+        }
+        if (prof && prof_n) {
+            std::lock_guard<std::mutex> lk(g->qm);          // (queries share the handle: the profile table is written under the context lock)
+            bool found = false;
+            for (auto &e : g->prof) if (!strcmp(e.name, "mismatches")) { e.ms += prof_ms; e.launches += prof_n; found = true; break; }
+            if (!found) g->prof.push_back({"mismatches", prof_ms, prof_n});
+        }
+    });
+}
+}  // extern "C"

@@ -559,6 +559,8 @@ void trav_free(rb_graph *g);    // rb_query.hip: state of a traversal on a shard
 void cbf_counts_device(rb_graph *g, const uint64_t *d_h0, size_t n, float *d_out);   // rb_query.hip
 void launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, uint32_t r_first, const int64_t *koff,   // rb_query.hip: k_batch_counts
                          int64_t row_base, float *dst, hipStream_t s);                                                   // with packed rows
+void launch_get_kmers(rb_graph *g, const rb_batch *b, const int64_t *koff, uint64_t *f, uint64_t *r, float *count, hipStream_t s);   // rb_query.hip: k_get_kmers
+                                                                                          // over a whole batch made with the rnz plane: window p of read i at koff[i] + p
 void launch_pairs(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, int mode_hash, const uint32_t *chunk_off,
                   uint64_t *out_idx, unsigned long long *n_pairs_dev, hipStream_t st = nullptr, const BitFilter *into = nullptr /* another bit array of the pair filter's geometry (the sharded engine's accumulation copy) */);
 }  // namespace rb

@@ -694,6 +694,15 @@ void rb::launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t
     RB_HIP(hipGetLastError());
 }
 
+// getKmers of every read of a batch made from raw strings (rb_graph_kmers' kernel, for callers that keep the rows on the device:
+// rb_mismatch.hip): hashes and count of window p of read i at koff[i] + p
+void rb::launch_get_kmers(rb_graph *g, const rb_batch *b, const int64_t *koff, uint64_t *f, uint64_t *r, float *count, hipStream_t s) {
+    if (b->n_words > 0)
+        hipLaunchKernelGGL(k_get_kmers<false>, dim3(blocks_for(b->n_words)), dim3(TPB), 0, s, g->view(0, 0), (int)g->stranded, b->codes, b->valid,
+                           b->rnz, b->word_read, b->woff, b->len, b->n_words, g->k, koff, f, r, count);
+    RB_HIP(hipGetLastError());
+}
+
 using rb::HostPin;
 extern "C" {
 int rb_filter_lookup(rb_graph *g, int which, const uint64_t *h0, size_t n, uint8_t *out) {

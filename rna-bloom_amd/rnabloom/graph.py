@@ -505,6 +505,30 @@ class BloomFilterDeBruijnGraph:
         _, _, _, ko, sup = self.pairedKmerSegmentsFlat(which, seq, off, 1, None, support=True)
         return [sup[ko[i]:ko[i + 1]].astype(bool) for i in range(len(seqs))]
 
+    def correctMismatchesFlat(self, seq, offsets, thresholds, minKmerCov=1.0, counts=False):
+        """rb_graph_correct_mismatches on flat host text: sequence i is seq[offsets[i]:offsets[i + 1]] (uint8), thresholds one covThreshold
+        per sequence (a scalar is used for all of them).  Returns (out, n_fixed, koffsets, count_rows): out has seq's layout with the
+        corrected bases, n_fixed[i] is the number of replacements in sequence i, count_rows (None unless asked for) the final count of
+        every k-mer at koffsets[i] + p — getKmers of the corrected sequence."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float32), (n,)))
+        out = np.array(seq, copy=True)
+        nf = np.zeros(n, np.int32); ko = np.zeros(n + 1, np.int64)
+        cnt = np.zeros(int(np.maximum(np.diff(off) - self.k + 1, 0).sum()), np.float32) if counts else None
+        check(lib.rb_graph_correct_mismatches(self.h, _ptr(seq), _ptr(off), n, _ptr(thr), minKmerCov, _ptr(out), _ptr(nf), _ptr(ko), _ptr(cnt)))
+        return out, nf, ko, cnt
+
+    def correctMismatches(self, seqs, thresholds, minKmerCov=1.0):
+        """GraphUtils.correctMismatches (R/util/GraphUtils.java:3914-3996) of each sequence's getKmers list: per sequence
+        (corrected bytes, number of replacements) — the reference's `corrected` is a number > 0.  thresholds: one covThreshold per
+        sequence (coverageStats' se_threshold, say) or a scalar."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        out, nf, _, _ = self.correctMismatchesFlat(seq, off, thresholds, minKmerCov)
+        return [(out[off[i]:off[i + 1]].tobytes(), int(nf[i])) for i in range(len(seqs))]
+
     def getNeighbors(self, f, r, charOut, direction):
         """4 successors (direction 0) / predecessors (1) of each k-mer: (f4, r4, count4) shaped [n,4]."""
         f = _u64(np.atleast_1d(f)); r = _u64(np.atleast_1d(r))
