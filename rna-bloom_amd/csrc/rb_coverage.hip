@@ -4,12 +4,11 @@
 // from a 129-bin histogram per segment instead of a sort on the host (DESIGN.md §5 "Coverage statistics").
 #include <math.h>
 #include <cmath>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "rb_pipeline.hpp"
+#include "rb_pieces.hpp"
 
 using namespace rb;
 
@@ -18,23 +17,10 @@ using namespace rb;
 
 namespace {
 
-constexpr int COV_BINS = 129;            // 0 = absent, 1 + c = MiniFloat code c (0..127) — every count getCount can return
+constexpr int COV_BINS = 129;            // a bin per count code (count_code_of, rb_device.hpp): every count getCount can return
 constexpr int COV_TPB = 256;
 constexpr int64_t COV_LONG = 4096;       // segments of at least this many windows get a workgroup of their own
 
-// the value of a histogram bin: BloomFilterDeBruijnGraph.getCount (:562-570) = MiniFloat.toFloat(code) + 1, or 0
-__device__ __forceinline__ float cov_bin_value(int b) { return b == 0 ? 0.0f : minifloat_to_float((uint32_t)(b - 1)) + 1.0f; }
-// its inverse: the bin of a count (counts are exact small integers; anything else would be a bug upstream, clamped to stay in LDS)
-__device__ __forceinline__ int cov_bin_of(float c) {
-    if (!(c > 0.0f)) return 0;
-    const uint32_t v = (uint32_t)(c - 1.0f);
-    uint32_t code = v;
-    if (v > 7u) {
-        const uint32_t e = 31u - (uint32_t)__clz(v) - 3u;          // v = (8 | m) << e
-        code = ((e + 1u) << 3) | ((v >> e) & 7u);
-    }
-    return code < 128u ? 1 + (int)code : 128;
-}
 // Math.round(float): floor(x + 1/2), exact in double for every float this file rounds
 __device__ __forceinline__ int64_t java_round(float x) { return (int64_t)floor((double)x + 0.5); }
 
@@ -107,7 +93,7 @@ __device__ __forceinline__ int bin_of_rank(const uint32_t *cum, int64_t r) {
 // next lower non-empty bin — the step-by-step loop's answer, multiplicities included.
 __device__ float cov_walk(const uint32_t *cum, int64_t s, float g, bool strict, bool &found) {
     int b = bin_of_rank(cum, s);
-    float v = cov_bin_value(b);
+    float v = count_code_value((uint32_t)b);
     int64_t seen = s - (int64_t)cum[b] + 1;            // elements of bin b at or below the walk's start
     for (;;) {
         const float t = v * g;
@@ -115,7 +101,7 @@ __device__ float cov_walk(const uint32_t *cum, int64_t s, float g, bool strict, 
         int pb = b - 1;
         while (pb >= 0 && cum[pb + 1] == cum[pb]) --pb;
         if (pb < 0) { found = false; return v; }
-        const float pv = cov_bin_value(pb);
+        const float pv = count_code_value((uint32_t)pb);
         if (strict ? t > pv : t >= pv) { found = true; return v; }
         b = pb; v = pv; seen = (int64_t)cum[b + 1] - cum[b];
     }
@@ -161,7 +147,7 @@ __global__ void __launch_bounds__(COV_TPB) k_cov_stats(const float *__restrict__
         const int t1 = (int)java_round((float)k * 0.9f), t2 = (int)java_round((float)(k / 2) * 0.9f), t3 = (int)java_round((float)(k / 3) * 0.9f);
         for (int64_t i = lt; i < n; i += TPS) {
             const float c = prof[row + i];
-            atomicAdd(&h[cov_bin_of(c)], 1u);
+            atomicAdd(&h[count_code_of(c)], 1u);
             solid += c >= p.min_kmer_cov ? 1u : 0u;
             if (COMPLEX && (c > 0.0f || window_usable(vw, (uint32_t)i, k)) && !window_is_repeat(cw32, (uint32_t)i, k, t1, t2, t3)) ++cplx;
         }
@@ -192,7 +178,7 @@ __global__ void __launch_bounds__(COV_TPB) k_cov_stats(const float *__restrict__
         if (lt < 8) {
             const int64_t base = lt < 3 ? q1i : lt < 5 ? halfLen : q3i;       // ranks 0, q1-1, q1, half-1, half, q3-1, q3, n-1
             const int64_t rk = lt == 0 ? 0 : lt == 7 ? n - 1 : base - ((lt & 1) ? 1 : 0);
-            res[grp][lt] = rk >= 0 ? cov_bin_value(bin_of_rank(h, rk)) : 0.0f;
+            res[grp][lt] = rk >= 0 ? count_code_value((uint32_t)bin_of_rank(h, rk)) : 0.0f;
         } else if (lt == 8) {
             const int64_t start = n - 1 - java_round((float)n * p.cov_fpr);
             bool found = false;
@@ -296,18 +282,9 @@ int rb_graph_read_coverage(rb_graph *g, const rb_batch *b, int64_t first, int64_
         if (!out) return;
         const int64_t n_rec = segoff[(size_t)n] + (mates ? n : 0);
         if (n_rec == 0) return;
-        // pieces of <= 64 M windows + reads (the profile is 4 bytes a window, a record 48 bytes): scratch stays bounded whatever n is
-        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)64 << 20;
-        std::vector<int64_t> cut{0};
-        {
-            int64_t acc = 0;
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t c = 1 + nk((size_t)i) + (mates ? 1 + nk((size_t)(n + i)) : 0);
-                if (acc > 0 && acc + c > piece_max) { cut.push_back(i); acc = 0; }
-                acc += c;
-            }
-            cut.push_back(n);
-        }
+        // pieces of <= 64 M windows + reads (rb_pieces.hpp; the profile is 4 bytes a window, a record 48 bytes): scratch stays bounded whatever n is
+        const std::vector<int64_t> cut = piece_cuts_by_cost([&](int64_t i) { return 1 + nk((size_t)i) + (mates ? 1 + nk((size_t)(n + i)) : 0); }, n,
+                                                            query_piece_max((int64_t)64 << 20));
         // per piece, one host table uploaded to b0: koffsets of the reads [pn + 1] (of the mates [pn + 1]), segment rows [nseg + 1], long segments
         struct Piece { int64_t ra, rb, nseg, nlo, nlong, kmers; size_t ko_b, row_at, long_at; std::vector<int64_t> tab; };
         std::vector<Piece> pcs;

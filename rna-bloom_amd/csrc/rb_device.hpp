@@ -127,6 +127,20 @@ __host__ __device__ __forceinline__ float minifloat_to_float(uint32_t b) {
     uint32_t e = (b >> 3) - 1u;                    // 0..14
     return (float)(((b & 7u) | 8u) << e);          // exact: < 2^24
 }
+// A count as one byte: 0 = absent (or a window with an unusable base), 1 + c = MiniFloat code c — the 129 values getCount can return, in
+// increasing order of value (BloomFilterDeBruijnGraph.getCount :562-570 = MiniFloat.toFloat(code) + 1, or 0).  count_code_value: the count
+// of a code; count_code_of: its inverse (counts are exact small integers; anything else would be a bug upstream, clamped to 128).
+__device__ __forceinline__ float count_code_value(uint32_t b) { return b == 0u ? 0.0f : minifloat_to_float(b - 1u) + 1.0f; }
+__device__ __forceinline__ uint32_t count_code_of(float c) {
+    if (!(c > 0.0f)) return 0u;
+    const uint32_t v = (uint32_t)(c - 1.0f);
+    uint32_t code = v;
+    if (v > 7u) {
+        const uint32_t e = 31u - (uint32_t)__clz(v) - 3u;            // v = (8 | m) << e
+        code = ((e + 1u) << 3) | ((v >> e) & 7u);
+    }
+    return code < 128u ? 1u + code : 128u;
+}
 
 // k-mer owner in the sharded engine = the rank that holds the k-mer's FIRST COUNTER: idx_0 = (h0 >>> 1) % cbf_size lies in
 // exactly one rank's index range [lo, hi).  With the usual sizing (dbgbf bits = cbf bytes, both from

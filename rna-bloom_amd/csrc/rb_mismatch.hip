@@ -5,15 +5,13 @@
 // sequences and thresholds go in and the corrected sequences, the number of replacements and (on request) the final count rows come out
 // (DESIGN.md §5 "Mismatch correction").
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "rb_kernels.hpp"
-#include "rb_pipeline.hpp"
+#include "rb_pieces.hpp"
 
 using namespace rb;
 
@@ -27,25 +25,12 @@ constexpr int MM_WAVES = MM_TPB / 64;    // sequences per workgroup: a wavefront
 constexpr int MM_LDS_ROW = 4096;         // windows of a sequence whose code row lives in LDS; longer ones keep it in device scratch
 constexpr int MM_SLOTS = (RB_MAX_K + 63) / 64;   // windows a lane owns of the k windows of one candidate
 
-// a count as one byte: 0 = absent (or a window with an unusable base), 1 + c = MiniFloat code c — the 129 values getCount can return,
-// in increasing order of value (BloomFilterDeBruijnGraph.getCount :562-570 = MiniFloat.toFloat(code) + 1, or 0)
-__device__ __forceinline__ float mm_value(uint32_t b) { return b == 0u ? 0.0f : minifloat_to_float(b - 1u) + 1.0f; }
-__device__ __forceinline__ uint32_t mm_code_of(float c) {
-    if (!(c > 0.0f)) return 0u;
-    const uint32_t v = (uint32_t)(c - 1.0f);
-    uint32_t code = v;
-    if (v > 7u) {
-        const uint32_t e = 31u - (uint32_t)__clz(v) - 3u;            // v = (8 | m) << e
-        code = ((e + 1u) << 3) | ((v >> e) & 7u);
-    }
-    return code < 128u ? 1u + code : 128u;
-}
-// the smallest code whose value is >= t (129: none): `count >= t` is `code >= mm_threshold_code(t)` for every count there is
+// the smallest count code (count_code_of, rb_device.hpp) whose value is >= t (129: none): `count >= t` is `code >= mm_threshold_code(t)` for every count there is
 __device__ __forceinline__ uint32_t mm_threshold_code(float t, uint32_t lane) {
-    const unsigned long long m0 = __ballot(mm_value(lane) >= t), m1 = __ballot(mm_value(64u + lane) >= t);
+    const unsigned long long m0 = __ballot(count_code_value(lane) >= t), m1 = __ballot(count_code_value(64u + lane) >= t);
     if (m0) return (uint32_t)__builtin_ctzll(m0);
     if (m1) return 64u + (uint32_t)__builtin_ctzll(m1);
-    return mm_value(128u) >= t ? 128u : 129u;
+    return count_code_value(128u) >= t ? 128u : 129u;
 }
 
 // rotation by a run-time amount out of 32-bit funnel shifts: no 64-bit shift takes its amount from a vector register here
@@ -172,9 +157,9 @@ __device__ __forceinline__ uint32_t mm_kth(const uint32_t (&c)[MM_SLOTS], int n,
     return lo;
 }
 __device__ __forceinline__ float mm_median(const uint32_t (&c)[MM_SLOTS], int n) {
-    const float hi = mm_value(mm_kth(c, n, n / 2));
+    const float hi = count_code_value(mm_kth(c, n, n / 2));
     if (n & 1) return hi;
-    return (mm_value(mm_kth(c, n, n / 2 - 1)) + hi) / 2.0f;
+    return (count_code_value(mm_kth(c, n, n / 2 - 1)) + hi) / 2.0f;
 }
 
 // A wavefront per sequence: sequence r of the piece has windows [kof[r], kof[r + 1]) of F / R / cnt (what the getKmers kernel left) and
@@ -218,7 +203,7 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
     uint64_t *f_ = F + k0, *r_ = R + k0;
     float *c_ = cnt + k0;
     const uint32_t tcode = mm_threshold_code(T, lane), mcode = mm_threshold_code(min_cov, lane);
-    for (int32_t p = (int32_t)lane; p < nk; p += 64) row[p] = (uint8_t)mm_code_of(c_[p]);
+    for (int32_t p = (int32_t)lane; p < nk; p += 64) row[p] = (uint8_t)count_code_of(c_[p]);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     int32_t nfix = 0;
     for (int dir = 0; dir < 2; ++dir) {
@@ -285,7 +270,7 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
         }
     }
     if (write_counts)
-        for (int32_t p = (int32_t)lane; p < nk; p += 64) c_[p] = mm_value(row[p]);
+        for (int32_t p = (int32_t)lane; p < nk; p += 64) c_[p] = count_code_value(row[p]);
     if (lane == 0) n_fixed[r] = nfix;
 }
 
@@ -303,15 +288,10 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
         RB_REQUIRE(g->k >= 2, "rb_graph_correct_mismatches: k = %d (the reference's median of k - 1 counts needs k >= 2)", g->k);
         RB_REQUIRE(std::isfinite(min_kmer_cov), "rb_graph_correct_mismatches: min_kmer_cov must be finite");
         RB_REQUIRE(!counts || koffsets, "rb_graph_correct_mismatches: counts needs koffsets");
-        const int64_t uk = g->k;
-        std::vector<int64_t> ko((size_t)n + 1, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t l = offsets[i + 1] - offsets[i], nk = l >= uk ? l - uk + 1 : 0;
-            RB_REQUIRE(l >= 0, "rb_graph_correct_mismatches: offsets[%lld] > offsets[%lld]", (long long)i, (long long)i + 1);
-            RB_REQUIRE(nk <= INT32_MAX, "rb_graph_correct_mismatches: sequence %lld has more k-mers than an int holds", (long long)i);
+        std::vector<int64_t> ko((size_t)n + 1);
+        kmer_offsets(offsets, n, g->k, ko.data(), "rb_graph_correct_mismatches");
+        for (int64_t i = 0; i < n; ++i)
             RB_REQUIRE(std::isfinite(cov_threshold[i]), "rb_graph_correct_mismatches: cov_threshold[%lld] is not finite", (long long)i);
-            ko[(size_t)i + 1] = ko[(size_t)i] + nk;
-        }
         const int64_t text = n ? offsets[n] - offsets[0] : 0;
         RB_REQUIRE(text == 0 || seq, "rb_graph_correct_mismatches: null sequence text");
         if (koffsets) std::copy(ko.begin(), ko.end(), koffsets);
@@ -327,21 +307,11 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
         QueryLease q(g);
         const FilterView fv = g->view(0, 0);
         hipStream_t s = q.c->st;
-        // with profiling on (rb_graph_profile_enable) the kernels of every piece are timed by events on the query stream: entry "mismatches"
-        const bool prof = g->prof_on;
-        rb::Event ev[2];
-        if (prof) { RB_HIP(hipEventCreate(&ev[0].e)); RB_HIP(hipEventCreate(&ev[1].e)); }
-        double prof_ms = 0;
-        int64_t prof_n = 0;
-        // pieces of <= 16 M k-mers, as rb_graph_kmers: 21 bytes of scratch a k-mer (two hashes, the count, the long sequences' code row),
-        // the text and the piece's batch
-        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)16 << 20;
+        // piece by piece (rb_pieces.hpp): 21 bytes of scratch a k-mer (two hashes, the count, the long sequences' code row), the text and the
+        // piece's batch; with profiling on the kernels of every piece are timed: entry "mismatches"
         std::vector<int64_t> tab;
-        for (int64_t ra = 0; ra < n;) {
-            int64_t lo = ra + 1, hi = n;
-            while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (ko[(size_t)mid] - ko[(size_t)ra] <= piece_max) lo = mid; else hi = mid - 1; }
-            const int64_t rb_ = lo, pn = rb_ - ra, pt = ko[(size_t)rb_] - ko[(size_t)ra], tb = offsets[rb_] - offsets[ra];
-            if (pt == 0) { ra = rb_; continue; }
+        for_each_host_piece(g, s, seq, offsets, ko.data(), n, "mismatches", [&](HostPiece &pc) {
+            const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt, tb = offsets[pc.rb] - offsets[ra];
             // the piece's table: k-mer offsets [pn + 1], text offsets [pn + 1], the sequences whose code row does not fit LDS
             tab.assign((size_t)(2 * pn + 2), 0);
             for (int64_t i = 0; i <= pn; ++i) {
@@ -351,13 +321,7 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
             for (int64_t i = 0; i < pn; ++i)
                 if (tab[(size_t)i + 1] - tab[(size_t)i] > MM_LDS_ROW) tab.push_back(i);
             const int64_t nlong = (int64_t)tab.size() - (2 * pn + 2);
-            rb::AsciiUpload up;
-            rb_batch *b = nullptr;
-            try {
-                rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
-                b = rb::ascii_batch_finish(up);
-            } catch (...) { rb::ascii_batch_abort(up); throw; }
-            rb::BatchPtr guard(b);
+            const rb_batch *b = pc.batch();
             // b3: counts [pt] floats, thresholds [pn], replacements [pn], text [tb], code rows of the long sequences [pt]
             const size_t o_thr = (size_t)pt * 4, o_nf = o_thr + (size_t)pn * 4, o_txt = o_nf + (size_t)pn * 4, o_row = up16(o_txt + (size_t)tb);
             q.c->b0.reserve(tab.size() * 8);
@@ -372,7 +336,7 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
             RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
             RB_HIP(hipMemcpyAsync(dthr, cov_threshold + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
             RB_HIP(hipMemcpyAsync(dtxt, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
-            if (prof) RB_HIP(hipEventRecord(ev[0], s));
+            pc.kernels_begin();
             rb::launch_get_kmers(g, b, dkof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, s);
             hipLaunchKernelGGL((k_mismatch<true>), dim3(blocks_for(pn, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov, pn,
                                (const int64_t *)nullptr, (int64_t)0, dkof, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(),
@@ -384,20 +348,11 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
                                    dthr, dnf, counts ? 1 : 0);
                 RB_HIP(hipGetLastError());
             }
-            if (prof) RB_HIP(hipEventRecord(ev[1], s));
+            pc.kernels_end();
             RB_HIP(hipMemcpyAsync(out_seq + offsets[ra], dtxt, (size_t)tb, hipMemcpyDeviceToHost, s));
             RB_HIP(hipMemcpyAsync(n_fixed + ra, dnf, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
             if (counts) RB_HIP(hipMemcpyAsync(counts + ko[(size_t)ra], dcnt, (size_t)pt * 4, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipStreamSynchronize(s));                    // (the table and the piece's batch are released next)
-            if (prof) { float ms = 0; RB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); prof_ms += ms; ++prof_n; }
-            ra = rb_;
-        }
-        if (prof && prof_n) {
-            std::lock_guard<std::mutex> lk(g->qm);          // (queries share the handle: the profile table is written under the context lock)
-            bool found = false;
-            for (auto &e : g->prof) if (!strcmp(e.name, "mismatches")) { e.ms += prof_ms; e.launches += prof_n; found = true; break; }
-            if (!found) g->prof.push_back({"mismatches", prof_ms, prof_n});
-        }
+        });
     });
 }
 }  // extern "C"

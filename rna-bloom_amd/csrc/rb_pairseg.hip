@@ -2,14 +2,10 @@
 // breakWithFragPairedKmers (R/util/GraphUtils.java:4184-4405) on the device.  k_pair_support probes the pair filter for every pair position
 // and leaves one support bit per position in device scratch; k_pair_segments walks those bits a sequence per lane and writes the segments.
 // Only the sequences go in and the segments (plus, on request, one support byte per k-mer) come out (DESIGN.md §5 "Paired-k-mer segments").
-#include <stdlib.h>
-#include <string.h>
-
 #include <algorithm>
 #include <vector>
 
-#include "rb_kernels.hpp"
-#include "rb_pipeline.hpp"
+#include "rb_pieces.hpp"
 
 using namespace rb;
 
@@ -180,17 +176,13 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
         RB_REQUIRE(!support || koffsets, "rb_graph_paired_kmer_segments: support needs koffsets");
         RB_REQUIRE(!segs || n_segs, "rb_graph_paired_kmer_segments: segs needs n_segs");
         RB_REQUIRE(n == 0 || seq || offsets[n] == offsets[0], "rb_graph_paired_kmer_segments: null sequence text");
-        const int64_t uk = g->k;
-        std::vector<int64_t> ko((size_t)n + 1, 0), so((size_t)n + 1, 0);
+        std::vector<int64_t> ko((size_t)n + 1), so((size_t)n + 1, 0);
+        kmer_offsets(offsets, n, g->k, ko.data(), "rb_graph_paired_kmer_segments");
         for (int64_t i = 0; i < n; ++i) {
-            const int64_t l = offsets[i + 1] - offsets[i], nk = l >= uk ? l - uk + 1 : 0;
-            RB_REQUIRE(l >= 0, "rb_graph_paired_kmer_segments: offsets[%lld] > offsets[%lld]", (long long)i, (long long)i + 1);
-            RB_REQUIRE(nk <= INT32_MAX, "rb_graph_paired_kmer_segments: sequence %lld has more k-mers than an int holds", (long long)i);
-            const int64_t rs = ranges ? ranges[2 * i] : 0, re = ranges ? ranges[2 * i + 1] : nk;
+            const int64_t nk = ko[(size_t)i + 1] - ko[(size_t)i], rs = ranges ? ranges[2 * i] : 0, re = ranges ? ranges[2 * i + 1] : nk;
             RB_REQUIRE(rs >= 0 && rs <= re && re <= nk, "rb_graph_paired_kmer_segments: range [%lld, %lld) of sequence %lld is outside [0, %lld]",
                        (long long)rs, (long long)re, (long long)i, (long long)nk);
             const int64_t span = re - 1 - d - rs;              // lastIndex - rangeStart
-            ko[(size_t)i + 1] = ko[(size_t)i] + nk;
             so[(size_t)i + 1] = so[(size_t)i] + (span >= 0 ? span / (d + 1) + 1 : 0);
         }
         std::copy(so.begin(), so.end(), seg_offsets);
@@ -206,20 +198,11 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
         const BitFilter *f = bit_filter(g, which);
         RB_REQUIRE(f->bits, "rb_graph_paired_kmer_segments: the pair filter is gone");
         hipStream_t s = q.c->st;
-        // with profiling on (rb_graph_profile_enable) the two kernels of every piece are timed by events on the query stream: entry "pair_segments"
-        const bool prof = g->prof_on;
-        rb::Event ev[2];
-        if (prof) { RB_HIP(hipEventCreate(&ev[0].e)); RB_HIP(hipEventCreate(&ev[1].e)); }
-        double prof_ms = 0;
-        int64_t prof_n = 0;
-        // pieces of <= 16 M k-mers, as rb_graph_kmers: the piece's batch (≈ 0.3 B a base) and 1 bit a position are all the scratch there is
-        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)16 << 20;
+        // piece by piece (rb_pieces.hpp): the piece's batch (≈ 0.3 B a base) and 1 bit a position are all the scratch there is; with profiling
+        // on the two kernels of every piece are timed: entry "pair_segments"
         std::vector<int64_t> tab;
-        for (int64_t ra = 0; ra < n;) {
-            int64_t lo = ra + 1, hi = n;
-            while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (ko[(size_t)mid] - ko[(size_t)ra] <= piece_max) lo = mid; else hi = mid - 1; }
-            const int64_t rb_ = lo, pn = rb_ - ra, pt = ko[(size_t)rb_] - ko[(size_t)ra];
-            if (pt == 0) { ra = rb_; continue; }
+        for_each_host_piece(g, s, seq, offsets, ko.data(), n, "pair_segments", [&](HostPiece &pc) {
+            const int64_t ra = pc.ra, rb_ = pc.rb, pn = pc.pn, pt = pc.pt;
             // the piece's table: k-mer offsets [pn + 1], support-word offsets [pn + 1], segment slots [pn + 1], ranges [2 pn]
             tab.assign((size_t)(5 * pn + 3), 0);
             int64_t *kof = tab.data(), *swo = kof + pn + 1, *cap = swo + pn + 1, *rng = cap + pn + 1;
@@ -234,16 +217,9 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
             const int64_t nw = swo[pn], nc = cap[pn];
             if (nw == 0 || (nc == 0 && !support)) {           // nothing to probe: no segment, every support byte 0
                 if (support) std::fill(support + ko[(size_t)ra], support + ko[(size_t)rb_], (uint8_t)0);
-                ra = rb_;
-                continue;
+                return;
             }
-            rb::AsciiUpload up;
-            rb_batch *b = nullptr;
-            try {
-                rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
-                b = rb::ascii_batch_finish(up);
-            } catch (...) { rb::ascii_batch_abort(up); throw; }
-            rb::BatchPtr guard(b);
+            const rb_batch *b = pc.batch();
             q.c->b0.reserve(tab.size() * 8);
             q.c->b1.reserve((size_t)nw * 8);
             q.c->b2.reserve((size_t)nc * 8 + (size_t)pn * 4 + 4);
@@ -255,7 +231,7 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
             RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
             RB_HIP(hipMemsetAsync(dover, 0, 4, s));
             if (support) RB_HIP(hipMemsetAsync(q.c->b3.p, 0, (size_t)pt, s));
-            if (prof) RB_HIP(hipEventRecord(ev[0], s));
+            pc.kernels_begin();
             hipLaunchKernelGGL(k_pair_support, dim3(blocks_for(nw, PS_TPB)), dim3(PS_TPB), 0, s, (const uint32_t *)f->bits, f->mod, f->num_hash,
                                kmul_of(g->k), (int)g->stranded, g->k, d, b->codes, b->valid, b->rnz, b->woff, dkof, dswo, drng, pn, nw,
                                q.c->b1.as<uint64_t>(), support ? q.c->b3.as<uint8_t>() : nullptr);
@@ -265,28 +241,20 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
                                    d, num_pairs_required, dsegs, dn, dover);
                 RB_HIP(hipGetLastError());
             }
-            if (prof) RB_HIP(hipEventRecord(ev[1], s));
+            pc.kernels_end();
             if (nc) {
                 RB_HIP(hipMemcpyAsync(segs + 2 * so[(size_t)ra], dsegs, (size_t)nc * 8, hipMemcpyDeviceToHost, s));
                 RB_HIP(hipMemcpyAsync(n_segs + ra, dn, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
                 RB_HIP(hipMemcpyAsync(&over, dover, 4, hipMemcpyDeviceToHost, s));
             }
             if (support) RB_HIP(hipMemcpyAsync(support + ko[(size_t)ra], q.c->b3.p, (size_t)pt, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipStreamSynchronize(s));                    // (the table and the piece's batch are released next)
+            pc.finish();                                        // (`over` is on the host)
             if (over) {
                 set_error("rb_graph_paired_kmer_segments: %d sequences of reads [%lld, %lld) have more segments than their slots (internal error)",
                           over, (long long)ra, (long long)rb_);
                 throw HipError{RB_ERR_STATE};
             }
-            if (prof) { float ms = 0; RB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1])); prof_ms += ms; ++prof_n; }
-            ra = rb_;
-        }
-        if (prof && prof_n) {
-            std::lock_guard<std::mutex> lk(g->qm);          // (queries share the handle: the profile table is written under the context lock)
-            bool found = false;
-            for (auto &e : g->prof) if (!strcmp(e.name, "pair_segments")) { e.ms += prof_ms; e.launches += prof_n; found = true; break; }
-            if (!found) g->prof.push_back({"pair_segments", prof_ms, prof_n});
-        }
+        });
     });
 }
 }  // extern "C"

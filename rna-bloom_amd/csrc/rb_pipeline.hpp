@@ -496,14 +496,14 @@ struct rb_graph {
         prof_pending.push_back({name, prof_open[w], e1});
         prof_open[w] = nullptr;
     }
+    void prof_add(const char *name, double ms, int64_t launches) {   // (a query call: under qm)
+        for (auto &e : prof) if (!strcmp(e.name, name)) { e.ms += ms; e.launches += launches; return; }
+        prof.push_back({name, ms, launches});
+    }
     void prof_collect() {   // call with both streams idle
         for (auto &pp : prof_pending) {
             float ms = 0;
-            if (hipEventElapsedTime(&ms, pp.e0, pp.e1) == hipSuccess) {
-                bool found = false;
-                for (auto &e : prof) if (!strcmp(e.name, pp.name)) { e.ms += ms; e.launches++; found = true; break; }
-                if (!found) prof.push_back({pp.name, ms, 1});
-            }
+            if (hipEventElapsedTime(&ms, pp.e0, pp.e1) == hipSuccess) prof_add(pp.name, ms, 1);
             prof_pool.push_back(pp.e0); prof_pool.push_back(pp.e1);
         }
         prof_pending.clear();

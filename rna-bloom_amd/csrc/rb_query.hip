@@ -20,7 +20,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
-#include "rb_pipeline.hpp"
+#include "rb_pieces.hpp"
 
 using namespace rb;
 
@@ -790,11 +790,7 @@ int rb_graph_kmers(rb_graph *g, const char *seq, const int64_t *offsets, int64_t
                    uint64_t *f, uint64_t *r, float *count) {
     return guarded([&] {
         RB_REQUIRE(g && offsets && koffsets && n_reads >= 0, "rb_graph_kmers: null argument");
-        koffsets[0] = 0;
-        for (int64_t i = 0; i < n_reads; ++i) {
-            int64_t l = offsets[i + 1] - offsets[i];
-            koffsets[i + 1] = koffsets[i] + (l >= g->k ? l - g->k + 1 : 0);
-        }
+        rb::kmer_offsets(offsets, n_reads, g->k, koffsets, nullptr);      // (unchecked, as ever: a piece's upload refuses a negative length)
         const int64_t total = koffsets[n_reads];
         if (!f || !count || total == 0) return;
         RB_HIP(hipSetDevice(g->p.device));
@@ -802,44 +798,31 @@ int rb_graph_kmers(rb_graph *g, const char *seq, const int64_t *offsets, int64_t
                 pin_c(count, (size_t)total * 4);
         QueryLease q(g);
         hipStream_t s = q.c->st;
-        // in pieces of <= 16 M k-mers (20 bytes of device scratch each): the scratch stays at 320 MB however many reads are asked for
-        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)16 << 20;
+        // piece by piece (rb_pieces.hpp; 20 bytes of device scratch a k-mer): the scratch stays at 320 MB however many reads are asked for
         std::vector<int64_t> rel;
-        for (int64_t ra = 0; ra < n_reads;) {
-            int64_t lo = ra + 1, hi = n_reads;
-            while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (koffsets[mid] - koffsets[ra] <= piece_max) lo = mid; else hi = mid - 1; }
-            const int64_t rb_ = lo, pn = rb_ - ra, pt = koffsets[rb_] - koffsets[ra];
-            if (pt > 0) {
-                rb::AsciiUpload up;
-                rb_batch *b = nullptr;
-                try {
-                    rb::ascii_batch_begin(up, g->p.device, seq, nullptr, offsets, ra, pn, 0, s, true);
-                    b = rb::ascii_batch_finish(up);
-                } catch (...) { rb::ascii_batch_abort(up); throw; }
-                rb::BatchPtr guard(b);
-                rel.resize((size_t)pn + 1);
-                for (int64_t i = 0; i <= pn; ++i) rel[(size_t)i] = koffsets[ra + i] - koffsets[ra];
-                q.c->b0.reserve(((size_t)pn + 1) * 8); q.c->b1.reserve((size_t)pt * 8); q.c->b2.reserve((size_t)pt * 8); q.c->b3.reserve((size_t)pt * 4);
-                RB_HIP(hipMemcpyAsync(q.c->b0.p, rel.data(), ((size_t)pn + 1) * 8, hipMemcpyHostToDevice, s));
-                // on a shard of a distributed graph only the hashes are local (count = 1 for a usable window): the caller gets the
-                // counts with one rb_shard_query_* exchange (rnabloom/sharded.py::ShardRank.getKmers)
-                if (g->shard)
-                    hipLaunchKernelGGL(k_get_kmers<true>, dim3(blocks_for(b->n_words)), dim3(TPB), 0, s, g->view(0, 0), (int)g->stranded,
-                                       b->codes, b->valid, b->rnz, b->word_read, b->woff, b->len, b->n_words, g->k, q.c->b0.as<int64_t>(),
-                                       q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), q.c->b3.as<float>());
-                else
-                    hipLaunchKernelGGL(k_get_kmers<false>, dim3(blocks_for(b->n_words)), dim3(TPB), 0, s, g->view(0, 0), (int)g->stranded,
-                                       b->codes, b->valid, b->rnz, b->word_read, b->woff, b->len, b->n_words, g->k, q.c->b0.as<int64_t>(),
-                                       q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), q.c->b3.as<float>());
-                RB_HIP(hipGetLastError());
-                const int64_t o = koffsets[ra];
-                RB_HIP(hipMemcpyAsync(f + o, q.c->b1.p, (size_t)pt * 8, hipMemcpyDeviceToHost, s));
-                if (r) RB_HIP(hipMemcpyAsync(r + o, q.c->b2.p, (size_t)pt * 8, hipMemcpyDeviceToHost, s));
-                RB_HIP(hipMemcpyAsync(count + o, q.c->b3.p, (size_t)pt * 4, hipMemcpyDeviceToHost, s));
-                RB_HIP(hipStreamSynchronize(s));                  // (rel and the piece's batch are released next)
-            }
-            ra = rb_;
-        }
+        rb::for_each_host_piece(g, s, seq, offsets, koffsets, n_reads, nullptr, [&](rb::HostPiece &pc) {
+            const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
+            const rb_batch *b = pc.batch();
+            rel.resize((size_t)pn + 1);
+            for (int64_t i = 0; i <= pn; ++i) rel[(size_t)i] = koffsets[ra + i] - koffsets[ra];
+            q.c->b0.reserve(((size_t)pn + 1) * 8); q.c->b1.reserve((size_t)pt * 8); q.c->b2.reserve((size_t)pt * 8); q.c->b3.reserve((size_t)pt * 4);
+            RB_HIP(hipMemcpyAsync(q.c->b0.p, rel.data(), ((size_t)pn + 1) * 8, hipMemcpyHostToDevice, s));
+            // on a shard of a distributed graph only the hashes are local (count = 1 for a usable window): the caller gets the
+            // counts with one rb_shard_query_* exchange (rnabloom/sharded.py::ShardRank.getKmers)
+            if (g->shard)
+                hipLaunchKernelGGL(k_get_kmers<true>, dim3(blocks_for(b->n_words)), dim3(TPB), 0, s, g->view(0, 0), (int)g->stranded,
+                                   b->codes, b->valid, b->rnz, b->word_read, b->woff, b->len, b->n_words, g->k, q.c->b0.as<int64_t>(),
+                                   q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), q.c->b3.as<float>());
+            else
+                hipLaunchKernelGGL(k_get_kmers<false>, dim3(blocks_for(b->n_words)), dim3(TPB), 0, s, g->view(0, 0), (int)g->stranded,
+                                   b->codes, b->valid, b->rnz, b->word_read, b->woff, b->len, b->n_words, g->k, q.c->b0.as<int64_t>(),
+                                   q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), q.c->b3.as<float>());
+            RB_HIP(hipGetLastError());
+            const int64_t o = koffsets[ra];
+            RB_HIP(hipMemcpyAsync(f + o, q.c->b1.p, (size_t)pt * 8, hipMemcpyDeviceToHost, s));
+            if (r) RB_HIP(hipMemcpyAsync(r + o, q.c->b2.p, (size_t)pt * 8, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(count + o, q.c->b3.p, (size_t)pt * 4, hipMemcpyDeviceToHost, s));
+        });
     });
 }
 
@@ -882,16 +865,10 @@ int rb_graph_batch_counts(rb_graph *g, const rb_batch *b, int64_t first, int64_t
         }
         // To the host in pieces of <= 64 M counts through two device buffers: the copy of piece c runs on its own stream beside
         // the kernel of piece c + 1, and the scratch stays at 512 MB however many reads are asked for.
-        const int64_t piece_max = getenv("RB_QUERY_PIECE") ? std::max<int64_t>(1, atoll(getenv("RB_QUERY_PIECE"))) : (int64_t)64 << 20;
-        std::vector<int64_t> cut{0};                              // read boundaries of the pieces (at least one read each)
         auto row_of = [&](int64_t i) { return koffsets ? koffsets[i] : i * stride; };
+        const std::vector<int64_t> cut = rb::piece_cuts(row_of, n, rb::query_piece_max((int64_t)64 << 20));     // (at least one read each)
         int64_t largest = 0;
-        while (cut.back() < n) {
-            int64_t a = cut.back(), lo = a + 1, hi = n;
-            while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (row_of(mid) - row_of(a) <= piece_max) lo = mid; else hi = mid - 1; }
-            cut.push_back(lo);
-            largest = std::max(largest, row_of(lo) - row_of(a));
-        }
+        for (size_t c = 0; c + 1 < cut.size(); ++c) largest = std::max(largest, row_of(cut[c + 1]) - row_of(cut[c]));
         q.c->b3.reserve((size_t)largest * 4 * 2);
         float *buf[2] = {q.c->b3.as<float>(), q.c->b3.as<float>() + largest};
         rb::Stream s2;

@@ -1,6 +1,6 @@
 // rb_sketch.hip — minimizer and strobemer extraction over long reads (BASELINE config 5).
 // Hash-only work: one read is independent of every other, so multi-GPU = replicas over read shards.
-#include "rb_pipeline.hpp"
+#include "rb_pieces.hpp"
 
 using namespace rb;
 
@@ -540,19 +540,11 @@ void launch_minimizers(const uint64_t *d_h, const int64_t *d_koff, const int64_t
 // all-window hashes of a set of reads; returns device buffer h (caller releases) and host koff
 void hash_all(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int mode, std::vector<int64_t> &koff,
               DevBuf &d_koff, DevBuf &d_h) {
-    koff.assign((size_t)n_reads + 1, 0);
-    for (int64_t i = 0; i < n_reads; ++i) {
-        int64_t l = offsets[i + 1] - offsets[i];
-        koff[(size_t)i + 1] = koff[(size_t)i] + (l >= k ? l - k + 1 : 0);
-    }
+    koff.resize((size_t)n_reads + 1);
+    rb::kmer_offsets(offsets, n_reads, k, koff.data(), nullptr);      // (unchecked, as ever: the upload below refuses a negative length)
     const int64_t total = koff[(size_t)n_reads];
     if (!total) return;
-    rb::BatchPtr b;
-    {
-        rb::AsciiUpload up;
-        try { rb::ascii_batch_begin(up, device, seq, nullptr, offsets, 0, n_reads, 0, nullptr, true); b.reset(rb::ascii_batch_finish(up)); }
-        catch (...) { rb::ascii_batch_abort(up); throw; }
-    }
+    const rb::BatchPtr b = rb::upload_text_batch(device, seq, offsets, 0, n_reads, nullptr);
     d_koff.reserve(((size_t)n_reads + 1) * 8);
     d_h.reserve((size_t)total * 8);
     RB_HIP(hipMemcpy(d_koff.p, koff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice));
