@@ -295,6 +295,69 @@ int rb_graph_paired_kmer_segments(rb_graph *g, int which, const char *seq, const
  * without koffsets; k < 2 (the reference's median of k - 1 counts does not exist). */
 int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, float min_kmer_cov,
                                 char *out_seq, int32_t *n_fixed, int64_t *koffsets, float *counts);
+/* Error correction of host sequences — GraphUtils.correctErrorHelper (R/util/GraphUtils.java:3711-3912), what correctErrorsSE (:3998-4049) and
+ * correctErrorsPE (:4051-4182) run on every read that passed the coverage screen: every run of k-mers below the threshold (a gap) is repaired,
+ * then correctMismatches (:3904) runs on the repaired list.  All of it happens on the device; gaps do not depend on each other (after a gap the
+ * reference appends the ORIGINAL good k-mer behind it, :3850, which is the next gap's left anchor, :3820), so all gaps of a call are resolved at once.
+ *   Input: sequence i is seq[offsets[i], offsets[i+1]) with T = cov_threshold[i]; its k-mer list is getKmers(String)'s, as rb_graph_kmers gives it
+ *   (nk = max(0, len - k + 1); count 0 for a window with a letter outside ACGTU).
+ *   Gap scan (:3730-3855): a k-mer is bad if count < T.  A run of nb bad k-mers [g, g + nb) that ends at a good k-mer is a gap; a run still open at
+ *   the end is the right edge (:3857-3902) if nb < nk.  A sequence that is bad throughout, has no k-mer, or has T <= 0 has no gap.
+ *   Left edge (g = 0, :3736-3781): Kmer.getLeftVariants(k, numHash, graph, min_kmer_cov) (R/graph/Kmer.java:361, CanonicalKmer.java:387) of the LAST
+ *   bad k-mer.  None -> kept.  Else nb < lookahead -> trimmed.  Else tipMed = Common.getMedian of the tip's counts (float32; an even number gives
+ *   (a + b) / 2f) and ext = greedyExtendLeft(graph, kmers[nb], lookahead, nb) (:1906-1921): if ext has nb k-mers and its median count > tipMed then
+ *   getPercentIdentity(assemble(ext), assemble(tip)) >= percent_identity -> replaced by ext; else !kmers[0].hasPredecessors && nb < k -> trimmed (a
+ *   blunt end); else kept.  Otherwise kept.  Right edge: the mirror image — getRightVariants of the FIRST bad k-mer, greedyExtendRight from the good
+ *   k-mer before it, hasSuccessors of the last k-mer.
+ *   getPercentIdentity (R/util/SeqUtils.java:164-175) is (max(|a|, |b|) - d) / max(|a|, |b|) in float32 with d = getDistance (:190-229): the
+ *   Levenshtein rows, except that the reference's row copy leaves out the last column, so d = min(D[|a|][|b|-1] + 1, |b| + 1,
+ *   D[|a|-1][|b|-1] + (a's last letter != b's last letter)) for the true matrix D — reproduced.  No length limit.
+ *   SNV bubble (nb == k, :3782-3818): for n in A C G T the counts of getKmers(kmers[g] + n + kmers[g+k-1]) — 2k + 1 letters, k + 2 windows.  A
+ *   candidate wins if its minimum >= min_kmer_cov and its median > best; best starts at Float.MIN_VALUE (the smallest positive float); the winner
+ *   needs best >= min_kmer_cov, and its k + 2 k-mers stand for the k bad ones: the sequence grows by two letters (reproduced, not fixed).
+ *   Path (every other interior gap, :3819-3845): getMaxCoveragePath(graph, kmers[g-1], kmers[g+nb], nb + max_indel_size, lookahead, min_kmer_cov)
+ *   (:1591-1675, with the meeting rule and SeqUtils.isLowComplexityShort :499-543).  A path of len k-mers is accepted if nb - max_indel_size <= len
+ *   <= nb + max_indel_size and (len <= k + max_indel_size or getPercentIdentity(assemble(path), assemble(kmers, g, g + nb)) >= percent_identity).
+ *   Then correctMismatches(kmers2, graph, T, min_kmer_cov) as rb_graph_correct_mismatches runs it, on the string kmers2 spells.
+ *   Letters outside ACGTU follow the existing primitives: such windows count 0; variants and neighbours are hashed as rb_graph_neighbors hashes
+ *   them (directions 2 / 3 and 0 / 1, SeqUtils.getAltNucleotides(byte) :130-145 choosing the alternatives); a walk from a seed with such a letter
+ *   ends with reason 4 (no path, the gap is kept) — the seeds here are good k-mers, which have none.  k-mers compare as the walk kernels compare
+ *   them (upper / lower case alike, U as T), and letters taken from a walk's k-mers come out as upper-case A C G T.
+ *   Output: out_offsets (host, n + 1) is a capacity layout from the lengths and max_indel_size alone: cap_i = len_i + floor((nk_i - 1) / 2) *
+ *   max_indel_size + 2 * floor((nk_i - 1) / (k + 1)) for nk_i >= 1, else len_i.  (An edge gap never grows.  Every interior gap has a good k-mer
+ *   before the first and behind each: p path gaps and s SNV gaps need 1 + 2p + (k + 1)s <= nk k-mers, a path gap grows by at most
+ *   max_indel_size, :3830-3832, an SNV gap by exactly 2; p <= (nk-1)/2 and s <= (nk-1)/(k+1) separately.)  out_seq[out_offsets[i] ..] holds the
+ *   string the reference's kmers2 spells after correctMismatches, out_len[i] its length.  flags[i]: RB_CORR_GAP a gap was replaced or trimmed,
+ *   RB_CORR_MISMATCH the mismatch pass replaced a base, RB_CORR_CORRECTED either (the reference returns non-null); with no bit set the sequence
+ *   comes back as it went in.  out_seq == NULL: a size query — out_offsets (and gap_offsets, if given: the capacity layout (nk_i + 1) / 2 per
+ *   sequence, whose last entry bounds the number of records) are filled and nothing is launched.
+ *   gaps (optional, requires gap_offsets): one record per gap, densely: those of sequence i are gaps[gap_offsets[i] .. gap_offsets[i+1]) in scan
+ *   order; `gaps` needs room for the size query's gap_offsets[n] records.  repl_len: the k-mers that stand for the run (kept: run, trimmed: 0).
+ * The call works in pieces (RB_QUERY_PIECE input k-mers, as rb_graph_kmers; by default 16 M / (1 + (max_indel_size + 1) / 2), so that a piece has
+ * about 16 M CAPACITY k-mers); results do not depend on the cuts.  Device scratch of a piece: 40 bytes per capacity k-mer (cap_i - k + 1 per
+ * sequence: two hashes, count, code row, text and bits of the stitched text) + 5 bytes per input letter + 60 bytes per gap + at most 256 MB for
+ * the walks that run together (one walk alone may need more: 42 bytes per step of its bound) — bounded by the piece and one sequence, not
+ * by the call.  It leases a query context (re-entrant on one handle).  With rb_graph_profile_enable on, the profile entry "correct_errors"
+ * gets the time from the first to the last kernel of each piece — the host's work at the piece's two intermediate synchronisations (prefix
+ * sums of the gap counts, sorting the gap records into lists) included, so it is an interval on the stream, not pure device time; the
+ * kernels alone are in the per-phase entries "correct_errors.profile" / ".scan" / ".walks" / ".resolve" / ".stitch" / ".mismatch".
+ * RB_ERR_STATE: a sequence outgrew its slot (an internal error; nothing is truncated silently).
+ * Refused (RB_ERR_INVALID, nothing launched): null handle / offsets / cov_threshold / p / out_offsets, out_seq without out_len or flags, seq
+ * where there is text; a shard handle; a destroyed dbgbf or counting filter; a threshold, percent_identity or min_kmer_cov that is not finite;
+ * lookahead outside 1..16 (the greedy kernel's limit); max_indel_size outside 0..4096; decreasing offsets; gaps without gap_offsets; k < 2. */
+enum { RB_GAP_LEFT_EDGE = 0, RB_GAP_RIGHT_EDGE = 1, RB_GAP_SNV = 2, RB_GAP_PATH = 3 };      /* rb_corr_gap.kind */
+enum { RB_GAP_KEPT = 0, RB_GAP_REPLACED = 1, RB_GAP_TRIMMED = 2 };                          /* rb_corr_gap.outcome */
+#define RB_CORR_CORRECTED 1u
+#define RB_CORR_GAP 2u
+#define RB_CORR_MISMATCH 4u
+typedef struct rb_corr_params { int32_t lookahead, max_indel_size; float percent_identity, min_kmer_cov; } rb_corr_params;
+typedef struct rb_corr_gap {            /* 20 bytes */
+    int32_t seq, first, run;            /* sequence, first bad k-mer, number of bad k-mers */
+    int32_t repl_len;
+    uint8_t kind, outcome, pad[2];
+} rb_corr_gap;
+int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, const rb_corr_params *p,
+                            int64_t *out_offsets, char *out_seq, int32_t *out_len, uint32_t *flags, rb_corr_gap *gaps, int64_t *gap_offsets);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

@@ -452,6 +452,34 @@ public class BloomFilterDeBruijnGraph {
         return res;
     }
 
+    /**
+     * GraphUtils.correctErrorHelper (src/rnabloom/util/GraphUtils.java:3711-3912) for a batch of sequences in ONE native call: the gap scan, the
+     * three repair rules and correctMismatches run on the device.  covThresholds[i] is sequence i's covThreshold.  Returns, per sequence, the
+     * string the reference's returned k-mers spell, or null where the reference returns null (nothing was corrected).
+     */
+    public String[] correctErrors(String[] seqs, float[] covThresholds, int lookahead, int maxIndelSize, float percentIdentity, float minKmerCov) {
+        final int n = seqs.length;
+        final long[] off = new long[n + 1], outOff = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("correctErrors: more than 2 GB of text in one batch");
+        final int total = (int) off[n];
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max(total, 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        // (the native throws IllegalArgumentException when the capacity layout outgrows an int)
+        final int cap = NativeGraph.correctErrors(handle, text, off, n, covThresholds, lookahead, maxIndelSize, percentIdentity, minKmerCov, outOff, null,
+                                                  null, null, null, null);
+        final ByteBuffer out = ByteBuffer.allocateDirect(Math.max(cap, 1));
+        final int[] len = new int[n], flags = new int[n];
+        NativeGraph.correctErrors(handle, text, off, n, covThresholds, lookahead, maxIndelSize, percentIdentity, minKmerCov, outOff, out, len, flags, null,
+                                  null);
+        final byte[] b = new byte[cap];
+        out.get(b, 0, cap);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = (flags[i] & 1) != 0 ? new String(b, (int) outOff[i], len[i], java.nio.charset.StandardCharsets.ISO_8859_1) : null;
+        return res;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

@@ -106,6 +106,17 @@ public final class NativeGraph {
      *  koffsets[i] + p) return the final count profile — getKmers of the corrected sequences. */
     public static native void correctMismatches(long h, ByteBuffer seq, long[] offsets, int n, float[] covThreshold, float minKmerCov,
                                                 ByteBuffer outSeq, int[] nFixed, long[] koffsets, float[] counts);
+    /** Error correction of n sequences (rb_graph_correct_errors; GraphUtils.correctErrorHelper, R/util/GraphUtils.java:3711-3912): gap repair
+     *  and the mismatch pass on the device.  outOffsets[n + 1] is filled from the lengths and maxIndelSize alone; outSeq == null sizes the
+     *  outputs only (gapOffsets, if given, then holds the capacity layout of the gap records).  Else corrected sequence i is outLen[i] bytes at
+     *  outSeq + outOffsets[i], flags[i] has bit 0 corrected (the reference returns non-null), bit 1 a gap was replaced or trimmed, bit 2 the
+     *  mismatch pass replaced a base.  gaps (optional, with gapOffsets[n + 1]): 5 ints per gap — sequence, first bad k-mer, run length,
+     *  replacement length, kind | outcome << 8 (kind 0 left edge, 1 right edge, 2 SNV, 3 path; outcome 0 kept, 1 replaced, 2 trimmed) —
+     *  those of sequence i at gaps[5 * gapOffsets[i]] .. gaps[5 * gapOffsets[i + 1]).  Returns outOffsets[n]; IllegalArgumentException
+     *  when that is more than an int holds (cut the batch). */
+    public static native int correctErrors(long h, ByteBuffer seq, long[] offsets, int n, float[] covThreshold, int lookahead, int maxIndelSize,
+                                           float percentIdentity, float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] outLen, int[] flags,
+                                           int[] gaps, long[] gapOffsets);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

@@ -380,6 +380,25 @@ void FN(correctMismatches)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray
     lr(e, offsets, off, JNI_ABORT); fr(e, covThreshold, thr, JNI_ABORT); ir(e, nFixed, nf, 0); lr(e, koffsets, ko, 0); fr(e, counts, pc, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_correct_errors: a gap record (rb_corr_gap, 20 bytes, little endian) is 5 ints to Java: seq, first, run, repl_len, kind | outcome << 8 */
+jint FN(correctErrors)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jfloatArray covThreshold, jint lookahead, jint maxIndelSize,
+                       jfloat percentIdentity, jfloat minKmerCov, jlongArray outOffsets, jobject outSeq, jintArray outLen, jintArray flags, jintArray gaps,
+                       jlongArray gapOffsets) {
+    jlong *off = la(e, offsets), *oo = la(e, outOffsets), *go = la(e, gapOffsets);
+    jfloat *thr = fa(e, covThreshold);
+    jint *ol = ia(e, outLen), *fl = ia(e, flags), *gp = ia(e, gaps);
+    rb_corr_params p;
+    (void)c;
+    p.lookahead = lookahead; p.max_indel_size = maxIndelSize; p.percent_identity = percentIdentity; p.min_kmer_cov = minKmerCov;
+    int rc = rb_graph_correct_errors(G(h), (const char *)direct(e, seq), (const int64_t *)off, n, thr, &p, (int64_t *)oo, outSeq ? (char *)direct(e, outSeq) : 0,
+                                     (int32_t *)ol, (uint32_t *)fl, (rb_corr_gap *)gp, (int64_t *)go);
+    if (rc == 0 && oo && n >= 0 && oo[n] > 0x7fffffffLL) rc = RB_ERR_INVALID;      /* the capacity layout does not fit the int this returns: smaller batches */
+    const jint cap = rc == 0 && oo && n >= 0 ? (jint)oo[n] : 0;
+    lr(e, offsets, off, JNI_ABORT); fr(e, covThreshold, thr, JNI_ABORT); lr(e, outOffsets, oo, 0); ir(e, outLen, ol, 0); ir(e, flags, fl, 0);
+    ir(e, gaps, gp, 0); lr(e, gapOffsets, go, 0);
+    if (rc) throw_rc(e, rc);
+    return cap;
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -178,7 +178,7 @@ __device__ __forceinline__ float mm_median(const uint32_t (&c)[MM_SLOTS], int n)
 template <bool LDS_ROW>
 __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded, int k, float min_cov, int64_t pn, const int64_t *__restrict__ ids,
                                                      int64_t n_ids, const int64_t *__restrict__ kof, const int64_t *__restrict__ tof,
-                                                     const uint32_t *__restrict__ woff, uint32_t *valid, uint8_t *txt, uint64_t *F, uint64_t *R, float *cnt,
+                                                     const int32_t *__restrict__ nks, const uint32_t *__restrict__ woff, uint32_t *valid, uint8_t *txt, uint64_t *F, uint64_t *R, float *cnt,
                                                      uint8_t *grow, const float *__restrict__ thr, int32_t *__restrict__ n_fixed, int write_counts) {
     __shared__ uint8_t s_row[MM_WAVES][LDS_ROW ? MM_LDS_ROW : 4];
     __shared__ uint32_t s_vc[MM_WAVES][RB_MAX_K];
@@ -188,8 +188,8 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
     if constexpr (LDS_ROW) { if (slot >= pn) return; r = slot; }
     else { if (slot >= n_ids) return; r = ids[slot]; }
     const int64_t k0 = kof[r];
-    const int32_t nk = (int32_t)(kof[r + 1] - k0);
-    if (LDS_ROW && nk > MM_LDS_ROW) return;
+    const int32_t nk = nks ? nks[r] : (int32_t)(kof[r + 1] - k0);
+    if (LDS_ROW ? nk > MM_LDS_ROW : nk <= MM_LDS_ROW) return;     // (ids may list a sequence by its capacity: the row of a short one is the other instantiation's)
     const float T = thr[r];
     if (nk <= k + 1 || !(T > 0.0f)) {                    // neither loop of the reference has a position / no count is below T
         if (lane == 0) n_fixed[r] = 0;
@@ -278,6 +278,21 @@ inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
 
+int rb::mismatch_lds_row() { return MM_LDS_ROW; }
+void rb::launch_mismatch(rb_graph *g, float min_kmer_cov, int64_t pn, const int64_t *ids, int64_t n_ids, const int64_t *kof, const int32_t *nks,
+                         const int64_t *tof, const uint32_t *woff, uint32_t *valid, uint8_t *txt, uint64_t *F, uint64_t *R, float *cnt, uint8_t *grow,
+                         const float *thr, int32_t *n_fixed, int write_counts, hipStream_t s) {
+    const FilterView fv = g->view(0, 0);
+    hipLaunchKernelGGL((k_mismatch<true>), dim3(blocks_for(pn, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov, pn,
+                       (const int64_t *)nullptr, (int64_t)0, kof, tof, nks, woff, valid, txt, F, R, cnt, grow, thr, n_fixed, write_counts);
+    RB_HIP(hipGetLastError());
+    if (n_ids) {
+        hipLaunchKernelGGL((k_mismatch<false>), dim3(blocks_for(n_ids, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov, pn, ids,
+                           n_ids, kof, tof, nks, woff, valid, txt, F, R, cnt, grow, thr, n_fixed, write_counts);
+        RB_HIP(hipGetLastError());
+    }
+}
+
 extern "C" {
 int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, float min_kmer_cov,
                                 char *out_seq, int32_t *n_fixed, int64_t *koffsets, float *counts) {
@@ -305,7 +320,6 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
         HostPin pin_seq(seq + offsets[0], (size_t)text), pin_out(out_seq + offsets[0], (size_t)text), pin_thr(cov_threshold, (size_t)n * 4),
                 pin_nf(n_fixed, (size_t)n * 4), pin_cnt(counts, counts ? (size_t)total * 4 : 0);
         QueryLease q(g);
-        const FilterView fv = g->view(0, 0);
         hipStream_t s = q.c->st;
         // piece by piece (rb_pieces.hpp): 21 bytes of scratch a k-mer (two hashes, the count, the long sequences' code row), the text and the
         // piece's batch; with profiling on the kernels of every piece are timed: entry "mismatches"
@@ -338,16 +352,8 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
             RB_HIP(hipMemcpyAsync(dtxt, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
             pc.kernels_begin();
             rb::launch_get_kmers(g, b, dkof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, s);
-            hipLaunchKernelGGL((k_mismatch<true>), dim3(blocks_for(pn, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov, pn,
-                               (const int64_t *)nullptr, (int64_t)0, dkof, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(),
-                               dcnt, drow, dthr, dnf, counts ? 1 : 0);
-            RB_HIP(hipGetLastError());
-            if (nlong) {
-                hipLaunchKernelGGL((k_mismatch<false>), dim3(blocks_for(nlong, MM_WAVES)), dim3(MM_TPB), 0, s, fv, (int)g->stranded, g->k, min_kmer_cov,
-                                   pn, dids, nlong, dkof, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, drow,
-                                   dthr, dnf, counts ? 1 : 0);
-                RB_HIP(hipGetLastError());
-            }
+            rb::launch_mismatch(g, min_kmer_cov, pn, dids, nlong, dkof, nullptr, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(),
+                                dcnt, drow, dthr, dnf, counts ? 1 : 0, s);
             pc.kernels_end();
             RB_HIP(hipMemcpyAsync(out_seq + offsets[ra], dtxt, (size_t)tb, hipMemcpyDeviceToHost, s));
             RB_HIP(hipMemcpyAsync(n_fixed + ra, dnf, (size_t)pn * 4, hipMemcpyDeviceToHost, s));

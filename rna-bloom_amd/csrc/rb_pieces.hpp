@@ -85,7 +85,7 @@ public:
     }
 private:
     template <typename Body>
-    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, Body &&);
+    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, int64_t, Body &&);
     rb_graph *g = nullptr;
     hipStream_t s = nullptr;
     const char *seq = nullptr;
@@ -97,18 +97,18 @@ private:
     int64_t launches = 0;
 };
 
-// body(piece) for every piece of <= 16 M k-mers (RB_QUERY_PIECE) of n host sequences that has a k-mer at all, in order, on the query
+// body(piece) for every piece of <= piece_dflt k-mers (RB_QUERY_PIECE overrides it) of n host sequences that has a k-mer at all, in order, on the query
 // stream s of a leased context.  ko: kmer_offsets of the sequences.  The body sizes its scratch, uploads its table, launches its kernels
 // between kernels_begin() and kernels_end() and enqueues its copies back, all on s.  prof_name: with profiling on
 // (rb_graph_profile_enable) the bracketed intervals of the call are summed into this profile entry, one launch a piece; nullptr: not timed.
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
-                         Body &&body) {
+                         int64_t piece_dflt, Body &&body) {
     HostPiece pc;
     pc.g = g; pc.s = s; pc.seq = seq; pc.offsets = offsets;
     pc.timing = prof_name && g->prof_on;
     if (pc.timing) for (Event &e : pc.ev) RB_HIP(hipEventCreate(&e.e));
-    const std::vector<int64_t> cut = piece_cuts([&](int64_t i) { return ko[i]; }, n, query_piece_max((int64_t)16 << 20));
+    const std::vector<int64_t> cut = piece_cuts([&](int64_t i) { return ko[i]; }, n, query_piece_max(piece_dflt));
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         pc.ra = cut[c]; pc.rb = cut[c + 1]; pc.pn = pc.rb - pc.ra; pc.pt = ko[pc.rb] - ko[pc.ra];
         if (pc.pt == 0) continue;
@@ -121,6 +121,12 @@ void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int6
         std::lock_guard<std::mutex> lk(g->qm);              // (queries share the handle: the profile table is written under the context lock)
         g->prof_add(prof_name, pc.ms, pc.launches);
     }
+}
+// ... with the usual pieces of 16 M k-mers
+template <typename Body>
+void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
+                         Body &&body) {
+    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, (int64_t)16 << 20, std::forward<Body>(body));
 }
 
 }  // namespace rb

@@ -561,6 +561,20 @@ void launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw,
                          int64_t row_base, float *dst, hipStream_t s);                                                   // with packed rows
 void launch_get_kmers(rb_graph *g, const rb_batch *b, const int64_t *koff, uint64_t *f, uint64_t *r, float *count, hipStream_t s);   // rb_query.hip: k_get_kmers
                                                                                           // over a whole batch made with the rnz plane: window p of read i at koff[i] + p
+// rb_query.hip: k_walk_max_cov / k_greedy_extend on device arrays with a bound per walk (bounds[i] <= bound; rows strided by `bound`)
+void launch_walk_max_cov(rb_graph *g, int direction, const uint8_t *seeds, const uint8_t *targets, size_t n, int bound, const int32_t *bounds,
+                         float min_cov, uint8_t *seq, uint8_t *out_b, uint64_t *out_f, uint64_t *out_r, float *out_c, int32_t *out_len,
+                         uint8_t *out_reason, hipStream_t s);
+void launch_greedy_extend(rb_graph *g, int direction, const uint8_t *seeds, size_t n, int lookahead, int bound, const int32_t *bounds, uint8_t *seq,
+                          uint8_t *out_b, float *out_c, int32_t *out_len, uint8_t *out_reason, hipStream_t s);
+size_t greedy_seq_stride(int k, int bound);            // bytes of a greedy walk's seq row
+// rb_mismatch.hip: correctMismatches' two scans over sequences whose text, getKmers rows and valid bits are on the device (rb_graph_correct_mismatches'
+// kernels; rb_correct.hip runs them on the stitched text).  nks: the k-mers of each sequence where kof is a capacity layout, or nullptr (kof[r + 1] - kof[r]);
+// ids / n_ids: the sequences that may have more k-mers than a code row in LDS holds (mismatch_lds_row()); grow: their rows, one byte a k-mer at kof
+int mismatch_lds_row();
+void launch_mismatch(rb_graph *g, float min_kmer_cov, int64_t pn, const int64_t *ids, int64_t n_ids, const int64_t *kof, const int32_t *nks, const int64_t *tof,
+                     const uint32_t *woff, uint32_t *valid, uint8_t *txt, uint64_t *F, uint64_t *R, float *cnt, uint8_t *grow, const float *thr, int32_t *n_fixed,
+                     int write_counts, hipStream_t s);
 void launch_pairs(rb_graph *g, const rb_batch *b, int64_t w0, int64_t nw, int mode_hash, const uint32_t *chunk_off,
                   uint64_t *out_idx, unsigned long long *n_pairs_dev, hipStream_t st = nullptr, const BitFilter *into = nullptr /* another bit array of the pair filter's geometry (the sharded engine's accumulation copy) */);
 }  // namespace rb

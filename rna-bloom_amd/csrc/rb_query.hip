@@ -284,9 +284,10 @@ __global__ void k_trav_absorb(TravArrays t, const float *__restrict__ ans, const
 // appended k-mers (3); a seed with a base outside ACGTU ends at once (4).
 // seq[i]: for a right walk the seed's bases followed by the appended ones; for a left walk the seed's bases
 // REVERSED followed by the prepended ones — either way k-mer number j of the walk (0-based) is seq[j+1 .. j+k].
+// bounds (optional): walk i appends at most bounds[i] <= bound k-mers (0: none); the rows keep the uniform stride of `bound`.
 template <class SRC>
 __global__ void k_walk_max_cov(SRC src, int stranded, int k, int direction, const uint8_t *__restrict__ seeds,
-                               const uint8_t *__restrict__ targets, size_t n, int bound, float min_cov,
+                               const uint8_t *__restrict__ targets, size_t n, int bound, const int32_t *__restrict__ bounds, float min_cov,
                                uint8_t *__restrict__ seq, uint8_t *__restrict__ out_b, uint64_t *__restrict__ out_f, uint64_t *__restrict__ out_r,
                                float *__restrict__ out_c, int32_t *__restrict__ out_len, uint8_t *__restrict__ out_reason) {
     __shared__ uint32_t s_seen[32][64];                   // [word][lane]: bitmap of the hashes the lane's walk appended
@@ -322,12 +323,13 @@ __global__ void k_walk_max_cov(SRC src, int stranded, int k, int direction, cons
     const uint8_t acgt[4] = {'A', 'C', 'G', 'T'};
     int len = 0;
     uint8_t reason = 3;
+    const int my_bound = bounds ? bounds[i] : bound;
     if (resume) {                                             // a suspended walk: where it stood, and the bitmap of what it appended
         f = ta.f[i]; r = ta.r[i]; len = ta.len[i];
         for (int j = 0; j < len; ++j) { const uint32_t hb = (uint32_t)((pf[j] * 0x9E3779B97F4A7C15ull) >> 54); s_seen[hb >> 5][threadIdx.x] |= 1u << (hb & 31u); }
     } else
         for (uint32_t q = 0; q < uk; ++q) sq[q] = (direction == 0) ? sb[q] : sb[uk - 1u - q];
-    while (len < bound) {
+    while (len < my_bound) {
         const uint32_t oc = code_of_char(sq[len]);            // base leaving: first base (right walk) / last base (left walk)
         const uint64_t s_out = seed_of(oc), sc_out = seed_of(3u - oc);
         float best_c = -1.0f;
@@ -540,7 +542,8 @@ __device__ __forceinline__ int walk_neighbors(W &w, uint64_t kmul, const WalkGat
 }
 template <class SRC>
 __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stranded, int k, int direction, const uint8_t *__restrict__ seeds, size_t n,
-                                int lookahead, int bound, uint8_t *__restrict__ seq, uint8_t *__restrict__ out_b,
+                                int lookahead, int bound, const int32_t *__restrict__ bounds /* optional: walk i stops after bounds[i] <= bound k-mers */,
+                                uint8_t *__restrict__ seq, uint8_t *__restrict__ out_b,
                                 float *__restrict__ out_c, int32_t *__restrict__ out_len, uint8_t *__restrict__ out_reason) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -570,7 +573,8 @@ __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stran
     int fr_n[WALK_MAX_LOOKAHEAD], fr_next[WALK_MAX_LOOKAHEAD];
     WalkCand path[WALK_MAX_LOOKAHEAD + 1];             // path[0] = the candidate being scored ("source")
     bool suspended = false;                            // sharded graphs: a neighbourhood whose counts are not known yet
-    while (len < bound) {
+    const int my_bound = bounds ? bounds[i] : bound;
+    while (len < my_bound) {
         const int nc = walk_neighbors(w, kmul, gate, stranded, uk, direction, f, r, code_of_char(sq[len]), 1.0f, cand);
         if (nc < 0) { suspended = true; break; }
         if (nc == 0) { reason = 0; break; }
@@ -693,6 +697,26 @@ void rb::launch_batch_counts(rb_graph *g, const rb_batch *b, int64_t w0, int64_t
                            b->word_read, b->woff, b->len, w0, nw, r_first, g->k, koff, (int64_t)0, row_base, dst);
     RB_HIP(hipGetLastError());
 }
+
+// the two walk kernels on device arrays, each walk with a bound of its own (rb_correct.hip): walk i runs at most bounds[i] <= bound steps; the row
+// layout is that of rb_graph_walk / rb_graph_greedy_extend with the uniform `bound` (seq rows of k + bound, resp. k + bound + 17 bytes)
+void rb::launch_walk_max_cov(rb_graph *g, int direction, const uint8_t *seeds, const uint8_t *targets, size_t n, int bound, const int32_t *bounds,
+                             float min_cov, uint8_t *seq, uint8_t *out_b, uint64_t *out_f, uint64_t *out_r, float *out_c, int32_t *out_len,
+                             uint8_t *out_reason, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_walk_max_cov<DirectCounts>, dim3(blocks_for((int64_t)n, 64)), dim3(64), 0, s, DirectCounts{g->view(0, 0)}, (int)g->stranded, g->k,
+                       direction, seeds, targets, n, bound, bounds, min_cov, seq, out_b, out_f, out_r, out_c, out_len, out_reason);
+    RB_HIP(hipGetLastError());
+}
+void rb::launch_greedy_extend(rb_graph *g, int direction, const uint8_t *seeds, size_t n, int lookahead, int bound, const int32_t *bounds, uint8_t *seq,
+                              uint8_t *out_b, float *out_c, int32_t *out_len, uint8_t *out_reason, hipStream_t s) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_greedy_extend<DirectCounts>, dim3(blocks_for((int64_t)n, 64)), dim3(64), 0, s, DirectCounts{g->view(0, 0)}, kmul_of(g->k),
+                       WalkGate{nullptr, g->dbg.mod, 0}, (int)g->stranded, g->k, direction, seeds, n, lookahead, bound, bounds, seq, out_b, out_c, out_len,
+                       out_reason);
+    RB_HIP(hipGetLastError());
+}
+size_t rb::greedy_seq_stride(int k, int bound) { return (size_t)k + (size_t)bound + (size_t)WALK_MAX_LOOKAHEAD + 1; }
 
 // getKmers of every read of a batch made from raw strings (rb_graph_kmers' kernel, for callers that keep the rows on the device:
 // rb_mismatch.hip): hashes and count of window p of read i at koff[i] + p
@@ -945,7 +969,7 @@ int rb_graph_walk(rb_graph *g, const char *seeds, const char *targets, size_t n,
         RB_HIP(hipMemcpyAsync(dseed, seeds, n * k, hipMemcpyHostToDevice, s));
         if (targets) RB_HIP(hipMemcpyAsync(dtarget, targets, n * k, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_walk_max_cov<DirectCounts>, dim3(blocks_for((int64_t)n, 64)), dim3(64), 0, s, DirectCounts{g->view(0, 0)}, (int)g->stranded, g->k, direction,
-                           dseed, targets ? dtarget : (const uint8_t *)nullptr, n, bound, min_cov, dseq, dbases, q.c->b1.as<uint64_t>(),
+                           dseed, targets ? dtarget : (const uint8_t *)nullptr, n, bound, (const int32_t *)nullptr, min_cov, dseq, dbases, q.c->b1.as<uint64_t>(),
                            q.c->b2.as<uint64_t>(), dc, dlen, dreason);
         RB_HIP(hipGetLastError());
         RB_HIP(hipMemcpyAsync(out_len, dlen, n * 4, hipMemcpyDeviceToHost, s));
@@ -990,7 +1014,7 @@ int rb_graph_greedy_extend(rb_graph *g, const rb_graph *gate, const char *seeds,
         RB_HIP(hipMemcpyAsync(dseed, seeds, n * k, hipMemcpyHostToDevice, s));
         WalkGate wg{gate ? gate->dbg.bits : nullptr, gate ? gate->dbg.mod : g->dbg.mod, gate ? gate->dbg.num_hash : 0};
         hipLaunchKernelGGL(k_greedy_extend<DirectCounts>, dim3(blocks_for((int64_t)n, 64)), dim3(64), 0, s, DirectCounts{g->view(0, 0)}, kmul_of(g->k), wg, (int)g->stranded, g->k, direction,
-                           dseed, n, lookahead, bound, dseq, dbases, dc, dlen, dreason);
+                           dseed, n, lookahead, bound, (const int32_t *)nullptr, dseq, dbases, dc, dlen, dreason);
         RB_HIP(hipGetLastError());
         RB_HIP(hipMemcpyAsync(out_len, dlen, n * 4, hipMemcpyDeviceToHost, s));
         RB_HIP(hipMemcpyAsync(out_reason, dreason, n, hipMemcpyDeviceToHost, s));
@@ -1210,10 +1234,10 @@ int rb_shard_trav_advance(rb_graph *g, int64_t *n_active, int64_t *bit_counts, i
             const dim3 gr(blocks_for((int64_t)n, 64)), th(64);
             if (t->kind == 0)
                 hipLaunchKernelGGL(k_walk_max_cov<ReplayCounts>, gr, th, 0, s, src, (int)g->stranded, g->k, t->direction, t->dseed,
-                                   t->has_targets ? t->dtarget : (const uint8_t *)nullptr, n, t->bound, t->min_cov, t->dseq, t->dbases, t->df, t->dr, t->dc, t->dlen, t->dreason);
+                                   t->has_targets ? t->dtarget : (const uint8_t *)nullptr, n, t->bound, (const int32_t *)nullptr, t->min_cov, t->dseq, t->dbases, t->df, t->dr, t->dc, t->dlen, t->dreason);
             else if (t->kind == 1)
                 hipLaunchKernelGGL(k_greedy_extend<ReplayCounts>, gr, th, 0, s, src, kmul_of(g->k), WalkGate{nullptr, g->dbg.mod, 0}, (int)g->stranded, g->k, t->direction,
-                                   t->dseed, n, t->lookahead, t->bound, t->dseq, t->dbases, t->dc, t->dlen, t->dreason);
+                                   t->dseed, n, t->lookahead, t->bound, (const int32_t *)nullptr, t->dseq, t->dbases, t->dc, t->dlen, t->dreason);
             else
                 hipLaunchKernelGGL(k_naive_extend<ReplayCounts>, gr, th, 0, s, src, (int)g->stranded, g->k, t->direction, t->mode, t->dseed, n, t->bound, t->cap, t->min_cov,
                                    t->dterm, t->dtoff, t->dtf, t->dtko, t->dseq, t->dbases, t->df, t->dlen, t->dreason);

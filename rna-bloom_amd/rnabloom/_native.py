@@ -59,6 +59,13 @@ class CovStats(C.Structure):
 assert C.sizeof(CovParams) == 24 and C.sizeof(CovStats) == 48
 
 
+class CorrParams(C.Structure):
+    _fields_ = [("lookahead", C.c_int32), ("max_indel_size", C.c_int32), ("percent_identity", C.c_float), ("min_kmer_cov", C.c_float)]
+
+
+assert C.sizeof(CorrParams) == 16
+
+
 class Profile(C.Structure):
     _fields_ = [("n", C.c_int32), ("name", C.c_char_p * PROF_MAX), ("ms", C.c_double * PROF_MAX),
                 ("launches", C.c_int64 * PROF_MAX)]
@@ -99,6 +106,7 @@ SYMBOLS = [
     ("rb_graph_read_coverage", _i32, [_vp, _vp, _i64, _i64, _vp, _i64, C.POINTER(CovParams), _vp, _vp, _i32]),
     ("rb_graph_paired_kmer_segments", _i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_correct_mismatches", _i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    ("rb_graph_correct_errors", _i32, [_vp, _vp, _vp, _i64, _vp, C.POINTER(CorrParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -529,6 +529,41 @@ class BloomFilterDeBruijnGraph:
         out, nf, _, _ = self.correctMismatchesFlat(seq, off, thresholds, minKmerCov)
         return [(out[off[i]:off[i + 1]].tobytes(), int(nf[i])) for i in range(len(seqs))]
 
+    GAP_DTYPE = np.dtype([("seq", "<i4"), ("first", "<i4"), ("run", "<i4"), ("repl_len", "<i4"), ("kind", "u1"), ("outcome", "u1"), ("pad", "u1", (2,))])
+    GAP_KINDS = ("left_edge", "right_edge", "snv", "path")
+    GAP_OUTCOMES = ("kept", "replaced", "trimmed")
+    CORR_CORRECTED, CORR_GAP, CORR_MISMATCH = 1, 2, 4
+
+    def correctErrorsFlat(self, seq, offsets, thresholds, lookahead=5, maxIndelSize=1, percentIdentity=0.9, minKmerCov=1.0, gaps=False):
+        """rb_graph_correct_errors on flat host text (GraphUtils.correctErrorHelper, R/util/GraphUtils.java:3711-3912): sequence i is
+        seq[offsets[i]:offsets[i + 1]] (uint8), thresholds one covThreshold per sequence (a scalar is used for all).  Returns (out, out_offsets,
+        out_len, flags, gap_records, gap_offsets): corrected sequence i is out[out_offsets[i]:out_offsets[i] + out_len[i]]; flags carry
+        CORR_CORRECTED / CORR_GAP / CORR_MISMATCH; with gaps=True one GAP_DTYPE record per gap, those of sequence i at
+        gap_records[gap_offsets[i]:gap_offsets[i + 1]] (else both None)."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        thr = np.ascontiguousarray(np.broadcast_to(np.asarray(thresholds, np.float32), (n,)))
+        p = N.CorrParams(lookahead, maxIndelSize, percentIdentity, minKmerCov)
+        oo = np.zeros(n + 1, np.int64)
+        go = np.zeros(n + 1, np.int64) if gaps else None
+        check(lib.rb_graph_correct_errors(self.h, _ptr(seq), _ptr(off), n, _ptr(thr), C.byref(p), _ptr(oo), None, None, None, None, _ptr(go)))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        ol = np.zeros(n, np.int32); fl = np.zeros(n, np.uint32)
+        rec = np.zeros(max(1, int(go[n])), self.GAP_DTYPE) if gaps else None
+        check(lib.rb_graph_correct_errors(self.h, _ptr(seq), _ptr(off), n, _ptr(thr), C.byref(p), _ptr(oo), _ptr(out), _ptr(ol), _ptr(fl), _ptr(rec), _ptr(go)))
+        if gaps:
+            rec = rec[:int(go[n])]
+        return out, oo, ol, fl, rec, go
+
+    def correctErrors(self, seqs, thresholds, lookahead=5, maxIndelSize=1, percentIdentity=0.9, minKmerCov=1.0):
+        """GraphUtils.correctErrorHelper of each sequence's getKmers list: per sequence (bytes, corrected) — the string the reference's
+        returned k-mers spell, or the sequence itself with corrected False where the reference returns null."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        out, oo, ol, fl, _, _ = self.correctErrorsFlat(seq, off, thresholds, lookahead, maxIndelSize, percentIdentity, minKmerCov)
+        return [(out[oo[i]:oo[i] + ol[i]].tobytes(), bool(fl[i] & self.CORR_CORRECTED)) for i in range(len(seqs))]
+
     def getNeighbors(self, f, r, charOut, direction):
         """4 successors (direction 0) / predecessors (1) of each k-mer: (f4, r4, count4) shaped [n,4]."""
         f = _u64(np.atleast_1d(f)); r = _u64(np.atleast_1d(r))
