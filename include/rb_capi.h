@@ -358,6 +358,54 @@ typedef struct rb_corr_gap {            /* 20 bytes */
 } rb_corr_gap;
 int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, const rb_corr_params *p,
                             int64_t *out_offsets, char *out_seq, int32_t *out_len, uint32_t *flags, rb_corr_gap *gaps, int64_t *gap_offsets);
+/* Overlap of read pairs — GraphUtils.overlap (R/util/GraphUtils.java:4898-5063), the first half of overlapAndConnect (:5065-5090) that the
+ * FragmentAssembler runs on every corrected pair (R/RNABloom.java:2148), over SeqUtils.overlapMaximally (R/util/SeqUtils.java:1335-1379).  A wavefront
+ * per pair on the device; the call is read-only.  Pair i is left = lseq[loffsets[i], loffsets[i+1]) and right = rseq[roffsets[i], roffsets[i+1]); each
+ * read's k-mer list is getKmers(String)'s, as rb_graph_kmers gives it (every window; count 0 for a window with a letter outside ACGTU).
+ *   match(a, b, mo): the smallest shift s in [0, |a| - mo] at which b agrees with a over the whole extent they share, a[s, min(s + |b|, |a|)) ==
+ *   b[0, ...), bytes compared exactly (case matters) — the first hit of the reference's indexOf(prefix) loop.  s + |b| < |a|: overlapped = a (b is
+ *   contained); else overlapped = a + b[|a| - s ..].  No such s, |a| < |b| and b contains a: overlapped = b.
+ *   1. match(left, right, min_overlap).  None: mo' = max(min_overlap, min(|left|, |right|) * 3 / 4) (int arithmetic) and match(right, left, mo'); a
+ *      hit swaps the roles (dovetail, RB_OVL_SWAPPED: left / right below, LEFT / RIGHT and the text are in swapped terms).  None: NONE, WHY_NO_MATCH.
+ *   2. o = |left| + |right| - |overlapped| bases overlap.  o >= k: |overlapped| == max(|left|, |right|) -> LEFT if |left| >= |right| else RIGHT
+ *      (the longer read's k-mers are returned).  Else at least one of right's k-mers 0 .. o - k must not be a homopolymer (all k bytes equal), else
+ *      NONE, WHY_NO_COMPLEX; the result is left's k-mers and right's from o - k + 1: MERGED.  No graph look-up.
+ *   3. o < k: the spanning k-mers are the windows span_first = |left| - k + 1 .. span_first + span_n - 1 of overlapped, span_n = k - 1 - o
+ *      (graph.getKmers(overlapped, start, end): [start, end) is a range of bases).  In order: the first with count < min_kmer_cov makes the span
+ *      invalid and ends the walk; a k-mer seen before that which is no homopolymer makes the span complex.  Valid: an empty or a complex span gives
+ *      SPANNED (left + spanning + right), else NONE, WHY_NO_COMPLEX.  Invalid: the reference rescues the pair (:5018-5056: addDbgOnly of the
+ *      spanning k-mers of count 0, correctMismatches with threshold 2, addReadPairedKmers) if some right k-mer i < min(o, nkR) has count == 1
+ *      (else WHY_NO_RIGHT_SINGLETON), some left k-mer i >= max(0, nkL - o) has count == 1 (else WHY_NO_LEFT_SINGLETON) and
+ *      !SeqUtils.isRepeat(right[0, o)) (:417-456; else WHY_REPEAT), tested in that order: RESCUE.  The call changes nothing: a RESCUE record
+ *      describes the pair BEFORE the mutation (the text is overlapped before correctMismatches) and the caller applies those lines.  After them the
+ *      reference's no-complex-k-mer test cannot fail: a span of homopolymers forces right[0, o) to be one letter, for which isRepeat is true.
+ *      isRepeat(String) indexes its count arrays with -1 at a letter outside ACGTU (upper case only) and throws unless a threshold was reached
+ *      before that letter: WHY_REPEAT_THROWS (NONE; the reference's worker dies there).
+ *   A pair with a read shorter than max(k, min_overlap) gets NONE, WHY_SHORT (the reference throws in substring, or is never called).
+ *   Output: out_offsets (host, n + 1) is the capacity layout |left_i| + |right_i|, from the lengths alone.  out_seq == NULL: a size query — only
+ *   out_offsets is filled, nothing is launched.  out_seq[out_offsets[i] ..] holds the string the returned k-mer list spells and recs[i].out_len its
+ *   length: the containing read's text (LEFT / RIGHT), overlapped (MERGED / SPANNED / RESCUE), nothing (NONE: out_len 0).  recs[i].overlap = o
+ *   and the SWAPPED flag are set whenever a match was found (NONE with another reason than NO_MATCH / SHORT included), span_first / span_n for
+ *   SPANNED and RESCUE, else 0.  A NONE is the caller's cue for GraphUtils.join; `why` says which line returned null.
+ * Every pair is judged against the graph as it stands when the call starts: a rescue is not applied before the next pair is looked at.  The
+ * reference's `-t N` workers give no order between pairs either.
+ * The call works in pieces cut by the input letters of both reads (RB_QUERY_PIECE letters, 64 M by default; 2 bytes of device scratch per letter and
+ * 48 per pair); results do not depend on the cuts.  It leases a query context (re-entrant on one handle).  With rb_graph_profile_enable on the
+ * kernels' device time is added to the profile entry "overlap".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle, loffsets, roffsets, out_offsets (or recs, unless out_seq is NULL too); text missing where
+ * offsets say there is some; decreasing offsets; a shard handle; a destroyed dbgbf or counting filter; min_overlap < 1; a min_kmer_cov that is
+ * not finite. */
+enum { RB_OVL_NONE = 0, RB_OVL_LEFT = 1, RB_OVL_RIGHT = 2, RB_OVL_MERGED = 3, RB_OVL_SPANNED = 4, RB_OVL_RESCUE = 5 };      /* rb_overlap_rec.outcome */
+enum { RB_OVL_WHY_FOUND = 0, RB_OVL_WHY_NO_MATCH = 1, RB_OVL_WHY_NO_COMPLEX = 2, RB_OVL_WHY_NO_RIGHT_SINGLETON = 3, RB_OVL_WHY_NO_LEFT_SINGLETON = 4,
+       RB_OVL_WHY_REPEAT = 5, RB_OVL_WHY_SHORT = 6, RB_OVL_WHY_REPEAT_THROWS = 7 };                                           /* rb_overlap_rec.why */
+#define RB_OVL_SWAPPED 1u
+typedef struct rb_overlap_rec {         /* 32 bytes */
+    int32_t outcome, why;
+    uint32_t flags;
+    int32_t overlap, out_len, span_first, span_n, pad;
+} rb_overlap_rec;
+int rb_graph_overlap_pairs(rb_graph *g, const char *lseq, const int64_t *loffsets, const char *rseq, const int64_t *roffsets, int64_t n,
+                           int min_overlap, float min_kmer_cov, int64_t *out_offsets, char *out_seq, rb_overlap_rec *recs);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

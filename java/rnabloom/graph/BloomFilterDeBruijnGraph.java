@@ -480,6 +480,34 @@ public class BloomFilterDeBruijnGraph {
         return res;
     }
 
+    /**
+     * GraphUtils.overlap (src/rnabloom/util/GraphUtils.java:4898-5063) for a batch of read pairs in ONE native call: the suffix / prefix match,
+     * the dovetail attempt and the spanning k-mers' look-ups run on the device, a wavefront per pair, and nothing is written to the graph.
+     * Returns, per pair, the string the reference's returned k-mers spell, or null where the reference returns null (the cue for join).
+     * recs (optional, 8 * lefts.length ints) receives the records of NativeGraph.overlapPairs: a pair whose outcome recs[8 i] is 5 is one the
+     * reference would rescue — its string is the joined text BEFORE lines :5018-5056, which the caller runs on that pair's Kmer lists.
+     */
+    public String[] overlapPairs(String[] lefts, String[] rights, int minOverlap, float minKmerCov, int[] recs) {
+        final int n = lefts.length;
+        if (rights.length != n) throw new IllegalArgumentException("overlapPairs: " + n + " left reads and " + rights.length + " right reads");
+        final long[] lo = new long[n + 1], ro = new long[n + 1], outOff = new long[n + 1];
+        for (int i = 0; i < n; ++i) { lo[i + 1] = lo[i] + lefts[i].length(); ro[i + 1] = ro[i] + rights[i].length(); }
+        if (lo[n] + ro[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("overlapPairs: more than 2 GB of text in one batch");
+        final ByteBuffer lt = ByteBuffer.allocateDirect(Math.max((int) lo[n], 1)), rt = ByteBuffer.allocateDirect(Math.max((int) ro[n], 1));
+        for (String s : lefts) for (int i = 0; i < s.length(); ++i) lt.put((byte) s.charAt(i));
+        for (String s : rights) for (int i = 0; i < s.length(); ++i) rt.put((byte) s.charAt(i));
+        final int cap = (int) (lo[n] + ro[n]);
+        final ByteBuffer out = ByteBuffer.allocateDirect(Math.max(cap, 1));
+        final int[] rec = recs != null ? recs : new int[8 * n];
+        NativeGraph.overlapPairs(handle, lt, lo, rt, ro, n, minOverlap, minKmerCov, outOff, out, rec);
+        final byte[] b = new byte[cap];
+        out.get(b, 0, cap);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = rec[8 * i] != 0 ? new String(b, (int) outOff[i], rec[8 * i + 4], java.nio.charset.StandardCharsets.ISO_8859_1) : null;
+        return res;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

@@ -117,6 +117,16 @@ public final class NativeGraph {
     public static native int correctErrors(long h, ByteBuffer seq, long[] offsets, int n, float[] covThreshold, int lookahead, int maxIndelSize,
                                            float percentIdentity, float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] outLen, int[] flags,
                                            int[] gaps, long[] gapOffsets);
+    /** Overlap of n read pairs (rb_graph_overlap_pairs; GraphUtils.overlap, R/util/GraphUtils.java:4898-5063): pair i is lseq[loffsets[i],
+     *  loffsets[i + 1]) and rseq[roffsets[i], roffsets[i + 1]).  outOffsets[n + 1] is filled from the lengths alone (room for both reads);
+     *  outSeq == null sizes the output only.  Else recs holds 8 ints per pair — outcome (0 none, 1 left's k-mers, 2 right's k-mers, 3 merged,
+     *  4 spanned, 5 the reference would rescue the pair: lines :5018-5056 are the caller's), why (0 found, 1 no match, 2 no complex k-mer,
+     *  3 no singleton in the right read, 4 none in the left read, 5 the shared bases are a repeat, 6 a read shorter than max(k, minOverlap),
+     *  7 the reference's isRepeat throws), flags (bit 0: the reads changed roles), bases overlapped, length of the text, first spanning
+     *  window and number of spanning windows of that text, 0 — and the string the returned k-mers spell is recs[8 i + 4] bytes at outSeq +
+     *  outOffsets[i].  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
+    public static native int overlapPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int minOverlap,
+                                          float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

@@ -399,6 +399,21 @@ jint FN(correctErrors)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray off
     if (rc) throw_rc(e, rc);
     return cap;
 }
+/* rb_graph_overlap_pairs: a record (rb_overlap_rec, 32 bytes) is 8 ints to Java: outcome, why, flags, overlap, out_len, span_first, span_n, 0.  outSeq == null
+ * (then recs may be null too) sizes the output: outOffsets is filled and outOffsets[n] returned */
+jint FN(overlapPairs)(JNIEnv *e, jclass c, jlong h, jobject lseq, jlongArray loffsets, jobject rseq, jlongArray roffsets, jint n, jint minOverlap,
+                      jfloat minKmerCov, jlongArray outOffsets, jobject outSeq, jintArray recs) {
+    jlong *lo = la(e, loffsets), *ro = la(e, roffsets), *oo = la(e, outOffsets);
+    jint *rc8 = ia(e, recs);
+    (void)c;
+    int rc = rb_graph_overlap_pairs(G(h), (const char *)direct(e, lseq), (const int64_t *)lo, (const char *)direct(e, rseq), (const int64_t *)ro, n, minOverlap,
+                                    minKmerCov, (int64_t *)oo, outSeq ? (char *)direct(e, outSeq) : 0, (rb_overlap_rec *)rc8);
+    if (rc == 0 && oo && n >= 0 && oo[n] > 0x7fffffffLL) rc = RB_ERR_INVALID;      /* the capacity layout does not fit the int this returns: smaller batches */
+    const jint cap = rc == 0 && oo && n >= 0 ? (jint)oo[n] : 0;
+    lr(e, loffsets, lo, JNI_ABORT); lr(e, roffsets, ro, JNI_ABORT); lr(e, outOffsets, oo, 0); ir(e, recs, rc8, 0);
+    if (rc) throw_rc(e, rc);
+    return cap;
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -564,6 +564,64 @@ class BloomFilterDeBruijnGraph:
         out, oo, ol, fl, _, _ = self.correctErrorsFlat(seq, off, thresholds, lookahead, maxIndelSize, percentIdentity, minKmerCov)
         return [(out[oo[i]:oo[i] + ol[i]].tobytes(), bool(fl[i] & self.CORR_CORRECTED)) for i in range(len(seqs))]
 
+    OVL_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("flags", "<u4"), ("overlap", "<i4"), ("out_len", "<i4"), ("span_first", "<i4"),
+                          ("span_n", "<i4"), ("pad", "<i4")])
+    OVL_OUTCOMES = ("none", "left", "right", "merged", "spanned", "rescue")
+    OVL_WHYS = ("found", "no_match", "no_complex", "no_right_singleton", "no_left_singleton", "repeat", "short", "repeat_throws")
+    OVL_NONE, OVL_LEFT, OVL_RIGHT, OVL_MERGED, OVL_SPANNED, OVL_RESCUE = range(6)
+    OVL_SWAPPED = 1
+
+    def overlapPairsFlat(self, lseq, loffsets, rseq, roffsets, minOverlap, minKmerCov=1.0):
+        """rb_graph_overlap_pairs on flat host text (GraphUtils.overlap, R/util/GraphUtils.java:4898-5063): pair i is
+        lseq[loffsets[i]:loffsets[i + 1]] and rseq[roffsets[i]:roffsets[i + 1]] (uint8).  Returns (out, out_offsets, recs): one OVL_DTYPE
+        record per pair, the string the returned k-mer list spells at out[out_offsets[i]:out_offsets[i] + recs[i]["out_len"]].  Read-only:
+        a pair whose outcome is OVL_RESCUE is the caller's to apply (applyOverlapRescue)."""
+        flat = lambda a: np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+        lseq, rseq = flat(lseq), flat(rseq)
+        lo, ro = np.ascontiguousarray(loffsets, dtype=np.int64), np.ascontiguousarray(roffsets, dtype=np.int64)
+        n = lo.size - 1
+        oo = np.zeros(n + 1, np.int64)
+        args = (self.h, _ptr(lseq), _ptr(lo), _ptr(rseq), _ptr(ro), n, minOverlap, minKmerCov, _ptr(oo))
+        check(lib.rb_graph_overlap_pairs(*args, None, None))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        recs = np.zeros(n, self.OVL_DTYPE)
+        check(lib.rb_graph_overlap_pairs(*args, _ptr(out), _ptr(recs)))
+        return out, oo, recs
+
+    def overlapPairs(self, lefts, rights, minOverlap, minKmerCov=1.0):
+        """GraphUtils.overlap of each pair's getKmers lists: per pair (bytes or None, outcome, swapped) — the string the returned k-mers
+        spell (None where the reference returns null: the cue for join), the OVL_* outcome, and whether the reads changed roles (the
+        dovetail attempt).  For OVL_RESCUE the bytes are the joined text BEFORE the reference's mutation (applyOverlapRescue)."""
+        enc = lambda seqs: [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        (lseq, lo), (rseq, ro) = _pack(enc(lefts)), _pack(enc(rights))
+        out, oo, recs = self.overlapPairsFlat(lseq, lo, rseq, ro, minOverlap, minKmerCov)
+        return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes() if rc["outcome"] != self.OVL_NONE else None, int(rc["outcome"]),
+                 bool(rc["flags"] & self.OVL_SWAPPED)) for i, rc in enumerate(recs)]
+
+    def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
+        """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
+        calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and
+        addReadPairedKmers of the result.  Returns the corrected text (the string the reference's returned k-mers spell).
+          Not exact in one respect: the reference gives a rescued k-mer the literal count 1 and runs correctMismatches on that list; here
+        correctMismatches recounts every k-mer from the filters after addDbgOnly, so a rescued k-mer counts cbf + 1 (1 unless its counters
+        are taken: a false positive, or a k-mer the counting filter has seen) and a spanning window with a letter outside ACGTU — which
+        the reference also adds and counts as 1 — counts 0."""
+        left, right = (s.encode() if isinstance(s, str) else bytes(s) for s in (left, right))
+        assert int(rec["outcome"]) == self.OVL_RESCUE
+        if int(rec["flags"]) & self.OVL_SWAPPED:
+            left, right = right, left
+        joined = left + right[int(rec["overlap"]):]
+        _, f, r, c = self.getKmers([joined])
+        h0 = f if self.stranded else np.where(r.view(np.int64) < f.view(np.int64), r, f)
+        span = slice(int(rec["span_first"]), int(rec["span_first"]) + int(rec["span_n"]))
+        missing = h0[span][c[span] == 0]
+        if missing.size:
+            self.addDbgOnly(missing)
+        fixed = self.correctMismatches([joined], 2.0, minKmerCov)[0][0]
+        _, f, r, _ = self.getKmers([fixed])
+        self.addReadPairedKmers(f, r)
+        return fixed
+
     def getNeighbors(self, f, r, charOut, direction):
         """4 successors (direction 0) / predecessors (1) of each k-mer: (f4, r4, count4) shaped [n,4]."""
         f = _u64(np.atleast_1d(f)); r = _u64(np.atleast_1d(r))
