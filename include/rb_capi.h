@@ -788,6 +788,25 @@ int rb_debug_probe_cbf(rb_graph *g, int mode, float *ms_out);
  * (hi_begin < 0: one range); vals may be NULL (keys only), vals64 != 0: 64-bit values. */
 int rb_debug_scan_u32(int device, const uint32_t *in, size_t n, uint32_t *out, int misalign);
 int rb_debug_sort_pairs(int device, uint64_t *keys, void *vals, int vals64, size_t n, int lo_begin, int lo_end, int hi_begin, int hi_end);
+/* development / tests: the grouping stage of the insert pipeline (csrc/rb_group.hip) on host arrays, called the way an insert calls it.
+ * In: n > 0 records (keys[i], vals[i]) = (base hash, occurrence id); group_bits, bucket_target (0: default) and flags (1: records with
+ * key and value all ones are cancelled ones) as an insert passes them; seed, ordinal0, pos_bits of the strength draws; idx_span != 0:
+ * partition keyed by the filter index ((key >> 1) % idx_size, indices [idx_lo, idx_lo + idx_span)), else by the hash bits.
+ * Out, n entries each: vals_out (occurrences in grouped order; the first info[9] are written), tz_out (their strengths), and the runs
+ * uniq / counts / starts (the first info[7] are written; the rest reads 0).  brun / bnr (both or neither; room for 2^20 entries, the
+ * first 2^T are written): per fine bucket the first run slot and the number of runs, as the swept Bloom-bit stage gets them.
+ * info[12]: 0 T (partition bits), 1 t_hi, 2 t_lo (first / second partition pass), 3 l_hi, 4 l_lo (locally sorted bits below them),
+ * 5 the fix level in force, 6 index-keyed (0 / 1), 7 runs, 8 runs before the oversized buckets' (-1 without brun), 9 live records,
+ * 10 oversized buckets, 11 records of the largest of them.  The RB_GROUP_* environment switches are read on every call. */
+int rb_debug_group(int device, const uint64_t *keys, const uint32_t *vals, size_t n, int group_bits, int bucket_target, unsigned flags,
+                   uint64_t seed, uint64_t ordinal0, uint32_t pos_bits, uint64_t idx_size, uint64_t idx_lo, uint64_t idx_span,
+                   uint32_t *vals_out, uint8_t *tz_out, uint64_t *uniq, uint32_t *counts, uint32_t *starts, uint32_t *brun, uint32_t *bnr,
+                   int64_t *info);
+/* development / tests: the selection primitives (csrc/rb_sort.hip).  out_a = the indices i in [0, n) with (status[i] & mask_a) != 0, in
+ * order, counts[0] of them; mask_b != 0: the same for mask_b into out_b / counts[1] in the same two passes (mask_b == 0: the one-list
+ * call, out_b may be NULL, counts[1] = 0).  out_a / out_b have room for n entries. */
+int rb_debug_select(int device, const uint32_t *status, size_t n, uint32_t mask_a, uint32_t mask_b, uint32_t *out_a, uint32_t *out_b,
+                    uint32_t *counts);
 
 /* ---- the exchange driver below the C ABI (csrc/rb_comm.hip) ----
  * rb_shard_add_range = rnabloom/sharded.py::ShardRank.add_range in the library: all sub-batches of reads [first, first + n)

@@ -806,6 +806,83 @@ int rb_debug_sort_pairs(int device, uint64_t *keys, void *vals, int vals64, size
         if (vals) RB_HIP(hipMemcpy(vals, v1.p, n * vb, hipMemcpyDeviceToHost));
     });
 }
+int rb_debug_group(int device, const uint64_t *keys, const uint32_t *vals, size_t n, int group_bits, int bucket_target, unsigned flags,
+                   uint64_t seed, uint64_t ordinal0, uint32_t pos_bits, uint64_t idx_size, uint64_t idx_lo, uint64_t idx_span,
+                   uint32_t *vals_out, uint8_t *tz_out, uint64_t *uniq, uint32_t *counts, uint32_t *starts, uint32_t *brun, uint32_t *bnr, int64_t *info) {
+    DevBuf k0, v0, k1, v1, vo, tz, un, cn, st, br, bn, t, ctr;
+    return guarded([&] {
+        RB_REQUIRE(keys && vals && vals_out && tz_out && uniq && counts && starts && info, "rb_debug_group: null array");
+        RB_REQUIRE(n > 0 && n < ((size_t)1 << 28), "rb_debug_group: record count out of range");
+        RB_REQUIRE((brun == nullptr) == (bnr == nullptr), "rb_debug_group: brun and bnr go together");
+        RB_REQUIRE(pos_bits < 32 && (idx_span == 0 || idx_size > 0), "rb_debug_group: bad pos_bits / index range");
+        RB_HIP(hipSetDevice(device));
+        const int gflags = (int)flags;
+        const GrIdx idx = idx_span ? GrIdx{make_mod(idx_size), idx_lo, idx_span} : GrIdx{Mod{1, 0, 0}, 0, 0};
+        uint32_t plan[7];
+        group_debug_plan(n, group_bits, bucket_target, gflags, idx, plan);
+        const size_t nbk = (size_t)1 << plan[0];
+        k0.reserve(n * 8); v0.reserve(n * 4); k1.reserve(n * 8); v1.reserve(n * 4);
+        vo.reserve(n * 4); tz.reserve(n + 16); un.reserve(n * 8); cn.reserve((n + 1) * 4); st.reserve((n + 1) * 4);
+        t.reserve(group_temp_bytes(n, group_bits, bucket_target, gflags));
+        ctr.reserve(64);
+        RB_HIP(hipMemcpy(k0.p, keys, n * 8, hipMemcpyHostToDevice));
+        RB_HIP(hipMemcpy(v0.p, vals, n * 4, hipMemcpyHostToDevice));
+        // what the stage does not write (the slots behind the live records and behind the runs) reads as zero
+        RB_HIP(hipMemset(vo.p, 0, n * 4)); RB_HIP(hipMemset(tz.p, 0, n)); RB_HIP(hipMemset(un.p, 0, n * 8));
+        RB_HIP(hipMemset(cn.p, 0, n * 4)); RB_HIP(hipMemset(st.p, 0, n * 4)); RB_HIP(hipMemset(ctr.p, 0, 64));
+        GroupExport ex;
+        if (brun) {
+            br.reserve(nbk * 4 + 16); bn.reserve(nbk * 4 + 16);
+            RB_HIP(hipMemset(br.p, 0, nbk * 4)); RB_HIP(hipMemset(bn.p, 0, nbk * 4));
+            ex = GroupExport{br.as<uint32_t>(), bn.as<uint32_t>(), ctr.as<uint32_t>() + 1};
+        }
+        group_records_device(k0.as<uint64_t>(), v0.as<uint32_t>(), k1.as<uint64_t>(), v1.as<uint32_t>(), n, group_bits, seed, ordinal0, pos_bits,
+                             t.p, t.cap, vo.as<uint32_t>(), tz.as<uint8_t>(), un.as<uint64_t>(), cn.as<uint32_t>(), st.as<uint32_t>(), ctr.as<uint32_t>(),
+                             nullptr, nullptr, bucket_target, gflags, idx, ex);
+        RB_HIP(hipDeviceSynchronize());
+        uint32_t c[2] = {0, 0}, live = (uint32_t)n, n_big = 0, largest = 0;
+        uint64_t big_rec = 0;
+        RB_HIP(hipMemcpy(c, ctr.p, 8, hipMemcpyDeviceToHost));
+        if (gflags & GR_FLAG_DEAD) RB_HIP(hipMemcpy(&live, group_live_count(t.p, n, group_bits, bucket_target, gflags), 4, hipMemcpyDeviceToHost));
+        group_debug_big(t.p, n, group_bits, bucket_target, &n_big, &big_rec, &largest, gflags);
+        RB_REQUIRE(c[0] <= n && live <= n, "rb_debug_group: the stage reports %u runs and %u live records of %zu", c[0], live, n);
+        RB_HIP(hipMemcpy(vals_out, vo.p, n * 4, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(tz_out, tz.p, n, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(uniq, un.p, n * 8, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(counts, cn.p, n * 4, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(starts, st.p, n * 4, hipMemcpyDeviceToHost));
+        if (brun) {
+            RB_HIP(hipMemcpy(brun, br.p, nbk * 4, hipMemcpyDeviceToHost));
+            RB_HIP(hipMemcpy(bnr, bn.p, nbk * 4, hipMemcpyDeviceToHost));
+        }
+        for (int i = 0; i < 7; ++i) info[i] = (int64_t)plan[i];
+        info[7] = (int64_t)c[0]; info[8] = brun ? (int64_t)c[1] : -1; info[9] = (int64_t)live;
+        info[10] = (int64_t)n_big; info[11] = (int64_t)largest;
+    });
+}
+int rb_debug_select(int device, const uint32_t *status, size_t n, uint32_t mask_a, uint32_t mask_b, uint32_t *out_a, uint32_t *out_b, uint32_t *counts) {
+    DevBuf s, a, b, t, ctr;
+    return guarded([&] {
+        RB_REQUIRE(counts && (n == 0 || (status && out_a && (out_b || mask_b == 0u))), "rb_debug_select: null array");
+        RB_REQUIRE(n < ((size_t)1 << 31), "rb_debug_select: too many items");
+        RB_HIP(hipSetDevice(device));
+        s.reserve(n * 4 + 16); a.reserve(n * 4 + 16); b.reserve(n * 4 + 16); ctr.reserve(64);
+        t.reserve(mask_b ? select2_temp_bytes(n) : select_temp_bytes(n));
+        if (n) RB_HIP(hipMemcpy(s.p, status, n * 4, hipMemcpyHostToDevice));
+        RB_HIP(hipMemset(ctr.p, 0xFF, 64));
+        if (mask_b) select_flagged2(t.p, t.cap, s.as<uint32_t>(), n, mask_a, a.as<uint32_t>(), mask_b, b.as<uint32_t>(), ctr.as<uint32_t>(), nullptr);
+        else select_flagged(t.p, t.cap, s.as<uint32_t>(), mask_a, n, a.as<uint32_t>(), ctr.as<uint32_t>(), nullptr);
+        RB_HIP(hipGetLastError());
+        RB_HIP(hipDeviceSynchronize());
+        uint32_t c[2] = {0, 0};
+        RB_HIP(hipMemcpy(c, ctr.p, 8, hipMemcpyDeviceToHost));
+        if (!mask_b) c[1] = 0;
+        RB_REQUIRE(c[0] <= n && c[1] <= n, "rb_debug_select: the selection reports %u and %u of %zu items", c[0], c[1], n);
+        if (c[0]) RB_HIP(hipMemcpy(out_a, a.p, (size_t)c[0] * 4, hipMemcpyDeviceToHost));
+        if (c[1]) RB_HIP(hipMemcpy(out_b, b.p, (size_t)c[1] * 4, hipMemcpyDeviceToHost));
+        counts[0] = c[0]; counts[1] = c[1];
+    });
+}
 int rb_filter_size(rb_graph *g, int which, int64_t *size, int64_t *nbytes, int *num_hash) {
     if (!g) { set_error("null graph"); return RB_ERR_INVALID; }
     if (which == RB_CBF) {

@@ -1134,6 +1134,12 @@ uint32_t group_index_buckets(size_t N, int group_bits, int bucket_target, int fl
     const GroupPlan P = group_plan(N, group_bits, bucket_target, flags);
     return (P.T && idx.span > (1ull << P.T)) ? P.T : 0u;
 }
+// debugging aid (rb_debug_group): what such a grouping is planned as — T, t_hi, t_lo, l_hi, l_lo, the fix level, index-keyed partition (0 / 1)
+void group_debug_plan(size_t N, int group_bits, int bucket_target, int flags, GrIdx idx, uint32_t out[7]) {
+    const GroupPlan P = group_plan(N, group_bits, bucket_target, flags);
+    out[0] = P.T; out[1] = P.t_hi; out[2] = P.t_lo; out[3] = P.l_hi; out[4] = P.l_lo; out[5] = P.fix_cap;
+    out[6] = (P.T && gr_idx_dev(P, idx).mul != 0) ? 1u : 0u;
+}
 
 // ---- swept Bloom-bit stage -------------------------------------------------------------------------------------------------
 // Stage A tests and sets two Bloom bits per run.  With the grouping keyed by the first index, probe 0 of the runs of fine bucket c falls

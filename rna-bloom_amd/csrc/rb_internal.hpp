@@ -338,6 +338,9 @@ void group_records_device(uint64_t *keys0, uint32_t *vals0, uint64_t *keys_tmp, 
                           GroupExport ex = GroupExport{});
 // T, the log2 of the number of index ranges (fine buckets) such a grouping partitions by; 0: it would not be index-keyed
 uint32_t group_index_buckets(size_t N, int group_bits, int bucket_target, int flags, GrIdx idx);
+// debugging aid (rb_debug_group): the plan of such a grouping — T, t_hi, t_lo (partition bits: all, first pass, second pass), l_hi, l_lo
+// (locally sorted bits below them), the fix level in force, 1 if the partition is index-keyed
+void group_debug_plan(size_t N, int group_bits, int bucket_target, int flags, GrIdx idx, uint32_t out[7]);
 // Swept Bloom-bit stage (rb_group.hip): both Bloom bits of the D runs of an index-keyed grouping with 2^T buckets are tested and set range by
 // range through LDS; st0[d] / st1[d] = what probe 0 / 1 of run d found: 0 it set the bit, 1 set before the sub-batch, 2 set by another probe of
 // the sub-batch.  keys_* / vals_* are scratch for D records each.  The filter must be whole (idx.lo = 0 is the filter's first bit).

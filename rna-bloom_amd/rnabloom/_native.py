@@ -189,6 +189,9 @@ SYMBOLS = [
     ("rb_debug_probe_cbf", _i32, [_vp, _i32, C.POINTER(C.c_float)]),
     ("rb_debug_scan_u32", _i32, [_i32, _vp, _sz, _vp, _i32]),
     ("rb_debug_sort_pairs", _i32, [_i32, _vp, _vp, _i32, _sz, _i32, _i32, _i32, _i32]),
+    ("rb_debug_group", _i32, [_i32, _vp, _vp, _sz, _i32, _i32, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("rb_debug_select", _i32, [_i32, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     ("rb_graph_profile_enable", _i32, [_vp, _i32]),
     ("rb_graph_profile_get", _i32, [_vp, C.POINTER(Profile), _i32]),
 ]

@@ -1,4 +1,4 @@
-"""The library's own device-wide primitives (csrc/rb_sort.hip: scans, csrc/rb_group.hip: LSD radix sorts out of the
+"""The library's own device-wide primitives (csrc/rb_sort.hip: scans and selection, csrc/rb_group.hip: LSD radix sorts out of the
 grouping stage's stable partition passes) against numpy.  They replaced rocPRIM in round 4; every scan / sort of the
 insert pipeline, the conflict path, the FASTQ / FASTA record finders and the sketch sets goes through them."""
 import ctypes as C
@@ -86,3 +86,40 @@ def test_lsd_sort_keys_only_two_ranges_and_wide_values(n):
     v64 = rng.integers(0, 2**63, n, dtype=np.uint64)
     k, v = _sort(keys, v64, 0, 64, vals64=True)
     assert np.array_equal(k, keys[order]) and np.array_equal(v, v64[order])
+
+
+def _select(status, mask_a, mask_b=0):
+    from rnabloom import _native as N
+    st = np.ascontiguousarray(status, np.uint32)
+    a, b, cnt = np.full(st.size + 1, 0xFFFFFFFF, np.uint32), np.full(st.size + 1, 0xFFFFFFFF, np.uint32), np.zeros(2, np.uint32)
+    N.check(N.lib.rb_debug_select(0, st.ctypes.data_as(C.c_void_p), st.size, mask_a, mask_b, a.ctypes.data_as(C.c_void_p),
+                                  b.ctypes.data_as(C.c_void_p) if mask_b else None, cnt.ctypes.data_as(C.c_void_p)))
+    assert (a[cnt[0]:] == 0xFFFFFFFF).all() and (b[cnt[1]:] == 0xFFFFFFFF).all()      # nothing written behind the lists
+    return a[:cnt[0]], b[:cnt[1]]
+
+
+@pytest.mark.parametrize("density", ["none", "all", "sparse"])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 4095, 4096, 4097, 49_153, 1_000_003])
+def test_select_flagged_matches_flatnonzero(n, density):
+    """select_flagged (one mask) and select_flagged2 (two lists in the same two passes, overlapping and disjoint masks): the indices
+    of the flagged words in order, and their number"""
+    rng = np.random.default_rng(n + len(density))
+    A, B, OTHER = 0x6, 0x18, 0xFFFFFFE1                   # A and B share no bit; every word also carries bits that neither mask has
+    noise = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32) & np.uint32(OTHER)
+    if density == "none":
+        fa = fb = np.zeros(n, bool)
+    elif density == "all":
+        fa = fb = np.ones(n, bool)
+    else:
+        fa, fb = rng.random(n) < 1e-3, rng.random(n) < 1e-3
+        if n > 64:
+            fa[[0, n - 1]] = True; fb[[63, n - 2]] = True
+    bit = lambda m: np.where(rng.random(n) < 0.5, m & -m, m).astype(np.uint32)           # one bit of the mask or all of them
+    status = noise | np.where(fa, bit(A), 0).astype(np.uint32) | np.where(fb, bit(B), 0).astype(np.uint32)
+    want_a, want_b = np.flatnonzero(fa).astype(np.uint32), np.flatnonzero(fb).astype(np.uint32)
+    got, none = _select(status, A)
+    assert np.array_equal(got, want_a) and none.size == 0
+    got_a, got_b = _select(status, A, B)                  # disjoint masks
+    assert np.array_equal(got_a, want_a) and np.array_equal(got_b, want_b)
+    got_a, got_b = _select(status, A | B, B)              # overlapping masks
+    assert np.array_equal(got_a, np.flatnonzero(fa | fb).astype(np.uint32)) and np.array_equal(got_b, want_b)
