@@ -807,6 +807,18 @@ int rb_debug_group(int device, const uint64_t *keys, const uint32_t *vals, size_
  * call, out_b may be NULL, counts[1] = 0).  out_a / out_b have room for n entries. */
 int rb_debug_select(int device, const uint32_t *status, size_t n, uint32_t mask_a, uint32_t mask_b, uint32_t *out_a, uint32_t *out_b,
                     uint32_t *counts);
+/* development / tests: the no-op prefilter (step 1 of an insert) and its hot-k-mer cache, for tests/test_gpu_prefilter.py.
+ * rb_debug_cache_export: the handle's cache table to the host as it stands.  which = 0: the minimizer-bucketed table (*log2 = log2 of the
+ * number of buckets, 16 words each; *m = minimizer length), 1: the hash-bucketed table (*log2 = log2 of the number of words, 8 per bucket;
+ * *m = 0).  out == NULL: geometry only (the size query); else cap_words >= the table's words.  Fails when the handle has no such table.
+ * rb_debug_prefilter: the window walk of an insert over words [first_word, first_word + n_words) of the batch — whole reads — as add_range
+ * would dispatch it now (same cache choice, same walker, the RB_FILTER_PIPE / RB_READ_LANES / RB_RAGGED_LANES / RB_NO_MPF switches as read on
+ * every call), forward or canonical hashing by the handle's strandedness, draws from (the handle's seed, ordinal0 + read - first read of the range,
+ * window start).  cnt_out / mask_out, n_words entries each: kept windows and their bit mask per word (the word a window starts in).  Nothing
+ * is inserted; filters, cache and op ordinal stay as they are.  Both calls are synchronous. */
+int rb_debug_cache_export(rb_graph *g, int which, uint64_t *out, size_t cap_words, uint32_t *log2, uint32_t *m);
+int rb_debug_prefilter(rb_graph *g, const rb_batch *b, int64_t first_word, int64_t n_words, uint64_t ordinal0, uint32_t pos_bits,
+                       uint32_t *cnt_out, uint32_t *mask_out);
 
 /* ---- the exchange driver below the C ABI (csrc/rb_comm.hip) ----
  * rb_shard_add_range = rnabloom/sharded.py::ShardRank.add_range in the library: all sub-batches of reads [first, first + n)

@@ -883,6 +883,79 @@ int rb_debug_select(int device, const uint32_t *status, size_t n, uint32_t mask_
         counts[0] = c[0]; counts[1] = c[1];
     });
 }
+}  // extern "C"
+namespace {
+// What add_range (rb_graph.hip) decides about step 1 before it launches it, restated for rb_debug_prefilter so that it runs the walker an insert runs
+// (tests/test_gpu_prefilter.py holds the two together: what the debug call keeps must be what an insert of the same reads sorts).
+// Is the prefilter on for this handle?  (RB_WIDE_PREFILTER=0 sends 32 <= k <= 64 down the unfiltered generic path)
+bool debug_prefilter_on(const rb_graph *g) {
+    const bool wide_off = getenv("RB_WIDE_PREFILTER") && atoi(getenv("RB_WIDE_PREFILTER")) == 0;
+    return g->npf_log2 && (g->k <= 31 || (g->k <= 64 && !wide_off));
+}
+// ... does a call over nw words of this batch use the minimizer-bucketed cache, not the hash-bucketed one?
+bool debug_prefilter_uses_mpf(const rb_graph *g, const rb_batch *b, int64_t nw) {
+    return g->mpf_log2b && !getenv("RB_NO_MPF") && (uint32_t)g->k >= g->mpf_m &&
+           (g->k <= RB_MPF_MAX_K ? (uint32_t)g->k - g->mpf_m + 1u <= RB_MPF_MAX_RING : filter_wide_mpf_ok(b, nw, g->k));
+}
+// ... and does the walker save its rolling state for the resuming emit pass?
+bool debug_prefilter_saves_state(const rb_graph *g, const rb_batch *b, int64_t nw, bool use_mpf) {
+    return g->k > RB_MPF_MAX_K ? (use_mpf && filter_saves_state_wide(b, nw, g->k)) : filter_saves_state(b, nw, g->k);
+}
+}  // namespace
+extern "C" {
+int rb_debug_cache_export(rb_graph *g, int which, uint64_t *out, size_t cap_words, uint32_t *log2_out, uint32_t *m_out) {
+    return guarded([&] {
+        RB_REQUIRE(g && log2_out && m_out, "rb_debug_cache_export: null argument");
+        RB_REQUIRE(which == 0 || which == 1, "rb_debug_cache_export: which must be 0 (minimizer-bucketed) or 1 (hash-bucketed)");
+        rb::WriteLock wl(g->rw);
+        RB_REQUIRE(which == 0 ? g->mpf_log2b != 0u : g->npf_log2 != 0u, "rb_debug_cache_export: this handle has no %s prefilter cache (k = %d)",
+                   which == 0 ? "minimizer-bucketed" : "hash-bucketed", g->k);
+        const size_t words = which == 0 ? (size_t)16 << g->mpf_log2b : (size_t)1 << g->npf_log2;
+        *log2_out = which == 0 ? g->mpf_log2b : g->npf_log2;
+        *m_out = which == 0 ? g->mpf_m : 0u;
+        if (!out) return;
+        RB_REQUIRE(cap_words >= words, "rb_debug_cache_export: the table has %zu words, the array has room for %zu", words, cap_words);
+        RB_HIP(hipSetDevice(g->p.device));
+        for (hipStream_t st : {(hipStream_t)g->stream, (hipStream_t)g->stream2}) RB_HIP(hipStreamSynchronize(st));
+        RB_HIP(hipMemcpy(out, which == 0 ? g->mpf.p : g->npf.p, words * 8, hipMemcpyDeviceToHost));
+    });
+}
+int rb_debug_prefilter(rb_graph *g, const rb_batch *b, int64_t first_word, int64_t n_words, uint64_t ordinal0, uint32_t pos_bits,
+                       uint32_t *cnt_out, uint32_t *mask_out) {
+    DevBuf cnt, mask, tot, ws;
+    return guarded([&] {
+        RB_REQUIRE(g && b && cnt_out && mask_out, "rb_debug_prefilter: null argument");
+        rb::WriteLock wl(g->rw);
+        RB_REQUIRE(!g->shard, "rb_debug_prefilter: not available on a shard handle");
+        RB_REQUIRE(b->device == g->p.device, "batch lives on device %d, graph on %d", b->device, g->p.device);
+        RB_REQUIRE(debug_prefilter_on(g), "rb_debug_prefilter: an insert into this handle runs no prefilter (k = %d)", g->k);
+        RB_REQUIRE(pos_bits >= 1u && pos_bits < 32u, "rb_debug_prefilter: pos_bits in 1..31");
+        // the words of whole reads, as the sub-batches of an insert are
+        const auto &wo = b->h_woff;
+        RB_REQUIRE(!wo.empty() && first_word >= 0 && n_words > 0 && first_word + n_words <= b->n_words, "rb_debug_prefilter: bad word range");
+        const int64_t r0 = std::lower_bound(wo.begin(), wo.end(), (uint32_t)first_word) - wo.begin();
+        const int64_t r1 = std::lower_bound(wo.begin(), wo.end(), (uint32_t)(first_word + n_words)) - wo.begin();
+        RB_REQUIRE(r0 < (int64_t)wo.size() && wo[(size_t)r0] == (uint32_t)first_word && r1 < (int64_t)wo.size() && wo[(size_t)r1] == (uint32_t)(first_word + n_words),
+                   "rb_debug_prefilter: the word range does not start and end at read boundaries");
+        RB_HIP(hipSetDevice(g->p.device));
+        hipStream_t s = g->stream;
+        const bool use_mpf = debug_prefilter_uses_mpf(g, b, n_words);
+        const Npf npf{reinterpret_cast<unsigned long long *>(g->npf.p), g->npf_log2};
+        const Mpf mpf{use_mpf ? reinterpret_cast<unsigned long long *>(g->mpf.p) : nullptr, g->mpf_log2b, g->mpf_m};
+        const size_t nb = (size_t)n_words * 4;
+        cnt.reserve(nb + 4); mask.reserve(nb + 4); tot.reserve(2048);
+        // (a word the walker does not decide would come back as this pattern)
+        RB_HIP(hipMemsetAsync(cnt.p, 0xEE, nb, s)); RB_HIP(hipMemsetAsync(mask.p, 0xEE, nb, s)); RB_HIP(hipMemsetAsync(tot.p, 0, 2048, s));
+        void *wstate = nullptr;
+        if (debug_prefilter_saves_state(g, b, n_words, use_mpf)) { ws.reserve(((size_t)n_words + 1) * 16); wstate = ws.p; }
+        launch_filter_windows(b, first_word, n_words, g->k, g->stranded ? 0 : 1, (uint32_t)r0, pos_bits, g->p.rng_seed, ordinal0, npf,
+                              cnt.as<uint32_t>(), mask.as<uint32_t>(), tot.as<uint32_t>(), s, OwnRange{Mod{1, 0, 0}, 0, 0}, mpf, wstate);
+        RB_HIP(hipGetLastError());
+        RB_HIP(hipStreamSynchronize(s));
+        RB_HIP(hipMemcpy(cnt_out, cnt.p, nb, hipMemcpyDeviceToHost));
+        RB_HIP(hipMemcpy(mask_out, mask.p, nb, hipMemcpyDeviceToHost));
+    });
+}
 int rb_filter_size(rb_graph *g, int which, int64_t *size, int64_t *nbytes, int *num_hash) {
     if (!g) { set_error("null graph"); return RB_ERR_INVALID; }
     if (which == RB_CBF) {

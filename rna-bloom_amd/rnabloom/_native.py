@@ -192,6 +192,8 @@ SYMBOLS = [
     ("rb_debug_group", _i32, [_i32, _vp, _vp, _sz, _i32, _i32, C.c_uint, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_debug_select", _i32, [_i32, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    ("rb_debug_cache_export", _i32, [_vp, _i32, _vp, _sz, C.POINTER(_u32), C.POINTER(_u32)]),
+    ("rb_debug_prefilter", _i32, [_vp, _vp, _i64, _i64, _u64, _u32, _vp, _vp]),
     ("rb_graph_profile_enable", _i32, [_vp, _i32]),
     ("rb_graph_profile_get", _i32, [_vp, C.POINTER(Profile), _i32]),
 ]
