@@ -406,6 +406,47 @@ typedef struct rb_overlap_rec {         /* 32 bytes */
 } rb_overlap_rec;
 int rb_graph_overlap_pairs(rb_graph *g, const char *lseq, const int64_t *loffsets, const char *rseq, const int64_t *roffsets, int64_t n,
                            int min_overlap, float min_kmer_cov, int64_t *out_offsets, char *out_seq, rb_overlap_rec *recs);
+/* Paired-k-mer branch extension of host sequences — GraphUtils.extendRightSE / extendLeftSE (R/util/GraphUtils.java:6018-6204), the step the
+ * transcript assembler's extendSE loop (:6454-6565, R/RNABloom.java:1850) and join (:978, :1106) take across a branch.  A wavefront per sequence
+ * on the device; the call is read-only.  Sequence i is seq[offsets[i], offsets[i+1]) in its natural orientation with the floor min_kmer_cov[i];
+ * its k-mer list is getKmers(String)'s (a letter outside ACGTU hashes as in rb_graph_kmers).  direction 0: extendRightSE over that list;
+ * direction 1: extendLeftSE over the list reversed, as the reference's callers reverse it.  d = the read-paired k-mer distance, n = the
+ * number of k-mers; only the last min(n, d) k-mers of the list are read.
+ *   Candidates: the successors (direction 1: predecessors) of the last k-mer with graph.getCount >= 1 in the order A C G T (the two-argument
+ *   getSuccessors, R/graph/Kmer.java:228-230: not the floor).  None: NONE, WHY_NO_CANDIDATE.  One: SINGLE — the candidate followed by
+ *   naiveExtend{Right,Left}NoBackChecks(candidate, bound d - 2, floor) (:6888-6933, :7067-7112: rb_graph_naive_extend mode 2), unscored and
+ *   untrimmed (:6030-6035).
+ *   First level (:6043-6066): per candidate the same walk, then countKmerPairsSE / countKmerPairsReversedSE (:5718-5790) with gap 0: walked k-mer
+ *   i (0 <= i <= min(d - 1, size - 1)) is looked up with the list's k-mer n - d + i where that index is not negative — lookupReadKmerPair of
+ *   Kmer.getKmerPairHashValue, the list's k-mer on the left for direction 0 and on the right for direction 1 (rb_graph_paired_kmer_segments'
+ *   key).  pairs = supported k-mers, last = the largest supported i.  A supported extension scores Math.min(pathMinCov, median) * pairs /
+ *   (last + 1) in float32 (a product, then a quotient), pathMinCov = the minimum count of the last min(n, d) k-mers, median =
+ *   getMedianKmerCoverage(Collection) of the whole extension (:229-247).  The best is kept on score > best || (score == best && median >
+ *   bestMedian), from 0 / 0, trimmed to last + 1 k-mers.
+ *   Second level (:6067-6106): an unsupported first stretch of gap k-mers, gap < d - 1, is extended by every successor (count >= 1) of its last
+ *   k-mer and that k-mer's walk with bound d - gap; first stretch + extension is counted and scored the same way and competes for the same best.
+ *   A walk's own stop (:6919): the only neighbour equals the k-mer the walk started from or the k-mer added last.  maxTipLength does not
+ *   appear (see rb_graph_naive_extend).  A last k-mer with a letter outside ACGTU: NONE, WHY_INVALID_SEED, as the walks treat such a seed.
+ *   Output: recs[i]; out_bases[i * (d + 2) ..] the out_len bases the returned k-mers add, in walking order as rb_graph_walk (direction 0: the
+ *   last base of each k-mer, direction 1: the first), upper-case A C G T, zeros behind them; out_count (may be NULL) their graph.getCount.
+ *   winner: the first-level candidate's base 0..3, for SECOND the second-level candidate's base in bits 4..5; -1 for NONE.  pairs,
+ *   last_partnered, score: the winner's (0, -1, 0 for NONE and SINGLE).
+ * The call works in pieces through the shared driver (RB_QUERY_PIECE k-mers of the sequences' last d + k - 1 letters); results do not depend
+ * on the cuts.  Device scratch of a piece: 20 bytes per such k-mer, 36 + (d + 2) * 5 per sequence, and for d > 256 (the walks' rows do not fit
+ * LDS) about 25 d bytes for each of at most 4096 wavefronts.  It leases a query context (re-entrant on one handle).  With rb_graph_profile_enable
+ * on the kernels' device time is added to the profile entry "extend_se".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf, counting filter or read-pair filter (or a
+ * graph made without one); d < 2; a direction other than 0 / 1; n < 0; with n > 0: a null offsets / min_kmer_cov / out_bases / recs, a null seq
+ * where there is text, decreasing offsets, a floor that is not finite or is negative.  n == 0 succeeds and touches nothing. */
+enum { RB_EXT_NONE = 0, RB_EXT_SINGLE = 1, RB_EXT_FIRST = 2, RB_EXT_SECOND = 3 };                                             /* rb_extend_rec.outcome */
+enum { RB_EXT_WHY_FOUND = 0, RB_EXT_WHY_NO_CANDIDATE = 1, RB_EXT_WHY_NO_SUPPORT = 2, RB_EXT_WHY_INVALID_SEED = 3, RB_EXT_WHY_SHORT = 4 };  /* rb_extend_rec.why */
+typedef struct rb_extend_rec {          /* 32 bytes */
+    int32_t outcome, why;
+    int32_t n_candidates, out_len /* k-mers */, pairs, last_partnered, winner;
+    float score;
+} rb_extend_rec;
+int rb_graph_extend_se(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
+                       char *out_bases /* n * (d + 2) */, float *out_count /* n * (d + 2), may be NULL */, rb_extend_rec *recs);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

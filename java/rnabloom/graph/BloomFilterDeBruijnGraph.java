@@ -508,6 +508,34 @@ public class BloomFilterDeBruijnGraph {
         return res;
     }
 
+    /**
+     * GraphUtils.extendRightSE (direction 0) / extendLeftSE (direction 1) (src/rnabloom/util/GraphUtils.java:6018-6204) for a batch of sequences in ONE
+     * native call: the candidates' naive walks, the read-paired k-mer look-ups and the scores run on the device, a wavefront per sequence, and
+     * nothing is written to the graph.  seqs are in their natural orientation, minKmerCov holds one floor per sequence.  Returns, per sequence,
+     * the bases the reference's returned k-mers add, in walking order (direction 1: nearest to the sequence first), or null where the reference
+     * returns null.  recs (optional, 8 * seqs.length ints) receives the records of NativeGraph.extendSE.
+     */
+    public String[] extendStepSE(String[] seqs, int direction, float[] minKmerCov, int[] recs) {
+        final int n = seqs.length;
+        if (minKmerCov.length != n) throw new IllegalArgumentException("extendStepSE: " + n + " sequences and " + minKmerCov.length + " floors");
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("extendStepSE: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        final int stride = Math.max(getReadPairedKmerDistance(), 0) + 2;
+        if ((long) n * stride > Integer.MAX_VALUE || 8L * n > Integer.MAX_VALUE)
+            throw new IllegalArgumentException("extendStepSE: " + n + " sequences of " + stride + " output bases do not fit one array: smaller batches");
+        if (recs != null && recs.length < 8 * n) throw new IllegalArgumentException("extendStepSE: recs holds " + recs.length + " ints, " + 8 * n + " are needed");
+        final byte[] bases = new byte[Math.max(n * stride, 1)];
+        final int[] rec = recs != null ? recs : new int[8 * n];
+        NativeGraph.extendSE(handle, text, off, n, direction, minKmerCov, bases, null, rec);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = rec[8 * i] != 0 ? new String(bases, i * stride, rec[8 * i + 3], java.nio.charset.StandardCharsets.ISO_8859_1) : null;
+        return res;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

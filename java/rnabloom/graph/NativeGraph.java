@@ -127,6 +127,15 @@ public final class NativeGraph {
      *  outOffsets[i].  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
     public static native int overlapPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int minOverlap,
                                           float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] recs);
+    /** Paired-k-mer branch extension of n sequences (rb_graph_extend_se; GraphUtils.extendRightSE / extendLeftSE, R/util/GraphUtils.java:6018-6204):
+     *  sequence i is seq[offsets[i], offsets[i + 1]) in its natural orientation with the floor minKmerCov[i]; direction 0 extends to the right,
+     *  1 to the left.  recs holds 8 ints per sequence — outcome (0 none: the reference returns null, 1 the only candidate and its walk, 2 a
+     *  first-level winner, 3 a second-level winner), why (0 found, 1 no candidate, 2 no candidate was supported, 3 the last k-mer holds a letter
+     *  outside ACGTU, 4 shorter than k), candidates, k-mers returned, supporting pairs, last partnered k-mer, winner (candidate base, second base in
+     *  bits 4..5), Float.floatToRawIntBits(score) — and the bases the returned k-mers add are recs[8 i + 3] bytes at outBases + i * (d + 2), in
+     *  walking order; outCount (may be null) their counts.  Read-only. */
+    public static native void extendSE(long h, ByteBuffer seq, long[] offsets, int n, int direction, float[] minKmerCov, byte[] outBases,
+                                       float[] outCount, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

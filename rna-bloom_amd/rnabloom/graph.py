@@ -598,6 +598,37 @@ class BloomFilterDeBruijnGraph:
         return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes() if rc["outcome"] != self.OVL_NONE else None, int(rc["outcome"]),
                  bool(rc["flags"] & self.OVL_SWAPPED)) for i, rc in enumerate(recs)]
 
+    EXT_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("n_candidates", "<i4"), ("out_len", "<i4"), ("pairs", "<i4"),
+                          ("last_partnered", "<i4"), ("winner", "<i4"), ("score", "<f4")])
+    EXT_OUTCOMES = ("none", "single", "first", "second")
+    EXT_WHYS = ("found", "no_candidate", "no_support", "invalid_seed", "short")
+    EXT_NONE, EXT_SINGLE, EXT_FIRST, EXT_SECOND = range(4)
+
+    def extendStepSEFlat(self, seq, offsets, direction, minKmerCov, counts=False):
+        """rb_graph_extend_se on flat host text (GraphUtils.extendRightSE / extendLeftSE, R/util/GraphUtils.java:6018-6204): sequence i is
+        seq[offsets[i]:offsets[i + 1]] (uint8) in its natural orientation, minKmerCov one floor per sequence (a scalar is used for all).
+        Returns (bases[n, d + 2], recs, count[n, d + 2] or None): one EXT_DTYPE record per sequence, the bases the returned k-mers add in
+        walking order at bases[i, :recs[i]["out_len"]]."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        floors = np.ascontiguousarray(np.broadcast_to(np.asarray(minKmerCov, np.float32), (n,)))
+        width = max(self.getReadPairedKmerDistance(), 0) + 2
+        bases = np.zeros((n, width), np.uint8)
+        cnt = np.zeros((n, width), np.float32) if counts else None
+        recs = np.zeros(n, self.EXT_DTYPE)
+        check(lib.rb_graph_extend_se(self.h, _ptr(seq), _ptr(off), n, direction, _ptr(floors), _ptr(bases), _ptr(cnt), _ptr(recs)))
+        return bases, recs, cnt
+
+    def extendStepSE(self, seqs, direction, minKmerCov):
+        """GraphUtils.extendRightSE (direction 0) / extendLeftSE (direction 1) of each sequence's getKmers list, with that sequence's own
+        floor: (extensions, recs) — per sequence the bases the returned k-mers add, in walking order (for direction 1 nearest to the
+        sequence first), or None where the reference returns null; recs is the EXT_DTYPE record array."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        bases, recs, _ = self.extendStepSEFlat(seq, off, direction, minKmerCov)
+        return [bases[i, :rc["out_len"]].tobytes() if rc["outcome"] != self.EXT_NONE else None for i, rc in enumerate(recs)], recs
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and

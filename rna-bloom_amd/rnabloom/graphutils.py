@@ -183,3 +183,79 @@ def getKmersMinCoverage(graph, seqs, minCoverage):
         s, n = best if best is not None else first
         out.append((s, n, cnt[s:s + n].copy()))
     return out
+
+
+def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
+    """GraphUtils.extendSE(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6454-6565) for many sequences: first to the left,
+    then to the right, each sequence is extended across branches by extendLeftSE / extendRightSE until the step returns nothing at the
+    lowest floor or only k-mers the sequence already holds (usedKmers + hasDuplicatedKmerPair, :6416-6452).  The step runs on the device,
+    ONE graph.extendStepSE call per round for all sequences still growing, each with its own floor max(minKmerCov, min count of its last d
+    k-mers * 0.1), lowered by a further * 0.1 while the step returns nothing; the counts come from graph.getKmers of the sequences' ends.
+    Returns (extended sequences, [leftExtLen, leftExtLen + origLen] per sequence, in k-mers).  The reference's loop has no bound;
+    max_rounds raises instead of looping forever."""
+    F = np.float32
+    d, k = graph.getReadPairedKmerDistance(), graph.k
+    floor = F(minKmerCov)
+    texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    n0 = [max(len(t) - k + 1, 0) for t in texts]
+    kmers = [[t[i:i + k] for i in range(n)] for t, n in zip(texts, n0)]
+    used = [set(km) for km in kmers]
+    left = [0] * len(texts)
+    for direction in (1, 0):
+        if direction:
+            for km in kmers:
+                km.reverse()                                                                        # :6465
+        active = [i for i, n in enumerate(n0) if n > 0]
+        thr, rounds = {}, 0
+        while active:
+            rounds += 1
+            if rounds > max_rounds:
+                raise RuntimeError("extendSE: %d sequences still grow after %d rounds" % (len(active), max_rounds))
+            fresh = [i for i in active if i not in thr]
+            if fresh:                                                                               # :6468 / :6519 and the first :6473
+                ko, _, _, c = graph.getKmers([texts[i][:d + k - 1] if direction else texts[i][-(d + k - 1):] for i in fresh])
+                for j, i in enumerate(fresh):
+                    thr[i] = max(floor, F(F(c[int(ko[j]):int(ko[j + 1])].min()) * F(0.1)))
+            ext, _ = graph.extendStepSE([texts[i] for i in active], direction, np.array([thr[i] for i in active], F))
+            nxt = []
+            for i, e in zip(active, ext):
+                if not e:
+                    if thr[i] != floor:                                                             # :6477: lower the floor and ask again
+                        thr[i] = max(floor, F(thr[i] * F(0.1)))
+                        nxt.append(i)
+                    continue
+                t, km = texts[i], kmers[i]
+                new = e[::-1] + t if direction else t + e
+                ek = [new[len(e) - 1 - j:len(e) - 1 - j + k] for j in range(len(e))] if direction else [new[len(t) - k + 1 + j:len(t) + 1 + j] for j in range(len(e))]
+                is_used = all(x in used[i] for x in ek)                                             # :6486-6504
+                end_index = max(0, len(km) - d + len(ek))
+                j = len(km) - 1
+                while j >= end_index and is_used:
+                    is_used = km[j] in used[i]
+                    j -= 1
+                if is_used and (len(km) < d or _has_duplicated_kmer_pair(km, ek[-1], d, len(km) - 1 - d + len(ek))):
+                    continue                                                                        # :6506-6508
+                km += ek
+                used[i].update(ek)
+                texts[i] = new
+                del thr[i]
+                nxt.append(i)
+            active = nxt
+        if direction:
+            for i, km in enumerate(kmers):
+                left[i] = len(km) - n0[i]                                                           # :6514
+                km.reverse()
+    return texts, [[l, l + n] for l, n in zip(left, n0)]
+
+
+def _has_duplicated_kmer_pair(kmers, cursor, d, mate_index):
+    """GraphUtils.hasDuplicatedKmerPair (R/util/GraphUtils.java:6416-6452)"""
+    if mate_index < 0:
+        return False
+    mate = kmers[mate_index]
+    idx = [i for i, km in enumerate(kmers) if km == cursor]
+    if not idx or idx[-1] - d < 0:
+        return False
+    if mate == kmers[idx[-1] - d]:
+        return True
+    return any(i - d >= 0 and mate == kmers[i - d] for i in idx[:-1])
