@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_lookup.hpp"
 
 using namespace rb;
 
@@ -34,114 +35,40 @@ constexpr size_t WALK_CHUNK_BYTES = (size_t)256 << 20;      // device scratch of
 
 static_assert(sizeof(rb_corr_gap) == 20, "rb_corr_gap is 20 bytes");
 
-__device__ __forceinline__ uint32_t ce_code(uint32_t ch) {
-    switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;
-                  case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
-}
-__device__ __forceinline__ uint8_t ce_acgt(uint32_t code) { return (uint8_t)(code == 0u ? 'A' : code == 1u ? 'C' : code == 2u ? 'G' : 'T'); }
 // a base as the walk kernels write it: upper case, U as T (the letters of a good k-mer are all of ACGTU)
-__device__ __forceinline__ uint8_t ce_norm(uint32_t ch) { const uint32_t c = ce_code(ch); return c < 4u ? ce_acgt(c) : (uint8_t)ch; }
-// rotation by a run-time amount out of 32-bit funnel shifts (no 64-bit shift with a vector amount: tools/check_shift_last.py)
-__device__ __forceinline__ uint64_t ce_rot(uint64_t v, uint32_t s) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    if (s & 32u) { const uint32_t t = lo; lo = hi; hi = t; }
-    const uint32_t t = s & 31u;
-    const uint32_t nh = t ? __builtin_amdgcn_alignbit(hi, lo, 32u - t) : hi;
-    const uint32_t nl = t ? __builtin_amdgcn_alignbit(lo, hi, 32u - t) : lo;
-    return ((uint64_t)nh << 32) | nl;
-}
-// seeds of a raw letter as getKmers(String) hashes it (rb_mismatch.hip mm_seeds_of_char; NTHash.java:30, 133-166)
-__device__ __forceinline__ void ce_seeds_of_char(uint32_t ch, uint64_t &s, uint64_t &sc) {
-    const uint32_t code = ce_code(ch);
-    s = code < 4u ? seed_of(code) : 0ull;
-    const uint32_t cls = ch & 7u;
-    const uint32_t rc = cls == 1u ? 0u : cls == 3u ? 1u : cls == 7u ? 2u : 3u;
-    sc = ((0xBAu >> cls) & 1u) ? seed_of(3u - rc) : 0ull;
-}
-__device__ __forceinline__ uint32_t ce_alt_mask(uint32_t ch) {       // SeqUtils.getAltNucleotides(byte) :130-145 as a mask over A C G T
-    switch (ch) { case 'A': return 0xEu; case 'C': return 0xDu; case 'G': return 0xBu; case 'T': case 'U': return 0x7u; default: return 0xFu; }
-}
+__device__ __forceinline__ uint8_t ce_norm(uint32_t ch) { const uint32_t c = letter_code(ch); return c < 4u ? code_letter(c) : (uint8_t)ch; }
 __device__ __forceinline__ bool ce_contains(const FilterView &fv, uint64_t h0) { return bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h0); }
-__device__ __forceinline__ float ce_count(const FilterView &fv, uint64_t h0) {      // BloomFilterDeBruijnGraph.getCount :562-570
-    if (!ce_contains(fv, h0)) return 0.0f;
-    uint32_t mn = fv.cbf[index_of(h0, fv.cbf_mod)];
-    for (int j = 1; j < fv.cbf_h; ++j) mn = min(mn, (uint32_t)fv.cbf[index_of(multi_hash(h0, (uint32_t)j, fv.kmul), fv.cbf_mod)]);
-    return minifloat_to_float(mn) + 1.0f;
-}
-// the counts of four k-mers at once: with two hash functions per filter the 8 Bloom-bit loads and the 8 counter loads are issued before any is consumed
-__device__ __forceinline__ void ce_count4(const FilterView &fv, const uint64_t (&h)[4], float (&c)[4]) {
-    if (fv.dbg_h == 2 && fv.cbf_h == 2) {
-        uint64_t bi[4][2], ci[4][2];
-        uint32_t bw[4][2], cb[4][2];
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) {
-            const uint64_t h1 = multi_hash(h[a], 1u, fv.kmul);
-            bi[a][0] = index_of(h[a], fv.dbg_mod); bi[a][1] = index_of(h1, fv.dbg_mod);
-            ci[a][0] = index_of(h[a], fv.cbf_mod); ci[a][1] = index_of(h1, fv.cbf_mod);
-        }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) { bw[a][0] = fv.dbg[bi[a][0] >> 5]; bw[a][1] = fv.dbg[bi[a][1] >> 5]; }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) { cb[a][0] = fv.cbf[ci[a][0]]; cb[a][1] = fv.cbf[ci[a][1]]; }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) {
-            const uint32_t in = (bw[a][0] >> (uint32_t)(bi[a][0] & 31u)) & (bw[a][1] >> (uint32_t)(bi[a][1] & 31u)) & 1u;
-            const uint32_t mn = cb[a][0] < cb[a][1] ? cb[a][0] : cb[a][1];
-            c[a] = in ? minifloat_to_float(mn) + 1.0f : 0.0f;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) c[a] = ce_count(fv, h[a]);
-    }
-}
-
 // Kmer.getLeftVariants / getRightVariants(k, numHash, graph, minKmerCov) (R/graph/Kmer.java:361-405, CanonicalKmer.java:387-) of the k-mer with
 // getKmers hashes (f, r): is any alternative of the base ch (side 2: the first base, 3: the last) a k-mer with count >= min_cov?  The hashes are
 // rb_graph_neighbors' (direction 2 / 3); lanes 0..3 take a substitution each.
 __device__ __forceinline__ bool ce_has_variants(const FilterView &fv, int stranded, uint32_t uk, int side, uint64_t f, uint64_t r, uint32_t ch,
                                                 float min_cov, uint32_t lane) {
-    const uint32_t a = lane & 3u, oc = ce_code(ch);
+    const uint32_t a = lane & 3u, oc = letter_code(ch);
     const uint64_t s_out = oc < 4u ? seed_of(oc) : 0ull, sc_out = oc < 4u ? seed_of(3u - oc) : 0ull;
     uint64_t nf, nr;
-    if (side == 2) { nf = f ^ ce_rot(s_out, uk - 1u) ^ ce_rot(seed_of(a), uk - 1u); nr = r ^ sc_out ^ seed_of(3u - a); }
-    else { nf = f ^ s_out ^ seed_of(a); nr = r ^ ce_rot(sc_out, uk - 1u) ^ ce_rot(seed_of(3u - a), uk - 1u); }
+    if (side == 2) { nf = f ^ rotl_var(s_out, uk - 1u) ^ rotl_var(seed_of(a), uk - 1u); nr = r ^ sc_out ^ seed_of(3u - a); }
+    else { nf = f ^ s_out ^ seed_of(a); nr = r ^ rotl_var(sc_out, uk - 1u) ^ rotl_var(seed_of(3u - a), uk - 1u); }
     bool ok = false;
-    if (lane < 4u && ((ce_alt_mask(ch) >> a) & 1u)) ok = ce_count(fv, stranded ? nf : smin(nf, nr)) >= min_cov;
+    if (lane < 4u && ((alt_mask(ch) >> a) & 1u)) ok = graph_count(fv, stranded ? nf : smin(nf, nr)) >= min_cov;
     return __ballot(ok) != 0ull;
 }
 // Kmer.hasSuccessors (direction 0, ch = the first base) / hasPredecessors (1, ch = the last base) (R/graph/Kmer.java:97-125): graph.contains of
 // any of the four neighbours, hashed as rb_graph_neighbors hashes them
 __device__ __forceinline__ bool ce_has_neighbors(const FilterView &fv, int stranded, uint32_t uk, int direction, uint64_t f, uint64_t r, uint32_t ch,
                                                  uint32_t lane) {
-    const uint32_t a = lane & 3u, oc = ce_code(ch);
+    const uint32_t a = lane & 3u, oc = letter_code(ch);
     const uint64_t s_out = oc < 4u ? seed_of(oc) : 0ull, sc_out = oc < 4u ? seed_of(3u - oc) : 0ull;
     uint64_t nf, nr;
-    if (direction == 0) { nf = rotl1(f) ^ ce_rot(s_out, uk) ^ seed_of(a); nr = rotr1(r) ^ rotr1(sc_out) ^ ce_rot(seed_of(3u - a), uk - 1u); }
-    else { nf = rotr1(f) ^ rotr1(s_out) ^ ce_rot(seed_of(a), uk - 1u); nr = rotl1(r) ^ ce_rot(sc_out, uk) ^ seed_of(3u - a); }
+    if (direction == 0) { nf = rotl1(f) ^ rotl_var(s_out, uk) ^ seed_of(a); nr = rotr1(r) ^ rotr1(sc_out) ^ rotl_var(seed_of(3u - a), uk - 1u); }
+    else { nf = rotr1(f) ^ rotr1(s_out) ^ rotl_var(seed_of(a), uk - 1u); nr = rotl1(r) ^ rotl_var(sc_out, uk) ^ seed_of(3u - a); }
     bool ok = false;
     if (lane < 4u) ok = ce_contains(fv, stranded ? nf : smin(nf, nr));
     return __ballot(ok) != 0ull;
 }
 
-// Common.getMedian (R/util/Common.java:41-50) of n counts get(0 .. n-1), by the whole wavefront: an order statistic is found by bisection over the
-// 129 count codes (count_code_of), one ballot per 64 counts and step
-template <class GET> __device__ __forceinline__ uint32_t ce_kth(GET get, int n, int rank, uint32_t lane) {
-    uint32_t lo = 0, hi = 128;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        int cnt = 0;
-        for (int p0 = 0; p0 < n; p0 += 64) {
-            const int p = p0 + (int)lane;
-            cnt += __popcll(__ballot(p < n && count_code_of(get(p)) <= mid));
-        }
-        if (cnt >= rank + 1) hi = mid; else lo = mid + 1u;
-    }
-    return lo;
-}
+// Common.getMedian (R/util/Common.java:41-50) of the n counts get(0 .. n-1), by the whole wavefront
 template <class GET> __device__ __forceinline__ float ce_median(GET get, int n, uint32_t lane) {
-    const float hi = count_code_value(ce_kth(get, n, n / 2, lane));
-    if (n & 1) return hi;
-    return (count_code_value(ce_kth(get, n, n / 2 - 1, lane)) + hi) / 2.0f;
+    return median_code([&](int p) { return count_code_of(get(p)); }, n, lane);
 }
 
 // SeqUtils.getDistance(String, String) (R/util/SeqUtils.java:190-229) by the whole wavefront.  The reference's System.arraycopy(v1, 0, v0, 0, tLen)
@@ -331,7 +258,7 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_edge(FilterView fv, int stra
 
 // ---- SNV bubbles (:3782-3818): a wavefront per gap of exactly k k-mers.  The candidates are the k + 2 windows of left + n + right, 2k + 1 letters:
 // left = the first bad k-mer, right = the last one (the base they share stands twice).  Lane w hashes window w once without n (ntHash is XOR-linear,
-// so n's seed is added afterwards), probes the four candidates together (ce_count4) and parks the counts in LDS; minimum and median per candidate
+// so n's seed is added afterwards), probes the four candidates together (count_lookup4) and parks the counts in LDS; minimum and median per candidate
 // are wavefront reductions.  bestCov starts at Float.MIN_VALUE: medians are multiples of 0.5, so `median > bestCov` is `median > 0` at first.
 __global__ void __launch_bounds__(CE_TPB) k_resolve_snv(FilterView fv, int stranded, int k, CorrView v, const int32_t *__restrict__ list, int64_t n,
                                                         float min_cov) {
@@ -350,8 +277,8 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_snv(FilterView fv, int stran
         for (int q = 0; q < k; ++q) {
             const int xf = win + q, xr = win + k - 1 - q;
             uint32_t cf = 4u, cr = 4u;
-            if (xf != k) { cf = ce_code(S(xf)); ok = ok && cf < 4u; }
-            if (xr != k) cr = ce_code(S(xr));
+            if (xf != k) { cf = letter_code(S(xf)); ok = ok && cf < 4u; }
+            if (xr != k) cr = letter_code(S(xr));
             f = rotl1(f) ^ (cf < 4u ? seed_of(cf) : 0ull);
             r = rotl1(r) ^ (cr < 4u ? seed_of(3u - cr) : 0ull);     // Horner from the last base: r = XOR rotl(seed(comp(b_q)), q)
         }
@@ -360,11 +287,11 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_snv(FilterView fv, int stran
         float c[4];
 #pragma unroll
         for (uint32_t a = 0; a < 4u; ++a) {
-            const uint64_t nf = has_n ? f ^ ce_rot(seed_of(a), (uint32_t)(win - 1)) : f;
-            const uint64_t nr = has_n ? r ^ ce_rot(seed_of(3u - a), (uint32_t)(k - win)) : r;
+            const uint64_t nf = has_n ? f ^ rotl_var(seed_of(a), (uint32_t)(win - 1)) : f;
+            const uint64_t nr = has_n ? r ^ rotl_var(seed_of(3u - a), (uint32_t)(k - win)) : r;
             h[a] = stranded ? nf : canonical(nf, nr);
         }
-        ce_count4(fv, h, c);
+        count_lookup4(fv, h, [&](uint32_t a, bool in, uint32_t mn) { c[a] = in ? minifloat_to_float(mn) + 1.0f : 0.0f; });
 #pragma unroll
         for (int a = 0; a < 4; ++a) s_c[wv][a][win] = ok ? c[a] : 0.0f;
     }
@@ -381,7 +308,7 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_snv(FilterView fv, int stran
     }
     if (besta >= 0 && best >= min_cov) {
         uint8_t *rp = v.pool + v.rof[gi];                           // the last letters of the k + 2 k-mers
-        for (int x = (int)lane; x < nw; x += 64) rp[x] = x == 1 ? ce_acgt((uint32_t)besta) : x == 0 ? tx[k - 1] : tx[k - 1 + (x - 2)];
+        for (int x = (int)lane; x < nw; x += 64) rp[x] = x == 1 ? code_letter((uint32_t)besta) : x == 0 ? tx[k - 1] : tx[k - 1 + (x - 2)];
         if (lane == 0) { v.recs[gi].outcome = RB_GAP_REPLACED; v.recs[gi].repl_len = nw; }
     }
 }
@@ -392,10 +319,10 @@ template <class GET> __device__ bool ce_low_complexity(GET get, int k, uint32_t 
     if (k < 3) return false;
     const int t1 = min(32767, (int)floorf((float)k * 0.95f + 0.5f)), t2 = min(32767, (int)floorf((float)(k / 2) * 0.95f + 0.5f)),
               t3 = min(32767, (int)floorf((float)(k / 3) * 0.95f + 0.5f));
-    uint32_t c3 = ce_code(get(0)) & 3u, c2 = ce_code(get(1)) & 3u, c1 = ce_code(get(2)) & 3u;
+    uint32_t c3 = letter_code(get(0)) & 3u, c2 = letter_code(get(1)) & 3u, c1 = letter_code(get(2)) & 3u;
     int n1 = (lane == c3) + (lane == c2) + (lane == c1), n2 = (lane == c3 * 4u + c2) + (lane == c2 * 4u + c1), n3 = lane == c3 * 16u + c2 * 4u + c1;
     for (int q = 3; q < k; ++q) {
-        c3 = c2; c2 = c1; c1 = ce_code(get(q)) & 3u;
+        c3 = c2; c2 = c1; c1 = letter_code(get(q)) & 3u;
         bool hit = false;
         if (lane == c1) hit = ++n1 >= t1;
         if (lane == c2 * 4u + c1) hit = hit || ++n2 >= t2;
@@ -443,7 +370,7 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_path(int k, CorrView v, cons
                     const int xx = x0 + (int)__builtin_ctzll(mm);
                     mm &= mm - 1ull;
                     bool ne = false;
-                    for (int q = (int)lane; q < k; q += 64) ne = ne || ce_code(sl[xx + 1 + q]) != ce_code(sr[j + k - q]);
+                    for (int q = (int)lane; q < k; q += 64) ne = ne || letter_code(sl[xx + 1 + q]) != letter_code(sr[j + k - q]);
                     if (!__ballot(ne)) { hit = j; idx = xx; }
                 }
             }
@@ -523,7 +450,7 @@ __global__ void __launch_bounds__(CE_TPB) k_text_kmers(FilterView fv, int strand
     uint32_t *vw = valid + cwoff[r];
     for (int32_t wd = (int32_t)lane; wd * 32 < L; wd += 64) {
         uint32_t bits = 0;
-        for (int32_t b = 0; b < 32 && wd * 32 + b < L; ++b) bits |= (ce_code(tx[wd * 32 + b]) < 4u ? 1u : 0u) << b;
+        for (int32_t b = 0; b < 32 && wd * 32 + b < L; ++b) bits |= (letter_code(tx[wd * 32 + b]) < 4u ? 1u : 0u) << b;
         vw[wd] = bits;
     }
     uint64_t *f_ = F + ckof[r], *r_ = R + ckof[r];
@@ -532,9 +459,7 @@ __global__ void __launch_bounds__(CE_TPB) k_text_kmers(FilterView fv, int strand
         uint64_t f = 0, rv = 0;
         int32_t run = 0;
         for (int32_t q = 0; q < k; ++q) {
-            uint64_t s, sc, unused;
-            ce_seeds_of_char(tx[p0 + q], s, unused);
-            ce_seeds_of_char(tx[p0 + k - 1 - q], unused, sc);
+            const uint64_t s = letter_seed(tx[p0 + q]), sc = letter_rev_seed(tx[p0 + k - 1 - q]);
             run = s ? run + 1 : 0;
             f = rotl1(f) ^ s;
             rv = rotl1(rv) ^ sc;                                    // Horner from the window's last base
@@ -542,16 +467,15 @@ __global__ void __launch_bounds__(CE_TPB) k_text_kmers(FilterView fv, int strand
         const int32_t pe = min(nk, p0 + 32);
         for (int32_t p = p0; p < pe; ++p) {
             if (p > p0) {
-                uint64_t s_out, sc_out, s_in, sc_in;
-                ce_seeds_of_char(tx[p - 1], s_out, sc_out);
-                ce_seeds_of_char(tx[p + k - 1], s_in, sc_in);
+                const uint64_t s_out = letter_seed(tx[p - 1]), sc_out = letter_rev_seed(tx[p - 1]);
+                const uint64_t s_in = letter_seed(tx[p + k - 1]), sc_in = letter_rev_seed(tx[p + k - 1]);
                 run = s_in ? run + 1 : 0;
-                f = rotl1(f) ^ ce_rot(s_out, uk) ^ s_in;
-                rv = rotr1(rv) ^ rotr1(sc_out) ^ ce_rot(sc_in, uk - 1u);
+                f = rotl1(f) ^ rotl_var(s_out, uk) ^ s_in;
+                rv = rotr1(rv) ^ rotr1(sc_out) ^ rotl_var(sc_in, uk - 1u);
             }
             f_[p] = f;
             r_[p] = stranded ? 0ull : rv;
-            c_[p] = run >= k ? ce_count(fv, stranded ? f : canonical(f, rv)) : 0.0f;
+                        c_[p] = run >= k ? graph_count(fv, stranded ? f : canonical(f, rv)) : 0.0f;
         }
     }
 }

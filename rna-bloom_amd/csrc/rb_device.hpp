@@ -37,7 +37,56 @@ __device__ __forceinline__ uint64_t rotr(uint64_t v, uint32_t s) {
     s &= 63u;
     return (v >> s) | (v << ((64u - s) & 63u));
 }
+// rotation to the left by a RUN-TIME amount (any s; s & 63 counts) out of 32-bit funnel shifts: a 64-bit shift whose amount is a vector register can
+// end up with that amount in the wavefront's last VGPR, which gfx950 gets wrong now and then (profiles/r05_miscompile.md, tools/check_shift_last.py)
+__device__ __forceinline__ uint64_t rotl_var(uint64_t v, uint32_t s) {
+    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    if (s & 32u) { const uint32_t t = lo; lo = hi; hi = t; }
+    const uint32_t t = s & 31u;
+    const uint32_t nh = t ? __builtin_amdgcn_alignbit(hi, lo, 32u - t) : hi;
+    const uint32_t nl = t ? __builtin_amdgcn_alignbit(lo, hi, 32u - t) : lo;
+    return ((uint64_t)nh << 32) | nl;
+}
 __host__ __device__ __forceinline__ int64_t as_signed(uint64_t v) { return (int64_t)v; }
+
+// ---- raw letters, as the calls over host text meet them ----
+// [ACGTU], CASE_INSENSITIVE (R/util/SeqUtils.java:1436-1438) -> 2-bit code; 4 for every other letter
+__device__ __forceinline__ uint32_t letter_code(uint32_t ch) {
+    switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;
+                  case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
+}
+// 2-bit code -> letter, as the reference writes bases: upper case, T
+__device__ __forceinline__ uint8_t code_letter(uint32_t code) { return (uint8_t)(code == 0u ? 'A' : code == 1u ? 'C' : code == 2u ? 'G' : 'T'); }
+// The seeds of a letter as getKmers(String) hashes it (NTHash.java:30, 133-166).  Forward strand: the seedTab row of [ACGTU] in either case, else 0.
+// Reverse strand: seedTab[ch & 7] — classes 1 T, 3 G, 4 A, 5 A, 7 C carry a seed (mask 0xBA), the others 0, so a letter outside ACGTU may still
+// have one (K M S W Y I E ...).  rev_class_code: the code whose COMPLEMENT carries the class's seed (for A C G T U a c g t u the letter's own code)
+// — what the batch's rnz plane stores.
+__device__ __forceinline__ uint64_t letter_seed(uint32_t ch) {
+    switch (ch) {
+        case 'A': case 'a': return seed_of(0u);
+        case 'C': case 'c': return seed_of(1u);
+        case 'G': case 'g': return seed_of(2u);
+        case 'T': case 't': case 'U': case 'u': return seed_of(3u);
+        default: return 0ull;
+    }
+}
+__device__ __forceinline__ bool rev_class_has_seed(uint32_t cls) { return (0xBAu >> cls) & 1u; }
+__device__ __forceinline__ uint32_t rev_class_code(uint32_t cls) { return cls == 1u ? 0u : cls == 3u ? 1u : cls == 7u ? 2u : 3u; }
+__device__ __forceinline__ uint64_t letter_rev_seed(uint32_t ch) {
+    const uint32_t cls = ch & 7u;
+    return rev_class_has_seed(cls) ? seed_of(3u - rev_class_code(cls)) : 0ull;
+}
+// SeqUtils.getAltNucleotides (R/util/SeqUtils.java:147-162) as a mask over A C G T (bit a = base a is tried, in that order): the other
+// three of an upper-case A C G T, U as T, all four for any other letter (lower case included: the switch knows upper case only)
+__device__ __forceinline__ uint32_t alt_mask(uint32_t ch) {
+    switch (ch) {
+        case 'A': return 0xEu;
+        case 'C': return 0xDu;
+        case 'G': return 0xBu;
+        case 'T': case 'U': return 0x7u;
+        default: return 0xFu;
+    }
+}
 
 // canonical = SIGNED min (rhVal<fhVal ? rhVal : fhVal), R/bloom/hash/NTHash.java:488,494
 __device__ __forceinline__ uint64_t canonical(uint64_t f, uint64_t r) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_lookup.hpp"
 
 using namespace rb;
 
@@ -67,33 +68,6 @@ struct ExChain {
     }
 };
 
-// graph.getCount of a k-mer hash as a count code (0 absent, 1 + MiniFloat code).  With two hash functions per filter the four probes are
-// issued before any is consumed.
-__device__ __forceinline__ uint32_t ex_count_code(const FilterView &fv, uint64_t h) {
-    if (fv.dbg_h == 2 && fv.cbf_h == 2) {
-        const uint64_t h1 = multi_hash(h, 1u, fv.kmul);
-        const uint64_t b0 = index_of(h, fv.dbg_mod), b1 = index_of(h1, fv.dbg_mod), c0 = index_of(h, fv.cbf_mod), c1 = index_of(h1, fv.cbf_mod);
-        const uint32_t w0 = fv.dbg[b0 >> 5], w1 = fv.dbg[b1 >> 5], n0 = fv.cbf[c0], n1 = fv.cbf[c1];
-        if (!((w0 >> (uint32_t)(b0 & 31u)) & (w1 >> (uint32_t)(b1 & 31u)) & 1u)) return 0u;
-        return 1u + min(n0, n1);
-    }
-    if (!bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h)) return 0u;
-    uint32_t mn = fv.cbf[index_of(h, fv.cbf_mod)];                    // CountingBloomFilter.getCount(long[]) :235-251
-    for (int j = 1; j < fv.cbf_h; ++j) mn = min(mn, (uint32_t)fv.cbf[index_of(multi_hash(h, (uint32_t)j, fv.kmul), fv.cbf_mod)]);
-    return 1u + mn;
-}
-
-// what the kernel needs of the read-pair filter
-struct ExPairs { const uint32_t *bits; Mod mod; int num_hash; uint64_t kmul; };
-__device__ __forceinline__ bool ex_pair_hit(const ExPairs &pf, uint64_t key) {
-    if (pf.num_hash == 2) {
-        const uint64_t i0 = index_of(key, pf.mod), i1 = index_of(multi_hash(key, 1u, pf.kmul), pf.mod);
-        const uint32_t w0 = pf.bits[i0 >> 5], w1 = pf.bits[i1 >> 5];
-        return ((w0 >> (uint32_t)(i0 & 31u)) & (w1 >> (uint32_t)(i1 & 31u)) & 1u) != 0u;
-    }
-    return bits_lookup(pf.bits, pf.mod, pf.num_hash, pf.kmul, key);
-}
-
 // Both strands of a k-mer, in walking order: A rolls like a forward hash along the walk, B like a reverse-strand hash.  A right-hand walk
 // has (f, r) = (A, B) with A over the bases' seeds and B over their complements'; a left-hand walk adds bases at the k-mer's front, so its
 // A is the k-mer's reverse-strand hash and its B the forward one: xm / ym turn a base into the code whose seed A / B take.
@@ -129,7 +103,7 @@ __device__ void ex_run_walks(const FilterView &fv, const ExDir &dr, float min_co
         const int ci = w.off + w.len - 1;                        // chain index of the k-mer the walk stands on
         if (w.alive) {
             dr.step(w.A, w.B, ch.base(ci + 1), in, nA, nB);
-            code = ex_count_code(fv, dr.hash(nA, nB));
+            code = count_code(fv, dr.hash(nA, nB));
             pass = count_code_value(code) >= min_cov;
         }
         const uint32_t m4 = (uint32_t)(__ballot(pass) >> (lane & ~3u)) & 0xFu;
@@ -171,7 +145,7 @@ struct ExTail {
 // nt - d + i where that is not negative; k-mers below i0 are known to have no support (they were counted with the first level).  Each lane
 // hashes its k-mer from the chain's bases (rotations by one only) and forms Kmer.getKmerPairHashValue (R/graph/Kmer.java:65-67,
 // CanonicalKmer.java:61-72) with the partner on the side the direction puts it.
-__device__ void ex_count_pairs(const ExPairs &pf, const ExDir &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane, int &pairs, int &last) {
+__device__ void ex_count_pairs(const PairView &pf, const ExDir &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane, int &pairs, int &last) {
     const int hi = min(d - 1, n - 1), k = (int)dr.uk;
     pairs = 0; last = -1;
     for (int base = i0; base <= hi; base += 64) {
@@ -188,7 +162,7 @@ __device__ void ex_count_pairs(const ExPairs &pf, const ExDir &dr, const ExChain
             uint64_t key;
             if (!dr.left) key = dr.stranded ? combine(pfw, f) : smin(combine(pfw, f), combine(r, prv));      // partner on the left
             else key = dr.stranded ? combine(f, pfw) : smin(combine(f, pfw), combine(prv, r));               // partner on the right
-            hit = ex_pair_hit(pf, key);
+            hit = pair_hit(pf, key);
         }
         const unsigned long long m = __ballot(hit);
         if (m) { pairs += __popcll(m); last = base + 63 - (int)__builtin_clzll(m); }
@@ -200,26 +174,11 @@ struct ExCodes {
     const uint8_t *c1, *c2;
     int gap, n;
     __device__ __forceinline__ uint32_t at(int i) const { return i < gap ? c1[i] : c2[i - gap]; }
+    __device__ __forceinline__ uint32_t operator()(int i) const { return at(i); }
 };
-// getMedianKmerCoverage(Collection) :229-247: sorted[n / 2], or (sorted[n / 2] + sorted[n / 2 - 1]) / 2.0f.  The order statistics are found by
-// bisection over the 129 count codes with one ballot per 64 k-mers and step, as correctMismatches' kernel finds them.
-__device__ uint32_t ex_kth(const ExCodes &cc, int rank, uint32_t lane) {
-    uint32_t lo = 0, hi = 128;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        int cnt = 0;
-        for (int base = 0; base < cc.n; base += 64) {
-            const int i = base + (int)lane;
-            cnt += __popcll(__ballot(i < cc.n && cc.at(i) <= mid));
-        }
-        if (cnt >= rank + 1) hi = mid; else lo = mid + 1u;
-    }
-    return lo;
-}
+// getMedianKmerCoverage(Collection) :229-247 of a chain's count codes
 __device__ float ex_median(const ExCodes &cc, uint32_t lane) {
-    const float hi = count_code_value(ex_kth(cc, cc.n / 2, lane));
-    if (cc.n & 1) return hi;
-    return (hi + count_code_value(ex_kth(cc, cc.n / 2 - 1, lane))) / 2.0f;
+    return median_code(cc, cc.n, lane);
 }
 
 __device__ __forceinline__ void ex_put(rb_extend_rec *rec, int outcome, int why, int n_cand, int out_len, int pairs, int last, int winner, float score) {
@@ -230,7 +189,7 @@ __device__ __forceinline__ void ex_put(rb_extend_rec *rec, int outcome, int why,
 
 struct ExArgs {
     FilterView fv;
-    ExPairs pf;
+    PairView pf;
     int stranded, k, d, direction, D;        // D: the distance the rows are laid out for (EX_LDS_D in LDS, d in device scratch)
     int64_t pn;
     const int64_t *kof;                      // k-mer offsets of the piece's (cut) sequences
@@ -249,7 +208,7 @@ __device__ void ex_emit(const ExArgs &a, int64_t r, const ExChain &ch, const ExC
     const int64_t o = r * (int64_t)(a.d + 2);
     for (int i = (int)lane; i < n; i += 64) {
         const uint32_t b = ch.base(a.k + i);
-        a.out_b[o + i] = (uint8_t)(b == 0u ? 'A' : b == 1u ? 'C' : b == 2u ? 'G' : 'T');
+        a.out_b[o + i] = code_letter(b);
         if (a.out_c) a.out_c[o + i] = count_code_value(cc.at(i));
     }
 }
@@ -302,7 +261,7 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
     uint32_t code = 0;
     if (lane < 4u) {
         dr.step(A0, B0, ch0.base(0), in, nA, nB);
-        code = ex_count_code(a.fv, dr.hash(nA, nB));
+        code = count_code(a.fv, dr.hash(nA, nB));
     }
     const uint32_t mask0 = (uint32_t)__ballot(lane < 4u && code >= 1u) & 0xFu;
     const int n_cand = __popc(mask0);
@@ -366,7 +325,7 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
         code = 0;
         if (probe) {
             dr.step(w1.A, w1.B, ch1.base(w1.len), in, nA, nB);
-            code = ex_count_code(a.fv, dr.hash(nA, nB));
+            code = count_code(a.fv, dr.hash(nA, nB));
         }
         mask2 = (uint32_t)__ballot(probe && code >= 1u) & 0xFFFFu;
         w2.A = ex_shfl64(nA, (int)wid); w2.B = ex_shfl64(nB, (int)wid);
@@ -497,7 +456,7 @@ int rb_graph_extend_se(rb_graph *g, const char *seq, const int64_t *offsets, int
             uint8_t *base3 = q.c->b3.as<uint8_t>();
             ExArgs a;
             a.fv = g->view(0, 0);
-            a.pf = ExPairs{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
+            a.pf = PairView{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
             a.stranded = (int)g->stranded; a.k = k; a.d = d; a.direction = direction; a.D = lds ? EX_LDS_D : d;
             a.pn = pn;
             a.kof = q.c->b0.as<int64_t>();

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_lookup.hpp"
 
 using namespace rb;
 
@@ -33,44 +34,6 @@ __device__ __forceinline__ uint32_t mm_threshold_code(float t, uint32_t lane) {
     return count_code_value(128u) >= t ? 128u : 129u;
 }
 
-// rotation by a run-time amount out of 32-bit funnel shifts: no 64-bit shift takes its amount from a vector register here
-__device__ __forceinline__ uint64_t rot64(uint64_t v, uint32_t s) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    if (s & 32u) { const uint32_t t = lo; lo = hi; hi = t; }
-    const uint32_t t = s & 31u;
-    const uint32_t nh = t ? __builtin_amdgcn_alignbit(hi, lo, 32u - t) : hi;
-    const uint32_t nl = t ? __builtin_amdgcn_alignbit(lo, hi, 32u - t) : lo;
-    return ((uint64_t)nh << 32) | nl;
-}
-
-// seeds of a raw letter as getKmers(String) hashes it: forward seedTab row of [ACGTU] in either case, else 0; reverse strand
-// seedTab[ch & 7] (NTHash.java:30, 133-166: classes 1 T, 3 G, 4 A, 5 A, 7 C, the others 0) — what the batch's valid / rnz planes encode
-__device__ __forceinline__ void mm_seeds_of_char(uint32_t ch, uint64_t &s, uint64_t &sc) {
-    uint32_t code = 4u;
-    switch (ch) {
-        case 'A': case 'a': code = 0u; break;
-        case 'C': case 'c': code = 1u; break;
-        case 'G': case 'g': code = 2u; break;
-        case 'T': case 't': case 'U': case 'u': code = 3u; break;
-        default: break;
-    }
-    s = code < 4u ? seed_of(code) : 0ull;
-    const uint32_t cls = ch & 7u;
-    const uint32_t rc = cls == 1u ? 0u : cls == 3u ? 1u : cls == 7u ? 2u : 3u;
-    sc = ((0xBAu >> cls) & 1u) ? seed_of(3u - rc) : 0ull;
-}
-// SeqUtils.getAltNucleotides (R/util/SeqUtils.java:147-162) as a mask over A C G T (bit a = base a is tried, in that order): the other
-// three of an upper-case A C G T, U as T, all four for any other letter (lower case included: the switch knows upper case only)
-__device__ __forceinline__ uint32_t mm_alt_mask(uint32_t ch) {
-    switch (ch) {
-        case 'A': return 0xEu;
-        case 'C': return 0xDu;
-        case 'G': return 0xBu;
-        case 'T': case 'U': return 0x7u;
-        default: return 0xFu;
-    }
-}
-
 // are the bases [j, j + k) of the sequence usable, position q (the one being replaced by A C G T) left out?
 __device__ __forceinline__ bool mm_window_clean(const uint32_t *__restrict__ vw, uint32_t j, uint32_t k, uint32_t q) {
     bool ok = true;
@@ -89,61 +52,33 @@ __device__ __forceinline__ bool mm_window_clean(const uint32_t *__restrict__ vw,
 // forward strand and er on the reverse strand the variant's hashes are f ^ rotl(seed(old) ^ seed(new), ef) and the mirrored term — no
 // rolling.  Returns the four count codes (byte a = substitution a; 0 where the window has another unusable base, `clean` false) and in
 // `inmask` bit a = the variant window is in dbgbf (graph.contains: the Bloom bits alone).  With two hash functions per filter — every
-// configuration the reference runs — the 8 Bloom-bit loads and the 8 counter loads of the four variants are issued before any is
-// consumed; a substitution that is not tried (the base itself) probes its neighbour's lines again instead of the window's own.
+// configuration the reference runs — the probes of the four variants are issued together (count_lookup4, rb_lookup.hpp); a substitution
+// that is not tried (the base itself) probes its neighbour's lines again instead of the window's own.
 __device__ __forceinline__ uint32_t mm_variant_codes(const FilterView &fv, int stranded, uint64_t f, uint64_t r, uint64_t so, uint64_t sco,
                                                      uint32_t ef, uint32_t er, uint32_t altmask, bool clean, uint32_t &inmask) {
     uint64_t h[4];
 #pragma unroll
     for (uint32_t a = 0; a < 4u; ++a) {
-        const uint64_t nf = f ^ rot64(so ^ seed_of(a), ef);
-        const uint64_t nr = r ^ rot64(sco ^ seed_of(3u - a), er);
+        const uint64_t nf = f ^ rotl_var(so ^ seed_of(a), ef);
+        const uint64_t nr = r ^ rotl_var(sco ^ seed_of(3u - a), er);
         h[a] = stranded ? nf : canonical(nf, nr);
     }
 #pragma unroll
     for (uint32_t a = 0; a < 4u; ++a)
         if (!((altmask >> a) & 1u)) h[a] = h[a ^ 1u];
-    uint32_t codes = 0;
-    inmask = 0;
-    if (fv.dbg_h == 2 && fv.cbf_h == 2) {
-        uint64_t bi[4][2], ci[4][2];
-        uint32_t bw[4][2], cb[4][2];
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) {
-            const uint64_t h1 = multi_hash(h[a], 1u, fv.kmul);
-            bi[a][0] = index_of(h[a], fv.dbg_mod); bi[a][1] = index_of(h1, fv.dbg_mod);
-            ci[a][0] = index_of(h[a], fv.cbf_mod); ci[a][1] = index_of(h1, fv.cbf_mod);
-        }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) { bw[a][0] = fv.dbg[bi[a][0] >> 5]; bw[a][1] = fv.dbg[bi[a][1] >> 5]; }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) { cb[a][0] = fv.cbf[ci[a][0]]; cb[a][1] = fv.cbf[ci[a][1]]; }
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) {
-            const uint32_t in = (bw[a][0] >> (uint32_t)(bi[a][0] & 31u)) & (bw[a][1] >> (uint32_t)(bi[a][1] & 31u)) & 1u;
-            const uint32_t mn = cb[a][0] < cb[a][1] ? cb[a][0] : cb[a][1];
-            inmask |= in << a;
-            codes |= ((in && clean) ? 1u + mn : 0u) << (8u * a);
-        }
-    } else {
-#pragma unroll
-        for (uint32_t a = 0; a < 4u; ++a) {
-            const bool in = bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h[a]);
-            uint32_t mn = 0;
-            if (in && clean) {                       // CountingBloomFilter.getCount(long[]) :235-251
-                mn = fv.cbf[index_of(h[a], fv.cbf_mod)];
-                for (int j = 1; j < fv.cbf_h; ++j) mn = min(mn, (uint32_t)fv.cbf[index_of(multi_hash(h[a], (uint32_t)j, fv.kmul), fv.cbf_mod)]);
-            }
-            inmask |= (in ? 1u : 0u) << a;
-            codes |= ((in && clean) ? 1u + mn : 0u) << (8u * a);
-        }
-    }
+    uint32_t codes = 0, ins = 0;
+    count_lookup4(fv, h, [&](uint32_t a, bool in, uint32_t mn) {
+        ins |= (in ? 1u : 0u) << a;
+        codes |= ((in && clean) ? 1u + mn : 0u) << (8u * a);
+    });
+    inmask = ins;
     return codes;
 }
 
 // Common.getMedian (R/util/Common.java:41-50) of the n codes a wavefront holds in c[] (lane l, slot s: element 64 s + l; 255 past the end):
 // sorted[n / 2], or (sorted[n / 2 - 1] + sorted[n / 2]) / 2.0f.  An order statistic is found by bisection over the 129 code values with
-// one ballot per slot and step: no sort, no LDS.
+// one ballot per slot and step: no sort, no LDS.  Not kth_code (rb_lookup.hpp): the slots are registers, which a slot index known only at run
+// time would send to scratch, so the loop over them stays unrolled here; the even / odd rule on top is the shared one.
 __device__ __forceinline__ uint32_t mm_kth(const uint32_t (&c)[MM_SLOTS], int n, int rank) {
     uint32_t lo = 0, hi = 128;
     while (lo < hi) {
@@ -157,9 +92,7 @@ __device__ __forceinline__ uint32_t mm_kth(const uint32_t (&c)[MM_SLOTS], int n,
     return lo;
 }
 __device__ __forceinline__ float mm_median(const uint32_t (&c)[MM_SLOTS], int n) {
-    const float hi = count_code_value(mm_kth(c, n, n / 2));
-    if (n & 1) return hi;
-    return (count_code_value(mm_kth(c, n, n / 2 - 1)) + hi) / 2.0f;
+    return median_of_kth([&](int rank) { return mm_kth(c, n, rank); }, n);
 }
 
 // A wavefront per sequence: sequence r of the piece has windows [kof[r], kof[r + 1]) of F / R / cnt (what the getKmers kernel left) and
@@ -218,9 +151,8 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
             const int32_t i = base + step * (int32_t)__builtin_ctzll(m);
             const int32_t j0 = dir ? i - k + 1 : i, gw = dir ? k - 1 : 0, q = j0 + k - 1;
             const uint32_t ch = tx[q];
-            const uint32_t altmask = mm_alt_mask(ch);
-            uint64_t so, sco;
-            mm_seeds_of_char(ch, so, sco);
+            const uint32_t altmask = alt_mask(ch);
+            const uint64_t so = letter_seed(ch), sco = letter_rev_seed(ch);
             // the k windows under the four substitutions
             uint32_t gl = 0;
             for (int32_t w = (int32_t)lane; w < k; w += 64) {
@@ -256,11 +188,11 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
                 for (int32_t w = (int32_t)lane; w < k; w += 64) {
                     const int32_t j = j0 + w;
                     row[j] = (uint8_t)((vc[w] >> (8 * besta)) & 255u);
-                    f_[j] ^= rot64(df, (uint32_t)w);
-                    if (!stranded) r_[j] ^= rot64(dr, (uint32_t)(k - 1 - w));
+                    f_[j] ^= rotl_var(df, (uint32_t)w);
+                    if (!stranded) r_[j] ^= rotl_var(dr, (uint32_t)(k - 1 - w));
                 }
                 if (lane == 0) {
-                    tx[q] = (uint8_t)(besta == 0 ? 'A' : besta == 1 ? 'C' : besta == 2 ? 'G' : 'T');
+                    tx[q] = code_letter((uint32_t)besta);
                     vw[q >> 5] |= 1u << (q & 31);
                 }
                 ++nfix;

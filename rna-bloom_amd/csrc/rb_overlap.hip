@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_lookup.hpp"
 
 using namespace rb;
 
@@ -27,28 +28,6 @@ constexpr int OV_LDS_ROW = 1024;         // bytes of LDS a pair's two reads may 
 __host__ __device__ inline int64_t ov_right_at(int64_t ll) { return (ll + 3) & ~(int64_t)3; }
 __host__ __device__ inline bool ov_fits_lds(int64_t ll, int64_t rl) { return ov_right_at(ll) + rl <= OV_LDS_ROW; }
 
-// seeds of a raw letter as getKmers(String) hashes it: forward seedTab row of [ACGTU] in either case, else 0; reverse strand
-// seedTab[ch & 7] (NTHash.java:30, 133-166: classes 1 T, 3 G, 4 A, 5 A, 7 C, the others 0)
-__device__ __forceinline__ bool ov_is_acgtu(uint32_t ch) {
-    switch (ch) {
-        case 'A': case 'a': case 'C': case 'c': case 'G': case 'g': case 'T': case 't': case 'U': case 'u': return true;
-        default: return false;
-    }
-}
-__device__ __forceinline__ uint64_t ov_fwd_seed(uint32_t ch) {
-    switch (ch) {
-        case 'A': case 'a': return seed_of(0u);
-        case 'C': case 'c': return seed_of(1u);
-        case 'G': case 'g': return seed_of(2u);
-        case 'T': case 't': case 'U': case 'u': return seed_of(3u);
-        default: return 0ull;
-    }
-}
-__device__ __forceinline__ uint64_t ov_rev_seed(uint32_t ch) {
-    const uint32_t cls = ch & 7u;
-    const uint32_t rc = cls == 1u ? 0u : cls == 3u ? 1u : cls == 7u ? 2u : 3u;
-    return ((0xBAu >> cls) & 1u) ? seed_of(3u - rc) : 0ull;
-}
 // SeqUtils.nucleotideArrayIndex(int) :315-330: upper case only, U as T, -1 for everything else
 __device__ __forceinline__ int ov_nt_index(uint32_t ch) {
     switch (ch) {
@@ -99,7 +78,7 @@ __device__ int ov_match(const uint8_t *a, int al, const uint8_t *b, int bl, int 
 
 // the getKmers count of the window of k letters at w of text t (0 where a letter is outside ACGTU, else graph.getCount of its hash:
 // BloomFilterDeBruijnGraph.java:562-570), and whether its k bytes are all equal (SeqUtils.isHomopolymer(byte[]) :354-368).  Both strands are
-// rolled one letter a step (rotations by one only).  With two hash functions per filter the four probes are issued before any is consumed.
+// rolled one letter a step (rotations by one only).
 template <typename T> __device__ float ov_window_count(const FilterView &fv, int stranded, int k, const T &t, int w, bool &homo) {
     uint64_t f = 0, r = 0;
     bool ok = true;
@@ -107,24 +86,15 @@ template <typename T> __device__ float ov_window_count(const FilterView &fv, int
     homo = true;
     for (int j = 0; j < k; ++j) {
         const uint32_t c = t(w + j);
-        f = rotl(f, 1) ^ ov_fwd_seed(c);
-        if (!stranded) r = rotl(r, 1) ^ ov_rev_seed(t(w + k - 1 - j));
-        ok = ok && ov_is_acgtu(c);
+        const uint64_t s = letter_seed(c);                 // (0 for a letter outside ACGTU, and for no other)
+        f = rotl(f, 1) ^ s;
+        if (!stranded) r = rotl(r, 1) ^ letter_rev_seed(t(w + k - 1 - j));
+        ok = ok && s != 0ull;
         homo = homo && c == c0;
     }
     if (!ok) return 0.0f;
     const uint64_t h = stranded ? f : canonical(f, r);
-    if (fv.dbg_h == 2 && fv.cbf_h == 2) {
-        const uint64_t h1 = multi_hash(h, 1u, fv.kmul);
-        const uint64_t b0 = index_of(h, fv.dbg_mod), b1 = index_of(h1, fv.dbg_mod), c0i = index_of(h, fv.cbf_mod), c1i = index_of(h1, fv.cbf_mod);
-        const uint32_t w0 = fv.dbg[b0 >> 5], w1 = fv.dbg[b1 >> 5], n0 = fv.cbf[c0i], n1 = fv.cbf[c1i];
-        if (!((w0 >> (uint32_t)(b0 & 31u)) & (w1 >> (uint32_t)(b1 & 31u)) & 1u)) return 0.0f;
-        return minifloat_to_float(min(n0, n1)) + 1.0f;
-    }
-    if (!bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h)) return 0.0f;
-    uint32_t mn = fv.cbf[index_of(h, fv.cbf_mod)];                    // CountingBloomFilter.getCount(long[]) :235-251
-    for (int j = 1; j < fv.cbf_h; ++j) mn = min(mn, (uint32_t)fv.cbf[index_of(multi_hash(h, (uint32_t)j, fv.kmul), fv.cbf_mod)]);
-    return minifloat_to_float(mn) + 1.0f;
+    return count_value(fv, h);
 }
 
 // does one of the windows [w0, w1) of t have count == 1?  A lane per window.

@@ -21,6 +21,7 @@
 #include <zlib.h>
 
 #include "rb_pieces.hpp"
+#include "rb_lookup.hpp"
 
 using namespace rb;
 
@@ -33,20 +34,6 @@ __global__ void rb::k_bits_add(uint32_t *bits, Mod mod, int num_hash, uint64_t k
 
 namespace {
 
-// CountingBloomFilter.getCount(long[]) :235-251 (zero check inside the h>=1 loop)
-__device__ __forceinline__ float cbf_get_count(const uint8_t *cbf, const Mod &mod, int num_hash, uint64_t kmul, uint64_t h0) {
-    uint32_t mn = cbf[index_of(h0, mod)];
-    for (int j = 1; j < num_hash; ++j) {
-        uint32_t c = cbf[index_of(multi_hash(h0, (uint32_t)j, kmul), mod)];
-        if (c < mn) mn = c;
-        if (mn == 0u) return 0.0f;
-    }
-    return minifloat_to_float(mn);
-}
-__device__ __forceinline__ float graph_count(const FilterView &fv, uint64_t h0) {   // BloomFilterDeBruijnGraph.java:562-570
-    if (!bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h0)) return 0.0f;
-    return cbf_get_count(fv.cbf, fv.cbf_mod, fv.cbf_h, fv.kmul, h0) + 1.0f;
-}
 __global__ void k_bits_lookup(const uint32_t *bits, Mod mod, int num_hash, uint64_t kmul, const uint64_t *__restrict__ h0, size_t n, uint8_t *out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = bits_lookup(bits, mod, num_hash, kmul, h0[i]) ? 1 : 0;
@@ -112,8 +99,8 @@ __global__ void k_get_kmers(FilterView fv, int stranded, const uint64_t *__restr
 // 0 where the window holds an unusable base (R/bloom/hash/CanonicalHashFunction.java:46-78) — what stage 2 reads first of every
 // read (R/RNABloom.java:1984, 2097-2114).  One thread per 32-window word as in k_get_kmers; the hashes are rolled, nothing but the
 // counts is written.  Written for memory-level parallelism: a lane collects four usable windows, computes all their filter
-// indices, issues the 8 Bloom-bit loads, then the 8 counter loads, and only then combines them (graph_count per window would be
-// four dependent round trips each).  koff == nullptr: rows of `stride` counts (uniform reads).
+// indices, issues the 8 Bloom-bit loads, then the 8 counter loads, and only then combines them (probe4_h2, rb_lookup.hpp; graph_count per
+// window would be four dependent round trips each).  koff == nullptr: rows of `stride` counts (uniform reads).
 __global__ void __launch_bounds__(256) k_batch_counts(FilterView fv, int stranded, const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid,
                                                       const uint32_t *__restrict__ word_read, const uint32_t *__restrict__ woff,
                                                       const uint32_t *__restrict__ len, int64_t w_first, int64_t n_words, uint32_t r_first, int k,
@@ -132,25 +119,8 @@ __global__ void __launch_bounds__(256) k_batch_counts(FilterView fv, int strande
     uint64_t f = 0, rv = 0, pend_h[4];
     uint32_t filled = 0, run = 0, pend_p[4], n_pend = 0;
     auto flush = [&]() {
-        uint64_t bi[4][2], ci[4][2];
-        uint32_t bw[4][2], cb[4][2];
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) {
-            const uint64_t h0 = q < n_pend ? pend_h[q] : pend_h[0], h1 = multi_hash(h0, 1u, fv.kmul);
-            bi[q][0] = index_of(h0, fv.dbg_mod); bi[q][1] = index_of(h1, fv.dbg_mod);
-            ci[q][0] = index_of(h0, fv.cbf_mod); ci[q][1] = index_of(h1, fv.cbf_mod);
-        }
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) { bw[q][0] = fv.dbg[bi[q][0] >> 5]; bw[q][1] = fv.dbg[bi[q][1] >> 5]; }
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) { cb[q][0] = fv.cbf[ci[q][0]]; cb[q][1] = fv.cbf[ci[q][1]]; }
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) {
-            if (q >= n_pend) break;
-            const bool in = ((bw[q][0] >> (uint32_t)(bi[q][0] & 31u)) & (bw[q][1] >> (uint32_t)(bi[q][1] & 31u)) & 1u) != 0u;
-            const uint32_t mn = cb[q][0] < cb[q][1] ? cb[q][0] : cb[q][1];
-            out_c[row + pend_p[q]] = in ? minifloat_to_float(mn) + 1.0f : 0.0f;
-        }
+        probe4_h2(fv, n_pend, [&](uint32_t q) { return q < n_pend ? pend_h[q] : pend_h[0]; },
+                  [&](uint32_t q, bool in, uint32_t mn) { out_c[row + pend_p[q]] = in ? minifloat_to_float(mn) + 1.0f : 0.0f; });
         n_pend = 0;
     };
     for (uint32_t b = b0; b < bend; ++b) {
@@ -183,10 +153,6 @@ __global__ void __launch_bounds__(256) k_batch_counts(FilterView fv, int strande
 
 // Kmer.getSuccessors / getPredecessors: the four neighbours' hashes and counts
 // (R/bloom/hash/{,Canonical}{Successors,Predecessors}NTHashIterator.java; R/graph/Kmer.java:210-255)
-__device__ __forceinline__ uint32_t code_of_char(uint32_t ch) {
-    switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2;
-                  case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
-}
 template <bool HASH_ONLY>
 __global__ void k_neighbors(FilterView fv, int stranded, int k, int direction, const uint64_t *__restrict__ f,
                             const uint64_t *__restrict__ r, const uint8_t *__restrict__ ch, size_t n,
@@ -195,7 +161,7 @@ __global__ void k_neighbors(FilterView fv, int stranded, int k, int direction, c
     if (t >= n * 4) return;
     const size_t i = t >> 2;
     const uint32_t in = (uint32_t)(t & 3u), uk = (uint32_t)k;
-    const uint32_t oc = code_of_char(ch[i]);
+    const uint32_t oc = letter_code(ch[i]);
     const uint64_t s_out = oc < 4 ? seed_of(oc) : 0ull, sc_out = oc < 4 ? seed_of(3u - oc) : 0ull;
     uint64_t nf, nr = 0;
     if (direction == 0) {
@@ -308,7 +274,7 @@ __global__ void k_walk_max_cov(SRC src, int stranded, int k, int direction, cons
     auto hash_kmer = [&](const uint8_t *b, uint64_t &f, uint64_t &r) -> bool {
         f = 0; r = 0;
         for (uint32_t q = 0; q < uk; ++q) {
-            const uint32_t c = code_of_char(b[q]);
+            const uint32_t c = letter_code(b[q]);
             if (c > 3u) return false;
             f = rotl(f, 1) ^ seed_of(c);
             r ^= rotl(seed_of(3u - c), q);
@@ -330,7 +296,7 @@ __global__ void k_walk_max_cov(SRC src, int stranded, int k, int direction, cons
     } else
         for (uint32_t q = 0; q < uk; ++q) sq[q] = (direction == 0) ? sb[q] : sb[uk - 1u - q];
     while (len < my_bound) {
-        const uint32_t oc = code_of_char(sq[len]);            // base leaving: first base (right walk) / last base (left walk)
+        const uint32_t oc = letter_code(sq[len]);            // base leaving: first base (right walk) / last base (left walk)
         const uint64_t s_out = seed_of(oc), sc_out = seed_of(3u - oc);
         float best_c = -1.0f;
         uint64_t best_f = 0, best_r = 0;
@@ -354,16 +320,16 @@ __global__ void k_walk_max_cov(SRC src, int stranded, int k, int direction, cons
         const uint8_t nb = acgt[best_in];
         // bases of the candidate: seq[len+1 .. len+k-1] + nb
         auto same_as = [&](const uint8_t *other_fwd_or_rev, bool other_is_seq) -> bool {   // other: k bases in walk orientation
-            for (uint32_t q = 0; q + 1u < uk; ++q) if (code_of_char(sq[(size_t)len + 1u + q]) != code_of_char(other_fwd_or_rev[q])) return false;
+            for (uint32_t q = 0; q + 1u < uk; ++q) if (letter_code(sq[(size_t)len + 1u + q]) != letter_code(other_fwd_or_rev[q])) return false;
             (void)other_is_seq;
-            return code_of_char(other_fwd_or_rev[uk - 1u]) == best_in;
+            return letter_code(other_fwd_or_rev[uk - 1u]) == best_in;
         };
         if (has_target && best_f == tf) {
             bool eq = true;                                    // target bases are given left to right
             for (uint32_t q = 0; q < uk && eq; ++q) {
                 const uint8_t cb = (q + 1u < uk) ? sq[(size_t)len + 1u + q] : nb;          // candidate in walk orientation
                 const uint8_t tq = (direction == 0) ? tb[q] : tb[uk - 1u - q];
-                eq = code_of_char(cb) == code_of_char(tq);
+                eq = letter_code(cb) == letter_code(tq);
             }
             if (eq) { reason = 1; break; }
         }
@@ -422,7 +388,7 @@ __global__ void k_naive_extend(SRC src, int stranded, int k, int direction, int 
     const uint8_t *sb = seeds + i * (size_t)k;
     uint64_t f = 0, r = 0;
     for (uint32_t q = 0; q < uk; ++q) {
-        const uint32_t c = code_of_char(sb[q]);
+        const uint32_t c = letter_code(sb[q]);
         if (c > 3u) { out_len[i] = 0; out_reason[i] = 4; if (SRC::kReplay) ta.phase[i] = 2; return; }
         f = rotl(f, 1) ^ seed_of(c);
         r ^= rotl(seed_of(3u - c), q);
@@ -436,14 +402,14 @@ __global__ void k_naive_extend(SRC src, int stranded, int k, int direction, int 
     // candidate (walk orientation: sq[len+1 .. len+k-1] + nb) against k bases given left to right
     auto cand_equals = [&](const uint8_t *other, uint32_t best_in) -> bool {
         for (uint32_t q = 0; q < uk; ++q) {
-            const uint32_t cq = (q + 1u < uk) ? code_of_char(sq[(size_t)len + 1u + q]) : best_in;      // walk orientation
-            const uint32_t oq = code_of_char((direction == 0) ? other[q] : other[uk - 1u - q]);
+            const uint32_t cq = (q + 1u < uk) ? letter_code(sq[(size_t)len + 1u + q]) : best_in;      // walk orientation
+            const uint32_t oq = letter_code((direction == 0) ? other[q] : other[uk - 1u - q]);
             if (cq != oq) return false;
         }
         return true;
     };
     for (;;) {
-        const uint32_t oc = code_of_char(sq[len]);            // base about to leave: first base (right walk) / last base (left walk)
+        const uint32_t oc = letter_code(sq[len]);            // base about to leave: first base (right walk) / last base (left walk)
         const uint64_t s_out = seed_of(oc), sc_out = seed_of(3u - oc);
         uint32_t n_nb = 0, best_in = 0;
         uint64_t best_f = 0, best_r = 0;
@@ -478,8 +444,8 @@ __global__ void k_naive_extend(SRC src, int stranded, int k, int direction, int 
                 if (term_f[j] == best_f && cand_equals(term_seq + term_off[i] + (j - term_koff[i]), best_in)) hit = true;
             for (int j = 0; j < len && !hit; ++j)
                 if (pf[j] == best_f) {                        // a k-mer the walk added: sq[j+1 .. j+k] in walk orientation
-                    bool eq = code_of_char(sq[(size_t)j + uk]) == best_in;
-                    for (uint32_t q = 0; q + 1u < uk && eq; ++q) eq = code_of_char(sq[(size_t)len + 1u + q]) == code_of_char(sq[(size_t)j + 1u + q]);
+                    bool eq = letter_code(sq[(size_t)j + uk]) == best_in;
+                    for (uint32_t q = 0; q + 1u < uk && eq; ++q) eq = letter_code(sq[(size_t)len + 1u + q]) == letter_code(sq[(size_t)j + 1u + q]);
                     hit = eq;
                 }
             if (hit) { reason = 5; break; }
@@ -487,8 +453,8 @@ __global__ void k_naive_extend(SRC src, int stranded, int k, int direction, int 
         } else if (mode == 2) {
             bool rep = best_f == seed_f && cand_equals(sb, best_in);
             if (!rep && len > 0 && pf[len - 1] == best_f) {   // equals the k-mer added last: sq[len .. len+k-1]
-                rep = code_of_char(sq[(size_t)len + uk - 1u]) == best_in;
-                for (uint32_t q = 0; q + 1u < uk && rep; ++q) rep = code_of_char(sq[(size_t)len + 1u + q]) == code_of_char(sq[(size_t)len + q]);
+                rep = letter_code(sq[(size_t)len + uk - 1u]) == best_in;
+                for (uint32_t q = 0; q + 1u < uk && rep; ++q) rep = letter_code(sq[(size_t)len + 1u + q]) == letter_code(sq[(size_t)len + q]);
             }
             if (rep) { reason = 7; break; }
         }
@@ -558,7 +524,7 @@ __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stran
     const uint8_t *sb = seeds + i * (size_t)k;
     uint64_t f = 0, r = 0;
     for (uint32_t q = 0; q < uk; ++q) {
-        const uint32_t c = code_of_char(sb[q]);
+        const uint32_t c = letter_code(sb[q]);
         if (c > 3u) { out_len[i] = 0; out_reason[i] = 4; if (SRC::kReplay) ta.phase[i] = 2; return; }
         f = rotl(f, 1) ^ seed_of(c);
         r ^= rotl(seed_of(3u - c), q);
@@ -575,7 +541,7 @@ __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stran
     bool suspended = false;                            // sharded graphs: a neighbourhood whose counts are not known yet
     const int my_bound = bounds ? bounds[i] : bound;
     while (len < my_bound) {
-        const int nc = walk_neighbors(w, kmul, gate, stranded, uk, direction, f, r, code_of_char(sq[len]), 1.0f, cand);
+        const int nc = walk_neighbors(w, kmul, gate, stranded, uk, direction, f, r, letter_code(sq[len]), 1.0f, cand);
         if (nc < 0) { suspended = true; break; }
         if (nc == 0) { reason = 0; break; }
         int best = 0;
@@ -588,7 +554,7 @@ __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stran
                 path[0] = cand[ci];
                 int psize = 1, depth = 0;                // psize = path.size(); depth = frontier.size()
                 WalkCand nb[4];
-                int nn = walk_neighbors(w, kmul, gate, stranded, uk, direction, cand[ci].f, cand[ci].r, code_of_char(sq[(size_t)len + 1u]), 1.0f, nb);
+                int nn = walk_neighbors(w, kmul, gate, stranded, uk, direction, cand[ci].f, cand[ci].r, letter_code(sq[(size_t)len + 1u]), 1.0f, nb);
                 // (sharded graphs: an unknown neighbourhood is filed and taken for a dead end, and the search goes on — through the
                 // siblings and the other candidates — so that ONE exchange round brings every neighbourhood that can be asked for now:
                 // a level of the search per round instead of a neighbourhood per round.  The step is replayed anyway.)
@@ -604,7 +570,7 @@ __global__ void k_greedy_extend(SRC src, uint64_t kmul, WalkGate gate, int stran
                         if (psize < lookahead) {
                             const WalkCand &cur = path[psize - 1];
                             // cursor = k-mer number (psize-1) after the candidate: its leaving base is sq[len + 1 + (psize-1)]
-                            nn = walk_neighbors(w, kmul, gate, stranded, uk, direction, cur.f, cur.r, code_of_char(sq[(size_t)len + (size_t)psize]), 1.0f, nb);
+                            nn = walk_neighbors(w, kmul, gate, stranded, uk, direction, cur.f, cur.r, letter_code(sq[(size_t)len + (size_t)psize]), 1.0f, nb);
                             if (nn < 0) { suspended = true; nn = 0; }
                             if (nn > 0) {
                                 for (int q = 0; q < nn; ++q) frontier[depth][q] = nb[q];

@@ -397,10 +397,10 @@ class World:
     is made for the right-hand direction and mirrored: the reversed transcripts are inserted too and the reversed queries go left."""
     FLOORS = (1.0, 2.0, 5.0, 1.0e6)
 
-    def __init__(self, k, stranded, seed, d=30, n_iso=6, read_len=100, tile=10, tx_len=500):
+    def __init__(self, k, stranded, seed, d=30, n_iso=6, read_len=100, tile=10, tx_len=500, hashes=(2, 2, 2)):
         from oracle import rbo
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.d = k, stranded, d
+        self.k, self.stranded, self.d, self.hashes = k, stranded, d, hashes
         rnd = lambda n: np.frombuffer(ACGT, np.uint8)[rng.integers(0, 4, n)].tobytes()
         half = tx_len // 2
         tx, q = [], []                                        # (transcript, multiplicity), (kind, sequence)
@@ -459,7 +459,7 @@ class World:
                 reads += [tt[a:a + read_len] for a in starts] * m
         self.reads = reads
         self.sizes = (4_800_011, 4_800_011, 4_800_017)
-        self.og = rbo.Graph(*self.sizes, 2, 2, 2, k, stranded, True, 5)
+        self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
         self.og.set_read_pair_distance(d)
         self.packed = rbo.pack_reads(reads, [b"I" * len(s) for s in reads])
         self.og.add_reads(*self.packed, 3, rbo.STORE_READ_PAIRS)

@@ -65,9 +65,9 @@ class OracleSide(MismatchOracle):
 class World:
     """an oracle graph from reads of random transcripts, the query sets, and — built on request — the device graph from the same reads"""
 
-    def __init__(self, k, stranded, seed, n_tx=20, n_reads=2600, sizes=(1_600_033, 1_600_033, 1009)):
+    def __init__(self, k, stranded, seed, n_tx=20, n_reads=2600, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2)):
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.sizes, self.rng = k, stranded, sizes, rng
+        self.k, self.stranded, self.sizes, self.rng, self.hashes = k, stranded, sizes, rng, hashes
         self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(600, 1000)))].tobytes() for _ in range(n_tx)]
         self.reads = []
         for _ in range(n_reads):
@@ -118,7 +118,7 @@ class World:
             cand = bad[g:g + k] + ACGT[rng.integers(0, 4, 1)].tobytes() + bad[g + k - 1:g + 2 * k - 1]
             self.reads += [cand] * 2
             q["bubbles"].append(bad)
-        self.og = rbo.Graph(*sizes, 2, 2, 2, k, stranded, True, 5)
+        self.og = rbo.Graph(*sizes, *hashes, k, stranded, True, 5)
         self.packed = rbo.pack_reads(self.reads, [b"I" * len(s) for s in self.reads])
         self.og.add_reads(*self.packed, 3, 0)
         self.o = OracleSide(self.og)
@@ -129,7 +129,7 @@ class World:
 
     def device(self):
         if self.gg is None:
-            self.gg = BloomFilterDeBruijnGraph(*self.sizes, 2, 2, 2, self.k, self.stranded, True, rngSeed=5)
+            self.gg = BloomFilterDeBruijnGraph(*self.sizes, *self.hashes, self.k, self.stranded, True, rngSeed=5)
             self.gg.addReads(*self.packed, 3)
             assert (self.gg.exportFilter(N.DBGBF) == self.og.dbgbf_bytes()).all() and (self.gg.exportFilter(N.CBF) == self.og.cbf_bytes()).all()
         return self.gg

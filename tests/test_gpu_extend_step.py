@@ -36,7 +36,7 @@ def release_the_device_graphs():
 def device(w):
     """the device twin of a world's oracle graph: the same reads through addReads, the read-pair filter filled by the product path"""
     if id(w) not in DEVICES:
-        g = BloomFilterDeBruijnGraph(*w.sizes, 2, 2, 2, w.k, w.stranded, True, rngSeed=5)
+        g = BloomFilterDeBruijnGraph(*w.sizes, *w.hashes, w.k, w.stranded, True, rngSeed=5)
         g.setReadPairedKmerDistance(w.d)
         g.addReads(*w.packed, 3, storeReadPairedKmers=True)
         assert (g.exportFilter(N.DBGBF) == w.og.dbgbf_bytes()).all() and (g.exportFilter(N.CBF) == w.og.cbf_bytes()).all()

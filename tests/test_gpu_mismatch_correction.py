@@ -62,9 +62,9 @@ class World:
     leaves the substitution to the reverse scan.  The device graph is built from the same reads on request."""
     T = 3.0
 
-    def __init__(self, k, stranded, seed, n_tx=24, n_reads=3200, sizes=(1_600_033, 1_600_033, 1009)):
+    def __init__(self, k, stranded, seed, n_tx=24, n_reads=3200, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2)):
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.sizes, self.rng = k, stranded, sizes, rng
+        self.k, self.stranded, self.sizes, self.rng, self.hashes = k, stranded, sizes, rng, hashes
         self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(900, 1500)))].tobytes() for _ in range(n_tx)]
         self.reads = []
         for _ in range(n_reads):
@@ -84,7 +84,7 @@ class World:
             bad = plant(s, [m], rng)
             self.rev_only.append(bad)
             self.reads += [bad[m - k + 1:m + 1]] * 6
-        self.og = rbo.Graph(*sizes, 2, 2, 2, k, stranded, True, 5)
+        self.og = rbo.Graph(*sizes, *hashes, k, stranded, True, 5)
         self.packed = rbo.pack_reads(self.reads, [b"I" * len(s) for s in self.reads])
         self.og.add_reads(*self.packed, 3, 0)
         self.o = OracleSide(self.og)
@@ -92,7 +92,7 @@ class World:
 
     def device(self):
         if self.gg is None:
-            self.gg = BloomFilterDeBruijnGraph(*self.sizes, 2, 2, 2, self.k, self.stranded, True, rngSeed=5)
+            self.gg = BloomFilterDeBruijnGraph(*self.sizes, *self.hashes, self.k, self.stranded, True, rngSeed=5)
             self.gg.addReads(*self.packed, 3)
             assert (self.gg.exportFilter(N.DBGBF) == self.og.dbgbf_bytes()).all() and (self.gg.exportFilter(N.CBF) == self.og.cbf_bytes()).all()
         return self.gg

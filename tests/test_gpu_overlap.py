@@ -59,9 +59,9 @@ class World:
     — once each, so that their k-mers count 1 and the k-mers across the junction are absent — and the pairs to ask about"""
     D = 30                          # read-paired k-mer distance
 
-    def __init__(self, k, stranded, seed, n_tx=40, n_single=48):
+    def __init__(self, k, stranded, seed, n_tx=40, n_single=48, hashes=(2, 2, 2)):
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.rng = k, stranded, rng
+        self.k, self.stranded, self.rng, self.hashes = k, stranded, rng, hashes
         rnd = lambda n: ACGT[rng.integers(0, 4, n)].tobytes()
         self.tx = [rnd(500) for _ in range(n_tx)] + [rnd(3000) for _ in range(2)]
         reads = [t[a:a + 100] for t in self.tx for a in range(0, len(t) - 99, 10)]
@@ -135,7 +135,7 @@ class World:
         add("long-none", big[0:1400], self.tx[-2][0:1400])
         self.reads = reads
         self.sizes = (2_400_011, 2_400_011, 400_009)
-        self.og = rbo.Graph(*self.sizes, 2, 2, 2, k, stranded, True, 5)
+        self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
         self.og.set_read_pair_distance(self.D)
         self.packed = rbo.pack_reads(reads, [b"I" * len(s) for s in reads])
         self.og.add_reads(*self.packed, 3, 0)
@@ -145,7 +145,7 @@ class World:
 
     def device(self):
         if self.gg is None:
-            self.gg = BloomFilterDeBruijnGraph(*self.sizes, 2, 2, 2, self.k, self.stranded, True, rngSeed=5)
+            self.gg = BloomFilterDeBruijnGraph(*self.sizes, *self.hashes, self.k, self.stranded, True, rngSeed=5)
             self.gg.setReadPairedKmerDistance(self.D)
             self.gg.addReads(*self.packed, 3)
             assert (self.gg.exportFilter(N.DBGBF) == self.og.dbgbf_bytes()).all() and (self.gg.exportFilter(N.CBF) == self.og.cbf_bytes()).all()

@@ -54,10 +54,13 @@ def filter_lookup(bits, size, num_hash, k, keys):
 
 
 class World:
-    """a device graph and the oracle built from the same reads (storeReadPairedKmers) and fragments (addFragments)"""
+    """a device graph and the oracle built from the same reads (storeReadPairedKmers) and fragments (addFragments).  hashes: the numbers of
+    hash functions of dbgbf, cbf and the pair filters ((2, 2, pk_h) unless given; its last entry then is pk_h).  device False: the oracle alone."""
 
-    def __init__(self, k, stranded, pk_h, read_d, frag_d, seed):
+    def __init__(self, k, stranded, pk_h, read_d, frag_d, seed, hashes=None, device=True):
         rng = np.random.default_rng(seed)
+        self.hashes = hashes = (2, 2, pk_h) if hashes is None else tuple(hashes)
+        pk_h = hashes[2]
         self.k, self.stranded, self.pk_h, self.read_d, self.frag_d = k, stranded, pk_h, read_d, frag_d
         self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(800, 1600)))].tobytes() for _ in range(30)]
         left, right = [], []
@@ -67,17 +70,21 @@ class World:
             left.append(t[a:a + 150]); right.append(t[a + 150:a + 300][::-1].translate(COMP))
         self.left, self.right = left, right
         self.sizes = (400_009, 1_000_003, 2_000_003)
-        self.og = rbo.Graph(*self.sizes, 2, 2, pk_h, k, stranded, True, 5)
-        self.gg = BloomFilterDeBruijnGraph(*self.sizes, 2, 2, pk_h, k, stranded, True, rngSeed=5)
-        self.og.set_read_pair_distance(read_d); self.gg.setReadPairedKmerDistance(read_d)
+        self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
+        self.gg = BloomFilterDeBruijnGraph(*self.sizes, *hashes, k, stranded, True, rngSeed=5) if device else None
+        self.og.set_read_pair_distance(read_d)
+        if device:
+            self.gg.setReadPairedKmerDistance(read_d)
         for reads, rc in ((left, False), (right, True)):
             seq, q, off = rbo.pack_reads(reads, [b"I" * len(s) for s in reads])
             self.og.add_reads(seq, q, off, 3, rbo.STORE_READ_PAIRS | (rbo.REVCOMP if rc else 0))
-            self.gg.addReads(seq, q, off, 3, reverseComplement=rc, storeReadPairedKmers=True)
+            if device:
+                self.gg.addReads(seq, q, off, 3, reverseComplement=rc, storeReadPairedKmers=True)
         # fragments: FragmentsToGraphWorker (addFragments) on the device, the same inserts one by one in the oracle
         self.fsize = 1_000_003
         self.og.init_fragment_pairs(self.fsize, pk_h, frag_d)
-        self.gg.initializePairKmersBloomFilter(self.fsize, pk_h); self.gg.setFragPairedKmerDistance(frag_d)
+        if device:
+            self.gg.initializePairKmersBloomFilter(self.fsize, pk_h); self.gg.setFragPairedKmerDistance(frag_d)
         self.frags = []
         for _ in range(120):
             t = self.tx[int(rng.integers(0, len(self.tx)))]
@@ -85,7 +92,7 @@ class World:
             self.frags.append(t[a:a + L])
         mode = 0 if stranded else 1
         for s in self.frags:
-            hv, _ = rbo.hash_region(s, k, 2, mode)
+            hv, _ = rbo.hash_region(s, k, self.og.h, mode)
             for i in range(hv.shape[0]):
                 self.og.add_dbg_only(hv[i])
             for dd, add in ((read_d, self.og.add_read_pair), (frag_d, self.og.add_fragment_pair)):
@@ -93,11 +100,12 @@ class World:
                     p, _, _ = rbo.hash_pairs_region(s, k, pk_h, dd, mode)
                     for i in range(p.shape[0]):
                         add(p[i])
-        fseq, foff = _pack(self.frags)
-        self.gg.addFragments(ReadBatch.from_ascii(fseq, None, foff, 3), loadPairedKmers=True)
         self.bits = {N.RPKBF: self.og.rpkbf_bytes(), N.FPKBF: self.og.fpkbf_bytes()}
-        assert (self.gg.exportFilter(N.RPKBF) == self.bits[N.RPKBF]).all()
-        assert (self.gg.exportFilter(N.FPKBF) == self.bits[N.FPKBF]).all()
+        if device:
+            fseq, foff = _pack(self.frags)
+            self.gg.addFragments(ReadBatch.from_ascii(fseq, None, foff, 3), loadPairedKmers=True)
+            assert (self.gg.exportFilter(N.RPKBF) == self.bits[N.RPKBF]).all()
+            assert (self.gg.exportFilter(N.FPKBF) == self.bits[N.FPKBF]).all()
 
     def support(self, which, seqs):
         """per sequence: bool support over [0, nk) (False where p + d >= nk), from the oracle"""
