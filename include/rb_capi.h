@@ -447,6 +447,35 @@ typedef struct rb_extend_rec {          /* 32 bytes */
 } rb_extend_rec;
 int rb_graph_extend_se(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
                        char *out_bases /* n * (d + 2) */, float *out_count /* n * (d + 2), may be NULL */, rb_extend_rec *recs);
+/* Fragment-paired branch extension of host sequences — GraphUtils.extendRightPE / extendLeftPE (R/util/GraphUtils.java:6206-6414), the step of
+ * the transcript assembler's extendPE loop (:6567-6678), which it runs instead of extendSE whenever fragment-paired k-mers exist
+ * (R/RNABloom.java:1846-1851).  Arguments, orientation, candidates, walks, output layout, pieces and refusals are rb_graph_extend_se's; what
+ * differs, with d_r the read-paired and d_f the fragment-paired k-mer distance (neither is assumed the larger):
+ *   Only the last min(n, max(d_r, d_f)) k-mers of the list are read.  The walks' bound is M = d_f - 2.  With two or more candidates M is
+ *   lowered by one for every trailing k-mer of the list that graph.isRepeatKmer accepts, from the last k-mer backwards up to the first that
+ *   is not one (:6226-6233; SeqUtils.isRepeat(byte[]) :458-497 of the k-mer in its natural orientation, its counters signed bytes: the
+ *   homopolymer threshold round(0.9 k) is never reached from k = 142 on).  Every bound <= 0 acts alike, so the scan ends when M reaches 0 and
+ *   max_ext = max(M, 0) is reported.  A k-mer inside the scanned stretch with a letter outside ACGTU makes the reference throw (unless a base
+ *   count reaches the threshold in front of that letter): NONE, WHY_REPEAT_THROWS.  Such a letter further back than the scan reaches — more
+ *   than d_f - 2 k-mers from the end, or behind the first k-mer that is no repeat — is not seen, as in the reference for the second case.
+ *   pathMinCov is the minimum count of the last min(n, d_f) k-mers.  countKmerPairsPE / countKmerPairsReversedPE (:5792-5888): walked k-mer i
+ *   (0 <= i <= min(d_f - 1, size - 1)) is looked up with the list's k-mer n - d_r + i in the read-pair filter and with k-mer n - d_f + i in
+ *   the fragment-pair filter, each where that index lies in [0, n); last_partnered is the largest i either filter supports.  An extension is
+ *   scored only with read_pairs > 0 and frag_pairs > 0: Math.min(pathMinCov, median) * (read_pairs + frag_pairs) / (last + 1) in float32.
+ *   Else a first stretch of gap k-mers is skipped if (gap >= d_r - 1 and read_pairs == 0) or (gap >= d_f - 1 and frag_pairs == 0), and
+ *   otherwise goes to the second level with bound M - gap; the whole chain's pairs are counted, the first stretch's included.
+ *   Lower-case letters are read as upper-case ones, as everywhere in this library (the reference's isRepeat would throw on them).
+ * out_bases / out_count rows are d_f + 2 long.  Device scratch follows d_f as rb_graph_extend_se's follows d; the profile entry is "extend_pe".
+ * Refused as rb_graph_extend_se, and also: no fragment-pair filter (rb_graph_init_fragment_pairs not called, or destroyed); d_f < 2. */
+enum { RB_EXT_WHY_REPEAT_THROWS = 5 };                                                                                           /* rb_extend_pe_rec.why, after RB_EXT_WHY_* */
+typedef struct rb_extend_pe_rec {       /* 40 bytes */
+    int32_t outcome, why;
+    int32_t n_candidates, out_len /* k-mers */, read_pairs, frag_pairs, last_partnered, winner;
+    float score;
+    int32_t max_ext;                    /* the bound the first-level walks ran with, max(M, 0): d_f - 2 where the repeat scan did not run (or threw) */
+} rb_extend_pe_rec;
+int rb_graph_extend_pe(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
+                       char *out_bases /* n * (frag_d + 2) */, float *out_count /* n * (frag_d + 2), may be NULL */, rb_extend_pe_rec *recs);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

@@ -536,6 +536,33 @@ public class BloomFilterDeBruijnGraph {
         return res;
     }
 
+    /**
+     * GraphUtils.extendRightPE (direction 0) / extendLeftPE (direction 1) (src/rnabloom/util/GraphUtils.java:6206-6414) for a batch of sequences in ONE
+     * native call, as extendStepSE: the repeat scan, the walks, the look-ups in the read-pair and the fragment-pair filter and the scores run on
+     * the device.  Returns, per sequence, the bases the reference's returned k-mers add, in walking order, or null where the reference returns
+     * null (and where its isRepeat throws: recs[10 i + 1] == 5).  recs (optional, 10 * seqs.length ints) receives the records of NativeGraph.extendPE.
+     */
+    public String[] extendStepPE(String[] seqs, int direction, float[] minKmerCov, int[] recs) {
+        final int n = seqs.length;
+        if (minKmerCov.length != n) throw new IllegalArgumentException("extendStepPE: " + n + " sequences and " + minKmerCov.length + " floors");
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("extendStepPE: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        final int stride = Math.max(getFragPairedKmerDistance(), 0) + 2;
+        if ((long) n * stride > Integer.MAX_VALUE || 10L * n > Integer.MAX_VALUE)
+            throw new IllegalArgumentException("extendStepPE: " + n + " sequences of " + stride + " output bases do not fit one array: smaller batches");
+        if (recs != null && recs.length < 10 * n) throw new IllegalArgumentException("extendStepPE: recs holds " + recs.length + " ints, " + 10 * n + " are needed");
+        final byte[] bases = new byte[Math.max(n * stride, 1)];
+        final int[] rec = recs != null ? recs : new int[10 * n];
+        NativeGraph.extendPE(handle, text, off, n, direction, minKmerCov, bases, null, rec);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = rec[10 * i] != 0 ? new String(bases, i * stride, rec[10 * i + 3], java.nio.charset.StandardCharsets.ISO_8859_1) : null;
+        return res;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

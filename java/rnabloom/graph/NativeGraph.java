@@ -136,6 +136,13 @@ public final class NativeGraph {
      *  walking order; outCount (may be null) their counts.  Read-only. */
     public static native void extendSE(long h, ByteBuffer seq, long[] offsets, int n, int direction, float[] minKmerCov, byte[] outBases,
                                        float[] outCount, int[] recs);
+    /** Fragment-paired branch extension of n sequences (rb_graph_extend_pe; GraphUtils.extendRightPE / extendLeftPE, R/util/GraphUtils.java:6206-6414):
+     *  arguments as extendSE.  recs holds 10 ints per sequence — outcome, why (as extendSE; 5: the reference's isRepeat throws on a k-mer of the
+     *  repeat scan), candidates, k-mers returned, supporting read pairs, supporting fragment pairs, last partnered k-mer, winner,
+     *  Float.floatToRawIntBits(score), the bound the first-level walks ran with — and the bases the returned k-mers add are recs[10 i + 3] bytes
+     *  at outBases + i * (fragD + 2), in walking order; outCount (may be null) their counts.  Read-only. */
+    public static native void extendPE(long h, ByteBuffer seq, long[] offsets, int n, int direction, float[] minKmerCov, byte[] outBases,
+                                       float[] outCount, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

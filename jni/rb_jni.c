@@ -434,6 +434,26 @@ void FN(extendSE)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets,
     lr(e, offsets, po, JNI_ABORT); fr(e, minKmerCov, pf, JNI_ABORT); br(e, outBases, ob, 0); fr(e, outCount, oc, 0); ir(e, recs, rc8, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_extend_pe: a record (rb_extend_pe_rec, 40 bytes) is 10 ints to Java: outcome, why, n_candidates, out_len, read_pairs, frag_pairs, last_partnered, winner,
+ * the bits of the float score (Float.intBitsToFloat) and max_ext.  outBases holds n rows of frag_d + 2 bytes, outCount (may be null) as many floats */
+void FN(extendPE)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jint direction, jfloatArray minKmerCov, jbyteArray outBases,
+                  jfloatArray outCount, jintArray recs) {
+    (void)c;
+    /* what can be told without the graph's distance: an array per sequence is long enough for n, and the counts' array as long as the bases' */
+    if (n < 0 || (n > 0 && (!offsets || !minKmerCov || !outBases || !recs)) ||
+        (n > 0 && ((*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, minKmerCov) < n || (*e)->GetArrayLength(e, recs) / 10 < n ||
+                   (*e)->GetArrayLength(e, outBases) / 2 < n || (outCount && (*e)->GetArrayLength(e, outCount) < (*e)->GetArrayLength(e, outBases))))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "extendPE: an array is too short for n sequences");
+        return;
+    }
+    jlong *po = la(e, offsets);
+    jfloat *pf = fa(e, minKmerCov), *oc = fa(e, outCount);
+    jbyte *ob = ba(e, outBases);
+    jint *rc10 = ia(e, recs);
+    int rc = rb_graph_extend_pe(G(h), (const char *)direct(e, seq), (const int64_t *)po, n, direction, pf, (char *)ob, oc, (rb_extend_pe_rec *)rc10);
+    lr(e, offsets, po, JNI_ABORT); fr(e, minKmerCov, pf, JNI_ABORT); br(e, outBases, ob, 0); fr(e, outCount, oc, 0); ir(e, recs, rc10, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

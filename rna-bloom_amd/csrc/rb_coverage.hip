@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_repeat.hpp"
 
 using namespace rb;
 
@@ -23,57 +24,6 @@ constexpr int64_t COV_LONG = 4096;       // segments of at least this many windo
 
 // Math.round(float): floor(x + 1/2), exact in double for every float this file rounds
 __device__ __forceinline__ int64_t java_round(float x) { return (int64_t)floor((double)x + 0.5); }
-
-__device__ __forceinline__ uint32_t base_at(const uint32_t *cw32, uint32_t b) { return (cw32[b >> 4] >> (2u * (b & 15u))) & 3u; }
-
-// SeqUtils.isRepeat (:458-497) of the k bases at b0: a base count >= t1, a dinucleotide count of one phase >= t2 or a trinucleotide count of
-// one phase >= t3.  Each threshold is more than half of its phase's elements whenever it is above 1, so only a phase's majority element
-// can reach it: one pass finds each phase's majority candidate (Boyer-Moore vote), a second pass counts it.  A phase holds the pairs /
-// triples starting at offsets of one residue mod 2 / 3 (U is T: the batch's code of U is T's).
-__device__ __forceinline__ void vote(uint32_t &cand, uint32_t &cnt, uint32_t d) {
-    if (cnt == 0u) { cand = d; cnt = 1u; } else if (cand == d) ++cnt; else --cnt;
-}
-__device__ bool window_is_repeat(const uint32_t *cw32, uint32_t b0, int k, int t1, int t2, int t3) {
-    uint32_t cnt_ac = 0, cnt_gt = 0;                                 // base counts, 16 bits each
-    uint32_t d0 = 0, d1 = 0, dn0 = 0, dn1 = 0;                       // dinucleotide candidates / votes, phases 0 1
-    uint32_t e0 = 0, e1 = 0, e2 = 0, en0 = 0, en1 = 0, en2 = 0;      // trinucleotide candidates / votes, phases 0 1 2
-    uint32_t p1 = 0, p2 = 0;                                         // the previous two bases
-    uint32_t ph3 = 0;                                                // (j - 2) mod 3
-    for (int j = 0; j < k; ++j) {
-        const uint32_t c = base_at(cw32, b0 + (uint32_t)j);
-        if (c & 2u) cnt_gt += 1u << (16u * (c & 1u)); else cnt_ac += 1u << (16u * (c & 1u));
-        if (j >= 1) {
-            const uint32_t d = (p1 << 2) | c;
-            if ((uint32_t)(j - 1) & 1u) vote(d1, dn1, d); else vote(d0, dn0, d);
-        }
-        if (j >= 2) {
-            const uint32_t d = (p2 << 4) | (p1 << 2) | c;
-            if (ph3 == 0u) vote(e0, en0, d); else if (ph3 == 1u) vote(e1, en1, d); else vote(e2, en2, d);
-            ph3 = ph3 == 2u ? 0u : ph3 + 1u;
-        }
-        p2 = p1; p1 = c;
-    }
-    const int m1 = (int)max(max(cnt_ac & 0xffffu, cnt_ac >> 16), max(cnt_gt & 0xffffu, cnt_gt >> 16));
-    if (m1 >= t1) return true;
-    uint32_t n20 = 0, n21 = 0, n30 = 0, n31 = 0, n32 = 0;
-    p1 = p2 = 0; ph3 = 0;
-    for (int j = 0; j < k; ++j) {
-        const uint32_t c = base_at(cw32, b0 + (uint32_t)j);
-        if (j >= 1) {
-            const uint32_t d = (p1 << 2) | c;
-            if ((uint32_t)(j - 1) & 1u) n21 += d == d1 ? 1u : 0u; else n20 += d == d0 ? 1u : 0u;
-        }
-        if (j >= 2) {
-            const uint32_t d = (p2 << 4) | (p1 << 2) | c;
-            if (ph3 == 0u) n30 += d == e0 ? 1u : 0u; else if (ph3 == 1u) n31 += d == e1 ? 1u : 0u; else n32 += d == e2 ? 1u : 0u;
-            ph3 = ph3 == 2u ? 0u : ph3 + 1u;
-        }
-        p2 = p1; p1 = c;
-    }
-    // a phase with no element never returns (the reference's loop does not run); with elements, its majority's count decides
-    return (k > 1 && (int)n20 >= t2) || (k > 2 && (int)n21 >= t2) ||
-           (k > 2 && (int)n30 >= t3) || (k > 3 && (int)n31 >= t3) || (k > 4 && (int)n32 >= t3);
-}
 
 __device__ __forceinline__ bool window_usable(const uint32_t *vw, uint32_t b0, int k) {
     for (uint32_t b = b0; b < b0 + (uint32_t)k; ++b)

@@ -1,19 +1,23 @@
-// rb_extend.hip — paired-k-mer branch extension of host sequences (rb_graph_extend_se): GraphUtils.extendRightSE / extendLeftSE
-// (R/util/GraphUtils.java:6018-6204) over countKmerPairsSE / countKmerPairsReversedSE (:5718-5790) and naiveExtend{Right,Left}NoBackChecks
-// (:6888-6933, :7067-7112), on the device.  Only the last min(n, d) k-mers of a sequence matter to the step, so the host hands the device
-// the last (first, for the left-hand direction) d + k - 1 letters of every sequence; per piece the getKmers kernel leaves their hashes and
-// counts in device scratch and k_extend_se runs the step, a wavefront per sequence: the up to 4 first-level and 16 second-level naive
-// walks advance side by side, a lane per (walk, neighbour base), and the pair look-ups of a finished walk go a lane per walked k-mer.
-// Nothing is written to the graph (DESIGN.md §5 "Branch extension").
+// rb_extend.hip — paired-k-mer branch extension of host sequences: rb_graph_extend_se = GraphUtils.extendRightSE / extendLeftSE
+// (R/util/GraphUtils.java:6018-6204) over countKmerPairsSE / countKmerPairsReversedSE (:5718-5790), and rb_graph_extend_pe = extendRightPE /
+// extendLeftPE (:6206-6414) over countKmerPairsPE / countKmerPairsReversedPE (:5792-5888) and graph.isRepeatKmer, both on
+// naiveExtend{Right,Left}NoBackChecks (:6888-6933, :7067-7112), on the device.  Only the last min(n, d) k-mers of a sequence matter to the
+// step (PE: max(d_r, d_f)), so the host hands the device the last (first, for the left-hand direction) d + k - 1 letters of every sequence;
+// per piece the getKmers kernel leaves their hashes and counts in device scratch and k_extend runs the step, a wavefront per sequence: the up
+// to 4 first-level and 16 second-level naive walks advance side by side, a lane per (walk, neighbour base), and the pair look-ups of a finished
+// walk go a lane per walked k-mer.  The two steps are one body, the fragment-paired one a compile-time variant (template parameter PE).
+// Nothing is written to the graph (DESIGN.md §5 "Branch extension", "Fragment-paired branch extension").
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
+#include "rb_repeat.hpp"
 
 using namespace rb;
 
@@ -145,28 +149,44 @@ struct ExTail {
 // nt - d + i where that is not negative; k-mers below i0 are known to have no support (they were counted with the first level).  Each lane
 // hashes its k-mer from the chain's bases (rotations by one only) and forms Kmer.getKmerPairHashValue (R/graph/Kmer.java:65-67,
 // CanonicalKmer.java:61-72) with the partner on the side the direction puts it.
-__device__ void ex_count_pairs(const PairView &pf, const ExDir &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane, int &pairs, int &last) {
+//   PE — countKmerPairsPE / countKmerPairsReversedPE (:5792-5888): d is the fragment-paired distance, and walked k-mer i has two partners, slot
+// nt - d_r + i in pf (the read-pair filter) and slot nt - d + i in ff (the fragment-pair filter), each looked up only where its slot lies
+// in [0, nt); the reference's loop ends once both slots have run off the list, which is when neither test holds any more.  Neither distance
+// is assumed the larger.  fpairs counts the fragment pairs, last is the largest i either filter supports.  Here k-mers below i0 are NOT
+// known to be without support — a first stretch reaches the second level with support of one kind — so the caller adds what the first
+// stretch's own count gave for them (the same i, the same slots: min(d - 1, n - 1) only grows with n).
+struct ExPairs { int pairs, fpairs, last; };
+template <bool PE>
+__device__ ExPairs ex_count_pairs(const PairView &pf, const PairView &ff, int d_r, const ExDir &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane) {
     const int hi = min(d - 1, n - 1), k = (int)dr.uk;
-    pairs = 0; last = -1;
+    ExPairs res{0, 0, -1};
     for (int base = i0; base <= hi; base += 64) {
-        const int i = base + (int)lane, j = tl.nt - d + i;
-        bool hit = false;
-        if (i <= hi && j >= 0) {
+        const int i = base + (int)lane, j = tl.nt - d + i, jr = PE ? tl.nt - d_r + i : j;
+        const bool ask_f = i <= hi && j >= 0 && (!PE || j < tl.nt), ask_r = PE ? (i <= hi && jr >= 0 && jr < tl.nt) : ask_f;
+        bool hit = false, fhit = false;
+        if (ask_r || ask_f) {
             uint64_t A = 0, B = 0;
             for (int q = 0; q < k; ++q) {
                 A = rotl(A, 1) ^ seed_of(ch.base(i + 1 + q) ^ dr.xm);
                 B = rotl(B, 1) ^ seed_of(ch.base(i + k - q) ^ dr.ym);
             }
             const uint64_t f = dr.left ? B : A, r = dr.left ? A : B;
-            const uint64_t pfw = tl.F[tl.at(j)], prv = dr.stranded ? 0ull : tl.R[tl.at(j)];
-            uint64_t key;
-            if (!dr.left) key = dr.stranded ? combine(pfw, f) : smin(combine(pfw, f), combine(r, prv));      // partner on the left
-            else key = dr.stranded ? combine(f, pfw) : smin(combine(f, pfw), combine(prv, r));               // partner on the right
-            hit = pair_hit(pf, key);
+            auto key_of = [&](int slot) {
+                const uint64_t pfw = tl.F[tl.at(slot)], prv = dr.stranded ? 0ull : tl.R[tl.at(slot)];
+                if (!dr.left) return dr.stranded ? combine(pfw, f) : smin(combine(pfw, f), combine(r, prv));      // partner on the left
+                return dr.stranded ? combine(f, pfw) : smin(combine(f, pfw), combine(prv, r));                    // partner on the right
+            };
+            if constexpr (PE) pair_hit2(pf, [&] { return key_of(jr); }, ask_r, ff, [&] { return key_of(j); }, ask_f, hit, fhit);   // both filters' words before either test
+            else hit = pair_hit(pf, key_of(j));
         }
         const unsigned long long m = __ballot(hit);
-        if (m) { pairs += __popcll(m); last = base + 63 - (int)__builtin_clzll(m); }
+        if (m) { res.pairs += __popcll(m); res.last = base + 63 - (int)__builtin_clzll(m); }
+        if constexpr (PE) {
+            const unsigned long long mf = __ballot(fhit);
+            if (mf) { res.fpairs += __popcll(mf); res.last = max(res.last, base + 63 - (int)__builtin_clzll(mf)); }
+        }
     }
+    return res;
 }
 
 // count codes of a chain's k-mers: the first `gap` from a first-level row, the rest from a second-level row
@@ -179,12 +199,6 @@ struct ExCodes {
 // getMedianKmerCoverage(Collection) :229-247 of a chain's count codes
 __device__ float ex_median(const ExCodes &cc, uint32_t lane) {
     return median_code(cc, cc.n, lane);
-}
-
-__device__ __forceinline__ void ex_put(rb_extend_rec *rec, int outcome, int why, int n_cand, int out_len, int pairs, int last, int winner, float score) {
-    rb_extend_rec v;
-    v.outcome = outcome; v.why = why; v.n_candidates = n_cand; v.out_len = out_len; v.pairs = pairs; v.last_partnered = last; v.winner = winner; v.score = score;
-    *rec = v;
 }
 
 struct ExArgs {
@@ -202,6 +216,30 @@ struct ExArgs {
     float *out_c;                            // [pn][d + 2] or nullptr
     rb_extend_rec *recs;
 };
+// The fragment-paired step's arguments: d above is then the FRAGMENT-paired distance (bounds, rows and the output stride follow it), pf the
+// read-pair filter with its own distance d_r, ff the fragment-pair filter; t1 t2 t3 are isRepeat's thresholds for a k-mer (t1 "never" where
+// the reference's signed-byte counter cannot reach it); recs stays null and the records go to recs_pe.
+struct ExArgsPE : ExArgs {
+    PairView ff;
+    int d_r, t1, t2, t3;
+    rb_extend_pe_rec *recs_pe;
+};
+template <bool PE> using ExArgsT = std::conditional_t<PE, ExArgsPE, ExArgs>;
+
+// one record: fpairs and max_ext are the fragment-paired step's fields
+template <bool PE>
+__device__ __forceinline__ void ex_put(const ExArgsT<PE> &a, int64_t r, int outcome, int why, int n_cand, int out_len, int pairs, int fpairs, int last, int winner, float score, int max_ext) {
+    if constexpr (PE) {
+        rb_extend_pe_rec v;
+        v.outcome = outcome; v.why = why; v.n_candidates = n_cand; v.out_len = out_len; v.read_pairs = pairs; v.frag_pairs = fpairs; v.last_partnered = last;
+        v.winner = winner; v.score = score; v.max_ext = max_ext;
+        a.recs_pe[r] = v;
+    } else {
+        rb_extend_rec v;
+        v.outcome = outcome; v.why = why; v.n_candidates = n_cand; v.out_len = out_len; v.pairs = pairs; v.last_partnered = last; v.winner = winner; v.score = score;
+        a.recs[r] = v;
+    }
+}
 
 // the chain's first n k-mers as output: bases in walking order (upper-case A C G T) and, on request, counts
 __device__ void ex_emit(const ExArgs &a, int64_t r, const ExChain &ch, const ExCodes &cc, int n, uint32_t lane) {
@@ -213,14 +251,60 @@ __device__ void ex_emit(const ExArgs &a, int64_t r, const ExChain &ch, const ExC
     }
 }
 
-// extendRightSE / extendLeftSE of sequence r of the piece, by one wavefront with `row` for its walks
-__device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) {
+// The repeat scan of extendRightPE / extendLeftPE (:6226-6233, :6333-6340): the number of trailing k-mers of the list, from the last one
+// backwards, that graph.isRepeatKmer accepts (SeqUtils.isRepeat(byte[]) :458-497 of the k-mer in its natural orientation, also for the
+// left-hand direction), each lowering the bound by one.  Every bound <= 0 acts alike — a walk adds one k-mer and ++extensionLength > bound
+// ends it, and the second level's bound - gap (gap >= 1) is then <= 0 as well — so the scan stops once the bound would reach 0: at most
+// `most` = d - 2 k-mers are tested, which the d + k - 1 letters on the device always hold when the list is that long.  A lane per k-mer
+// (window_is_repeat on the batch's packed codes), a ballot, the run of leading ones.  A k-mer holding a letter outside ACGTU: the
+// reference's first loop returns true if a base count reaches t1 before that letter and else indexes an array with -1 and throws; -1 is
+// returned for the throw.  A bad letter further back than the scan reaches is not seen.
+__device__ int ex_trailing_repeats(const ExArgsPE &a, int64_t r, int nt, int most, uint32_t lane) {
+    const uint32_t *cw32 = reinterpret_cast<const uint32_t *>(a.codes + a.woff[r]);
+    const uint32_t *vw = a.valid + a.woff[r];
+    const int k = a.k, S = min(nt, most);
+    int count = 0;
+    for (int base = 0; base < S; base += 64) {
+        const int t = base + (int)lane;
+        int verdict = 0;                                          // 0 not a repeat (or past the scan), 1 a repeat, 2 the reference throws
+        if (t < S) {
+            const uint32_t p = (uint32_t)(a.direction ? t : nt - 1 - t);           // the k-mer's place in the text
+            int fb = 0;                                           // letters before the first one outside ACGTU
+            while (fb < k && ((vw[(p + (uint32_t)fb) >> 5] >> ((p + (uint32_t)fb) & 31u)) & 1u)) ++fb;
+            if (fb == k) verdict = window_is_repeat(cw32, p, k, a.t1, a.t2, a.t3) ? 1 : 0;
+            else {
+                int c4[4] = {0, 0, 0, 0};
+                for (int j = 0; j < fb; ++j) {
+                    const uint32_t c = base_at(cw32, p + (uint32_t)j);
+                    c4[0] += c == 0u; c4[1] += c == 1u; c4[2] += c == 2u; c4[3] += c == 3u;
+                }
+                verdict = max(max(c4[0], c4[1]), max(c4[2], c4[3])) >= a.t1 ? 1 : 2;
+            }
+        }
+        const unsigned long long not_rep = ~__ballot(verdict == 1);
+        if (not_rep == 0ull) { count += 64; continue; }
+        const int first = (int)__builtin_ctzll(not_rep);
+        count += first;
+        if ((__ballot(verdict == 2) >> first) & 1ull) return -1;
+        break;
+    }
+    return count;
+}
+
+// extendRightSE / extendLeftSE (PE: extendRightPE / extendLeftPE, :6206-6414) of sequence r of the piece, by one wavefront with `row` for its
+// walks.  What the PE step does differently is marked where it does: the bound M = d - 2 lowered by the repeat scan when there are two or
+// more candidates, pathMinCov over the last min(n, d) k-mers of a list that may be longer (it holds max(d_r, d) k-mers), two pair filters,
+// scoring only with support of both kinds, the two-sided skip test and the second level's bound M - gap.
+//   Rows (the layout above, D >= d).  A walk adds at most max(bound, 0) + 1 k-mers.  First level: candidate + walk <= max(M, 0) + 2 <= d
+// entries for every d >= 2 and every M <= d - 2, negative M included (2 <= d).  Second level: bound M - gap <= d - 3, so next candidate +
+// walk <= max(d - 3, 0) + 2 = max(d - 1, 2) <= d + 2 entries.  The SE step's bounds are d - 2 and d - gap: d and d + 1 entries.
+template <bool PE>
+__device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t lane) {
     const int k = a.k, d = a.d, D = a.D;
-    rb_extend_rec *rec = a.recs + r;
     const int64_t k0 = a.kof[r];
     const int nt = (int)(a.kof[r + 1] - k0);
     if (nt == 0) {                                            // shorter than k: the reference's callers never get here
-        if (lane == 0) ex_put(rec, RB_EXT_NONE, RB_EXT_WHY_SHORT, 0, 0, 0, -1, -1, 0.0f);
+        if (lane == 0) ex_put<PE>(a, r, RB_EXT_NONE, RB_EXT_WHY_SHORT, 0, 0, 0, 0, -1, -1, 0.0f, d - 2);
         return;
     }
     const int S1 = ex_l1b_stride(D), S2 = ex_l2b_stride(D), C2 = ex_l2_cap(D);
@@ -228,6 +312,11 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
     const ExDir dr{a.stranded, a.direction, (uint32_t)k, a.direction ? 3u : 0u, a.direction ? 0u : 3u};
     const ExTail tl{a.F + k0, a.R + k0, nt, a.direction};
     const uint32_t in = lane & 3u;
+    int d_r = d;
+    if constexpr (PE) d_r = a.d_r;
+    // (the fragment-pair filter's view takes the read-pair filter's kmul: both are kmul_of(k), and one copy less to hold keeps the scratch
+    // instantiation at 168 registers)
+    const PairView ff = [&]() -> PairView { if constexpr (PE) return PairView{a.ff.bits, a.ff.mod, a.ff.num_hash, a.pf.kmul}; else return a.pf; }();
 
     // the last k-mer's bases in walking order, four a byte (lane l packs bases 4 l .. 4 l + 3); one outside ACGTU ends the sequence
     {
@@ -245,11 +334,15 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
         }
         if (4 * (int)lane < k) seed[lane] = (uint8_t)byte;
         if (__ballot(bad)) {
-            if (lane == 0) ex_put(rec, RB_EXT_NONE, RB_EXT_WHY_INVALID_SEED, 0, 0, 0, -1, -1, 0.0f);
+            if (lane == 0) ex_put<PE>(a, r, RB_EXT_NONE, RB_EXT_WHY_INVALID_SEED, 0, 0, 0, 0, -1, -1, 0.0f, d - 2);
             return;
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // PE: the repeat scan, used below only where there are two or more candidates.  It runs here, for every sequence, because nothing of the
+    // walks is held in registers yet (behind the candidates' probes it costs the kernel a dozen registers); one round of a lane per k-mer as a rule
+    int rep = 0;
+    if constexpr (PE) rep = ex_trailing_repeats(a, r, nt, d - 2, lane);
     const float min_cov = a.floors[r];
 
     // candidates: neighbours of the last k-mer with count >= 1, whatever the floor (Kmer.getSuccessors(k, numHash, graph), R/graph/Kmer.java:228-230)
@@ -266,18 +359,30 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
     const uint32_t mask0 = (uint32_t)__ballot(lane < 4u && code >= 1u) & 0xFu;
     const int n_cand = __popc(mask0);
     if (n_cand == 0) {
-        if (lane == 0) ex_put(rec, RB_EXT_NONE, RB_EXT_WHY_NO_CANDIDATE, 0, 0, 0, -1, -1, 0.0f);
+        if (lane == 0) ex_put<PE>(a, r, RB_EXT_NONE, RB_EXT_WHY_NO_CANDIDATE, 0, 0, 0, 0, -1, -1, 0.0f, d - 2);
         return;
     }
 
-    // first level: candidate c's walk is held by lanes 4 c .. 4 c + 3 and fills first-level row c, bound d - 2 (:6026)
+    // the walks' bound (:6026, :6215); PE with two or more candidates: less the trailing repeat k-mers, not below 0 (ex_trailing_repeats)
+    int M = d - 2;
+    if constexpr (PE) {
+        if (n_cand > 1) {
+            if (rep < 0) {
+                if (lane == 0) ex_put<PE>(a, r, RB_EXT_NONE, RB_EXT_WHY_REPEAT_THROWS, n_cand, 0, 0, 0, -1, -1, 0.0f, d - 2);
+                return;
+            }
+            M -= rep;
+        }
+    }
+
+    // first level: candidate c's walk is held by lanes 4 c .. 4 c + 3 and fills first-level row c, bound M
     const uint32_t c1 = (lane >> 2) & 3u;
     ExWalk w1;
     w1.A = ex_shfl64(nA, (int)c1); w1.B = ex_shfl64(nB, (int)c1);
     const uint32_t code1 = (uint32_t)__shfl((int)code, (int)c1, 64);
     w1.alive = lane < 16u && ((mask0 >> c1) & 1u);
     w1.start_f = dr.fwd(w1.A, w1.B);
-    w1.len = 1; w1.added = 0; w1.bound = d - 2; w1.cap = D; w1.off = 0;
+    w1.len = 1; w1.added = 0; w1.bound = M; w1.cap = D; w1.off = 0;
     uint8_t *crow1 = l1c + c1 * D, *brow1 = l1b + c1 * S1;
     if (w1.alive && in == 0u) { crow1[0] = (uint8_t)code1; ex_put2(brow1, 0, c1); }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -287,32 +392,40 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
 #pragma unroll
     for (int c = 0; c < 4; ++c) len1[c] = __shfl(w1.len, 4 * c, 64);
 
-    if (n_cand == 1) {                                        // :6030-6035: the only candidate and its walk, unscored and untrimmed
+    if (n_cand == 1) {                                        // :6030-6035, :6219-6224: the only candidate and its walk, unscored and untrimmed
         const int c = __builtin_ctz(mask0), n = len1[c];
         ex_emit(a, r, ExChain{seed, l1b + c * S1, l1b + c * S1, k, EX_NO_GAP}, ExCodes{l1c + c * D, l1c + c * D, EX_NO_GAP, n}, n, lane);
-        if (lane == 0) ex_put(rec, RB_EXT_SINGLE, RB_EXT_WHY_FOUND, 1, n, 0, -1, c, 0.0f);
+        if (lane == 0) ex_put<PE>(a, r, RB_EXT_SINGLE, RB_EXT_WHY_FOUND, 1, n, 0, 0, -1, c, 0.0f, M);
         return;
     }
 
-    // pathMinCov: the minimum count of the last min(n, d) k-mers (:6037)
+    // pathMinCov: the minimum count of the last min(n, d) k-mers (:6037, :6235) — all the device holds for SE, the list's last d slots for PE
     float path_min = INFINITY;
-    for (int p = (int)lane; p < nt; p += 64) path_min = fminf(path_min, a.cnt[k0 + p]);
+    if constexpr (PE) {
+        for (int j = max(nt - d, 0) + (int)lane; j < nt; j += 64) path_min = fminf(path_min, a.cnt[k0 + tl.at(j)]);
+    } else {
+        for (int p = (int)lane; p < nt; p += 64) path_min = fminf(path_min, a.cnt[k0 + p]);
+    }
     for (int s = 32; s > 0; s >>= 1) path_min = fminf(path_min, __shfl_xor(path_min, s, 64));
 
-    // the first stretches' pairs (:6047); an unsupported stretch shorter than d - 1 goes one branch further (:6067-6076)
-    int pairs1[4], last1[4];
+    // the first stretches' pairs (:6047); an unsupported stretch shorter than d - 1 goes one branch further (:6067-6076).  PE (:6249, :6268):
+    // a stretch without support of BOTH kinds goes further unless it is d_r - 1 long without a read pair or d - 1 long without a fragment pair
+    int pairs1[4], fpairs1[4], last1[4];
     uint32_t l2mask = 0;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        pairs1[c] = 0; last1[c] = -1;
+        pairs1[c] = 0; fpairs1[c] = 0; last1[c] = -1;
         if ((mask0 >> c) & 1u) {
-            ex_count_pairs(a.pf, dr, ExChain{seed, l1b + c * S1, l1b + c * S1, k, EX_NO_GAP}, tl, d, len1[c], 0, lane, pairs1[c], last1[c]);
-            if (pairs1[c] == 0 && len1[c] < d - 1) l2mask |= 1u << c;
+            const ExPairs cp = ex_count_pairs<PE>(a.pf, ff, d_r, dr, ExChain{seed, l1b + c * S1, l1b + c * S1, k, EX_NO_GAP}, tl, d, len1[c], 0, lane);
+            pairs1[c] = cp.pairs; fpairs1[c] = cp.fpairs; last1[c] = cp.last;
+            if constexpr (PE) {
+                if (!(cp.pairs > 0 && cp.fpairs > 0) && !((len1[c] >= d_r - 1 && cp.pairs == 0) || (len1[c] >= d - 1 && cp.fpairs == 0))) l2mask |= 1u << c;
+            } else if (cp.pairs == 0 && len1[c] < d - 1) l2mask |= 1u << c;
         }
     }
 
     // second level: the successors (count >= 1) of a first stretch's last k-mer — lane 4 c + c2 of the first-level lanes finds candidate
-    // (c, c2), which is second-level walk 4 c + c2, held by lanes 16 c + 4 c2 .. + 3, bound d - gap (:6079)
+    // (c, c2), which is second-level walk 4 c + c2, held by lanes 16 c + 4 c2 .. + 3, bound d - gap (:6079; PE: M - gap, :6278)
     uint32_t mask2 = 0;
     ExWalk w2;
     w2.alive = false; w2.len = 0;
@@ -332,154 +445,186 @@ __device__ void ex_one(const ExArgs &a, int64_t r, uint8_t *row, uint32_t lane) 
         const uint32_t code2 = (uint32_t)__shfl((int)code, (int)wid, 64);
         w2.alive = (mask2 >> wid) & 1u;
         w2.start_f = dr.fwd(w2.A, w2.B);
-        w2.len = 1; w2.added = 0; w2.bound = d - gap; w2.cap = C2; w2.off = gap;
+        w2.len = 1; w2.added = 0; w2.bound = (PE ? M : d) - gap; w2.cap = C2; w2.off = gap;
         if (w2.alive && in == 0u) { crow2[0] = (uint8_t)code2; ex_put2(brow2, 0, wid & 3u); }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         ex_run_walks(a.fv, dr, min_cov, ch2, crow2, brow2, w2, lane);
     }
 
-    // scores in the reference's order: candidate c's first stretch where it is supported, else its second-level extensions (:6051-6105)
+    // scores in the reference's order: candidate c's first stretch where it is supported, else its second-level extensions (:6051-6105).  A
+    // PE chain's counts are the first stretch's plus those of the k-mers behind it (ex_count_pairs), its score counts pairs of both kinds
     float best = 0.0f, best_cov = 0.0f;
-    int b_level = 0, b_win = -1, b_len = 0, b_pairs = 0, b_last = -1;
+    int b_level = 0, b_win = -1, b_len = 0, b_pairs = 0, b_fpairs = 0, b_last = -1;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         if (!((mask0 >> c) & 1u)) continue;
-        if (pairs1[c] > 0) {
+        if (pairs1[c] > 0 && (!PE || fpairs1[c] > 0)) {
             const float cov = ex_median(ExCodes{l1c + c * D, l1c + c * D, EX_NO_GAP, len1[c]}, lane);
-            const float score = fminf(path_min, cov) * (float)pairs1[c] / (float)(last1[c] + 1);
+            const float score = fminf(path_min, cov) * (float)(PE ? pairs1[c] + fpairs1[c] : pairs1[c]) / (float)(last1[c] + 1);
             if (score > best || (score == best && cov > best_cov)) {
-                best = score; best_cov = cov; b_level = 1; b_win = c; b_len = last1[c] + 1; b_pairs = pairs1[c]; b_last = last1[c];
+                best = score; best_cov = cov; b_level = 1; b_win = c; b_len = last1[c] + 1; b_pairs = pairs1[c]; b_fpairs = fpairs1[c]; b_last = last1[c];
             }
         } else if ((l2mask >> c) & 1u) {
             for (int c2 = 0; c2 < 4; ++c2) {
                 const int w = 4 * c + c2;
                 if (!((mask2 >> w) & 1u)) continue;
                 const int n = len1[c] + __shfl(w2.len, 4 * w, 64);
-                int pairs, last;
-                ex_count_pairs(a.pf, dr, ExChain{seed, l1b + c * S1, l2b + w * S2, k, len1[c]}, tl, d, n, len1[c], lane, pairs, last);
-                if (pairs == 0) continue;
+                ExPairs cp = ex_count_pairs<PE>(a.pf, ff, d_r, dr, ExChain{seed, l1b + c * S1, l2b + w * S2, k, len1[c]}, tl, d, n, len1[c], lane);
+                if constexpr (PE) {
+                    cp.pairs += pairs1[c]; cp.fpairs += fpairs1[c]; cp.last = max(cp.last, last1[c]);
+                    if (cp.pairs == 0 || cp.fpairs == 0) continue;
+                } else if (cp.pairs == 0) continue;
                 const float cov = ex_median(ExCodes{l1c + c * D, l2c + w * C2, len1[c], n}, lane);
-                const float score = fminf(path_min, cov) * (float)pairs / (float)(last + 1);
+                const float score = fminf(path_min, cov) * (float)(PE ? cp.pairs + cp.fpairs : cp.pairs) / (float)(cp.last + 1);
                 if (score > best || (score == best && cov > best_cov)) {
-                    best = score; best_cov = cov; b_level = 2; b_win = c | (c2 << 4); b_len = last + 1; b_pairs = pairs; b_last = last;
+                    best = score; best_cov = cov; b_level = 2; b_win = c | (c2 << 4); b_len = cp.last + 1; b_pairs = cp.pairs; b_fpairs = cp.fpairs; b_last = cp.last;
                 }
             }
         }
     }
     if (b_level == 0) {
-        if (lane == 0) ex_put(rec, RB_EXT_NONE, RB_EXT_WHY_NO_SUPPORT, n_cand, 0, 0, -1, -1, 0.0f);
+        if (lane == 0) ex_put<PE>(a, r, RB_EXT_NONE, RB_EXT_WHY_NO_SUPPORT, n_cand, 0, 0, 0, -1, -1, 0.0f, M);
         return;
     }
     // the winner, trimmed to its last supported k-mer (:6060-6064)
     const int c = b_win & 3, w = 4 * c + (b_win >> 4);
     if (b_level == 1) ex_emit(a, r, ExChain{seed, l1b + c * S1, l1b + c * S1, k, EX_NO_GAP}, ExCodes{l1c + c * D, l1c + c * D, EX_NO_GAP, b_len}, b_len, lane);
     else ex_emit(a, r, ExChain{seed, l1b + c * S1, l2b + w * S2, k, len1[c]}, ExCodes{l1c + c * D, l2c + w * C2, len1[c], b_len}, b_len, lane);
-    if (lane == 0) ex_put(rec, b_level == 1 ? RB_EXT_FIRST : RB_EXT_SECOND, RB_EXT_WHY_FOUND, n_cand, b_len, b_pairs, b_last, b_win, best);
+    if (lane == 0) ex_put<PE>(a, r, b_level == 1 ? RB_EXT_FIRST : RB_EXT_SECOND, RB_EXT_WHY_FOUND, n_cand, b_len, b_pairs, b_fpairs, b_last, b_win, best, M);
 }
 
-// A wavefront per sequence, taking sequences in turn.  LDS_ROW: the wavefront's rows are in LDS (d <= EX_LDS_D); else in its slot of `scratch`.
-template <bool LDS_ROW>
-__global__ void __launch_bounds__(EX_TPB) k_extend_se(ExArgs a, uint8_t *scratch, size_t row_bytes) {
+// A wavefront per sequence, taking sequences in turn.  PE: the fragment-paired step.  LDS_ROW: the wavefront's rows are in LDS
+// (d <= EX_LDS_D); else in its slot of `scratch`.
+template <bool PE, bool LDS_ROW>
+__global__ void __launch_bounds__(EX_TPB) k_extend(ExArgsT<PE> a, uint8_t *scratch, size_t row_bytes) {
     __shared__ __attribute__((aligned(16))) uint8_t s_row[EX_WAVES][LDS_ROW ? ex_row_bytes(EX_LDS_D) : 16];
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const int64_t slot = (int64_t)blockIdx.x * EX_WAVES + wv, n_slots = (int64_t)gridDim.x * EX_WAVES;
     uint8_t *row;
     if constexpr (LDS_ROW) row = s_row[wv]; else row = scratch + (size_t)slot * row_bytes;
     for (int64_t r = slot; r < a.pn; r += n_slots) {
-        ex_one(a, r, row, lane);
+        ex_one<PE>(a, r, row, lane);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
 }
 
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
+// Math.round(float) of the thresholds of SeqUtils.isRepeat: floor(x + 1/2), exact in double
+inline int java_round(float x) { return (int)std::floor((double)x + 0.5); }
+
+template <bool PE> void ex_blank(std::conditional_t<PE, rb_extend_pe_rec, rb_extend_rec> &v, int d) {
+    v.outcome = RB_EXT_NONE; v.why = RB_EXT_WHY_SHORT; v.n_candidates = 0; v.out_len = 0; v.last_partnered = -1; v.winner = -1; v.score = 0.0f;
+    if constexpr (PE) { v.read_pairs = 0; v.frag_pairs = 0; v.max_ext = d - 2; } else v.pairs = 0;
+}
+
+// rb_graph_extend_se (PE false) and rb_graph_extend_pe (PE true): the checks, the cut of every sequence to the letters the step reads, and the
+// pieces.  d is the distance the bounds, the rows and the output stride follow (read-paired for SE, fragment-paired for PE); the device
+// gets the last (first, for the left-hand direction) max(d_r, d) + k - 1 letters of a sequence.
+template <bool PE>
+void extend_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov, char *out_bases, float *out_count,
+                 std::conditional_t<PE, rb_extend_pe_rec, rb_extend_rec> *recs) {
+    using Rec = std::conditional_t<PE, rb_extend_pe_rec, rb_extend_rec>;
+    const char *who = PE ? "rb_graph_extend_pe" : "rb_graph_extend_se";
+    RB_REQUIRE(g, "%s: null handle", who);
+    RB_REQUIRE(!g->shard, "%s: not available on a shard handle", who);
+    RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
+    RB_REQUIRE(g->rpk.bits, "%s: the graph has no read-paired k-mer filter (created without useReadPairedKmers, or destroyed)", who);
+    if (PE) RB_REQUIRE(g->fpk.bits, "%s: the graph has no fragment-paired k-mer filter (rb_graph_init_fragment_pairs was not called, or it was destroyed)", who);
+    const int d_r = g->read_d, d = PE ? g->frag_d : d_r, k = g->k;
+    RB_REQUIRE(d_r >= 2, "%s: the read-paired k-mer distance is %d (the step needs d >= 2)", who, d_r);
+    if (PE) RB_REQUIRE(d >= 2, "%s: the fragment-paired k-mer distance is %d (the step needs d >= 2)", who, d);
+    RB_REQUIRE(direction == 0 || direction == 1, "%s: direction must be 0 (right) or 1 (left), not %d", who, direction);
+    RB_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
+    if (n == 0) return;
+    RB_REQUIRE(offsets && min_kmer_cov && out_bases && recs, "%s: null argument", who);
+    std::vector<int64_t> ko((size_t)n + 1), to((size_t)n + 1, 0);
+    kmer_offsets(offsets, n, k, ko.data(), who);
+    RB_REQUIRE(offsets[n] == offsets[0] || seq, "%s: null sequence text", who);
+    for (int64_t i = 0; i < n; ++i)
+        RB_REQUIRE(std::isfinite(min_kmer_cov[i]) && min_kmer_cov[i] >= 0.0f, "%s: min_kmer_cov[%lld] must be finite and not negative", who, (long long)i);
+    // the step reads the last min(nk, max(d_r, d)) k-mers of a sequence only: the device gets that many k-mers' letters at the end it extends
+    const int64_t keep = (int64_t)std::max(d_r, d) + k - 1, stride = (int64_t)d + 2;
+    for (int64_t i = 0; i < n; ++i) to[(size_t)i + 1] = to[(size_t)i] + std::min(offsets[i + 1] - offsets[i], keep);
+    std::vector<char> text((size_t)to[(size_t)n]);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = offsets[i + 1] - offsets[i], take = to[(size_t)i + 1] - to[(size_t)i];
+        if (take) memcpy(text.data() + to[(size_t)i], seq + (direction ? offsets[i] : offsets[i] + len - take), (size_t)take);
+    }
+    kmer_offsets(to.data(), n, k, ko.data(), nullptr);
+    // what no kernel touches: sequences of pieces without a k-mer, rows past a result's length
+    for (int64_t i = 0; i < n; ++i) ex_blank<PE>(recs[i], d);
+    memset(out_bases, 0, (size_t)(n * stride));
+    if (out_count) memset(out_count, 0, (size_t)(n * stride) * 4);
+    if (ko[(size_t)n] == 0) return;
+    RB_HIP(hipSetDevice(g->p.device));
+    HostPin pin_b(out_bases, (size_t)(n * stride)), pin_c(out_count, out_count ? (size_t)(n * stride) * 4 : 0), pin_r(recs, (size_t)n * sizeof(Rec));
+    QueryLease q(g);
+    hipStream_t s = q.c->st;
+    const bool lds = d <= EX_LDS_D;
+    const size_t row_bytes = ex_row_bytes(lds ? EX_LDS_D : d);
+    // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, floors, records, results and — for a
+    // distance past the LDS row — the wavefronts' walk rows; with profiling on the kernels of every piece are timed: entry "extend_se" / "extend_pe"
+    std::vector<int64_t> tab;
+    for_each_host_piece(g, s, text.data(), to.data(), ko.data(), n, PE ? "extend_pe" : "extend_se", [&](HostPiece &pc) {
+        const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
+        tab.assign((size_t)pn + 1, 0);
+        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
+        const rb_batch *b = pc.batch();
+        const int64_t slots = lds ? pn : std::min<int64_t>(pn, EX_SCRATCH_SLOTS);
+        const unsigned blocks = blocks_for(slots, EX_WAVES);
+        const size_t o_fl = up16((size_t)pt * 4), o_rec = up16(o_fl + (size_t)pn * 4), o_b = o_rec + (size_t)pn * sizeof(Rec),
+                     o_c = up16(o_b + (size_t)(pn * stride)), o_row = up16(o_c + (out_count ? (size_t)(pn * stride) * 4 : 0));
+        q.c->b0.reserve(tab.size() * 8);
+        q.c->b1.reserve((size_t)pt * 8);
+        q.c->b2.reserve((size_t)pt * 8);
+        q.c->b3.reserve(o_row + (lds ? 0 : (size_t)blocks * EX_WAVES * row_bytes) + 16);
+        uint8_t *base3 = q.c->b3.as<uint8_t>();
+        ExArgsT<PE> a;
+        a.fv = g->view(0, 0);
+        a.pf = PairView{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
+        a.stranded = (int)g->stranded; a.k = k; a.d = d; a.direction = direction; a.D = lds ? EX_LDS_D : d;
+        a.pn = pn;
+        a.kof = q.c->b0.as<int64_t>();
+        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
+        a.cnt = reinterpret_cast<float *>(base3);
+        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
+        a.floors = reinterpret_cast<float *>(base3 + o_fl);
+        Rec *d_recs = reinterpret_cast<Rec *>(base3 + o_rec);
+        if constexpr (PE) {
+            a.recs = nullptr; a.recs_pe = d_recs;
+            a.ff = PairView{g->fpk.bits, g->fpk.mod, g->fpk.num_hash, kmul_of(k)};
+            a.d_r = d_r;
+            // isRepeat keeps its counters in signed bytes: a threshold above 127 is never reached (t1 from k = 142 on; t2, t3 stay below for k <= RB_MAX_K)
+            const int t1 = java_round((float)k * 0.9f);
+            a.t1 = t1 > 127 ? INT32_MAX : t1; a.t2 = java_round((float)(k / 2) * 0.9f); a.t3 = java_round((float)(k / 3) * 0.9f);
+        } else a.recs = d_recs;
+        a.out_b = base3 + o_b;
+        a.out_c = out_count ? reinterpret_cast<float *>(base3 + o_c) : nullptr;
+        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemcpyAsync(base3 + o_fl, min_kmer_cov + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemsetAsync(base3 + o_b, 0, o_row - o_b, s));        // (what no wavefront writes comes back as zeros, whatever the cuts)
+        pc.kernels_begin();
+        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        if (lds) hipLaunchKernelGGL((k_extend<PE, true>), dim3(blocks), dim3(EX_TPB), 0, s, a, (uint8_t *)nullptr, row_bytes);
+        else hipLaunchKernelGGL((k_extend<PE, false>), dim3(blocks), dim3(EX_TPB), 0, s, a, base3 + o_row, row_bytes);
+        RB_HIP(hipGetLastError());
+        pc.kernels_end();
+        RB_HIP(hipMemcpyAsync(recs + ra, d_recs, (size_t)pn * sizeof(Rec), hipMemcpyDeviceToHost, s));
+        RB_HIP(hipMemcpyAsync(out_bases + ra * stride, a.out_b, (size_t)(pn * stride), hipMemcpyDeviceToHost, s));
+        if (out_count) RB_HIP(hipMemcpyAsync(out_count + ra * stride, a.out_c, (size_t)(pn * stride) * 4, hipMemcpyDeviceToHost, s));
+    });
+}
+
 }  // namespace
 
 extern "C" {
 int rb_graph_extend_se(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov, char *out_bases,
                        float *out_count, rb_extend_rec *recs) {
-    return guarded([&] {
-        RB_REQUIRE(g, "rb_graph_extend_se: null handle");
-        RB_REQUIRE(!g->shard, "rb_graph_extend_se: not available on a shard handle");
-        RB_REQUIRE(g->dbg.bits && g->cbf, "rb_graph_extend_se: dbgbf or the counting filter has been destroyed");
-        RB_REQUIRE(g->rpk.bits, "rb_graph_extend_se: the graph has no read-paired k-mer filter (created without useReadPairedKmers, or destroyed)");
-        const int d = g->read_d, k = g->k;
-        RB_REQUIRE(d >= 2, "rb_graph_extend_se: the read-paired k-mer distance is %d (the step needs d >= 2)", d);
-        RB_REQUIRE(direction == 0 || direction == 1, "rb_graph_extend_se: direction must be 0 (right) or 1 (left), not %d", direction);
-        RB_REQUIRE(n >= 0, "rb_graph_extend_se: n = %lld", (long long)n);
-        if (n == 0) return;
-        RB_REQUIRE(offsets && min_kmer_cov && out_bases && recs, "rb_graph_extend_se: null argument");
-        std::vector<int64_t> ko((size_t)n + 1), to((size_t)n + 1, 0);
-        kmer_offsets(offsets, n, k, ko.data(), "rb_graph_extend_se");
-        RB_REQUIRE(offsets[n] == offsets[0] || seq, "rb_graph_extend_se: null sequence text");
-        for (int64_t i = 0; i < n; ++i)
-            RB_REQUIRE(std::isfinite(min_kmer_cov[i]) && min_kmer_cov[i] >= 0.0f, "rb_graph_extend_se: min_kmer_cov[%lld] must be finite and not negative", (long long)i);
-        // the step reads the last min(nk, d) k-mers of a sequence only: the device gets the d + k - 1 letters at the end it extends
-        const int64_t keep = (int64_t)d + k - 1, stride = (int64_t)d + 2;
-        for (int64_t i = 0; i < n; ++i) to[(size_t)i + 1] = to[(size_t)i] + std::min(offsets[i + 1] - offsets[i], keep);
-        std::vector<char> text((size_t)to[(size_t)n]);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t len = offsets[i + 1] - offsets[i], take = to[(size_t)i + 1] - to[(size_t)i];
-            if (take) memcpy(text.data() + to[(size_t)i], seq + (direction ? offsets[i] : offsets[i] + len - take), (size_t)take);
-        }
-        kmer_offsets(to.data(), n, k, ko.data(), nullptr);
-        // what no kernel touches: sequences of pieces without a k-mer, rows past a result's length
-        for (int64_t i = 0; i < n; ++i) {
-            rb_extend_rec &v = recs[i];
-            v.outcome = RB_EXT_NONE; v.why = RB_EXT_WHY_SHORT; v.n_candidates = 0; v.out_len = 0; v.pairs = 0; v.last_partnered = -1; v.winner = -1; v.score = 0.0f;
-        }
-        memset(out_bases, 0, (size_t)(n * stride));
-        if (out_count) memset(out_count, 0, (size_t)(n * stride) * 4);
-        if (ko[(size_t)n] == 0) return;
-        RB_HIP(hipSetDevice(g->p.device));
-        HostPin pin_b(out_bases, (size_t)(n * stride)), pin_c(out_count, out_count ? (size_t)(n * stride) * 4 : 0), pin_r(recs, (size_t)n * sizeof(rb_extend_rec));
-        QueryLease q(g);
-        hipStream_t s = q.c->st;
-        const bool lds = d <= EX_LDS_D;
-        const size_t row_bytes = ex_row_bytes(lds ? EX_LDS_D : d);
-        // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, floors, records, results and — for a
-        // distance past the LDS row — the wavefronts' walk rows; with profiling on the kernels of every piece are timed: entry "extend_se"
-        std::vector<int64_t> tab;
-        for_each_host_piece(g, s, text.data(), to.data(), ko.data(), n, "extend_se", [&](HostPiece &pc) {
-            const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
-            tab.assign((size_t)pn + 1, 0);
-            for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-            const rb_batch *b = pc.batch();
-            const int64_t slots = lds ? pn : std::min<int64_t>(pn, EX_SCRATCH_SLOTS);
-            const unsigned blocks = blocks_for(slots, EX_WAVES);
-            const size_t o_fl = up16((size_t)pt * 4), o_rec = up16(o_fl + (size_t)pn * 4), o_b = o_rec + (size_t)pn * sizeof(rb_extend_rec),
-                         o_c = up16(o_b + (size_t)(pn * stride)), o_row = up16(o_c + (out_count ? (size_t)(pn * stride) * 4 : 0));
-            q.c->b0.reserve(tab.size() * 8);
-            q.c->b1.reserve((size_t)pt * 8);
-            q.c->b2.reserve((size_t)pt * 8);
-            q.c->b3.reserve(o_row + (lds ? 0 : (size_t)blocks * EX_WAVES * row_bytes) + 16);
-            uint8_t *base3 = q.c->b3.as<uint8_t>();
-            ExArgs a;
-            a.fv = g->view(0, 0);
-            a.pf = PairView{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
-            a.stranded = (int)g->stranded; a.k = k; a.d = d; a.direction = direction; a.D = lds ? EX_LDS_D : d;
-            a.pn = pn;
-            a.kof = q.c->b0.as<int64_t>();
-            a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-            a.cnt = reinterpret_cast<float *>(base3);
-            a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
-            a.floors = reinterpret_cast<float *>(base3 + o_fl);
-            a.recs = reinterpret_cast<rb_extend_rec *>(base3 + o_rec);
-            a.out_b = base3 + o_b;
-            a.out_c = out_count ? reinterpret_cast<float *>(base3 + o_c) : nullptr;
-            RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemcpyAsync(base3 + o_fl, min_kmer_cov + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemsetAsync(base3 + o_b, 0, o_row - o_b, s));        // (what no wavefront writes comes back as zeros, whatever the cuts)
-            pc.kernels_begin();
-            rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
-            if (lds) hipLaunchKernelGGL((k_extend_se<true>), dim3(blocks), dim3(EX_TPB), 0, s, a, (uint8_t *)nullptr, row_bytes);
-            else hipLaunchKernelGGL((k_extend_se<false>), dim3(blocks), dim3(EX_TPB), 0, s, a, base3 + o_row, row_bytes);
-            RB_HIP(hipGetLastError());
-            pc.kernels_end();
-            RB_HIP(hipMemcpyAsync(recs + ra, a.recs, (size_t)pn * sizeof(rb_extend_rec), hipMemcpyDeviceToHost, s));
-            RB_HIP(hipMemcpyAsync(out_bases + ra * stride, a.out_b, (size_t)(pn * stride), hipMemcpyDeviceToHost, s));
-            if (out_count) RB_HIP(hipMemcpyAsync(out_count + ra * stride, a.out_c, (size_t)(pn * stride) * 4, hipMemcpyDeviceToHost, s));
-        });
-    });
+    return guarded([&] { extend_call<false>(g, seq, offsets, n, direction, min_kmer_cov, out_bases, out_count, recs); });
+}
+int rb_graph_extend_pe(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov, char *out_bases,
+                       float *out_count, rb_extend_pe_rec *recs) {
+    return guarded([&] { extend_call<true>(g, seq, offsets, n, direction, min_kmer_cov, out_bases, out_count, recs); });
 }
 }  // extern "C"

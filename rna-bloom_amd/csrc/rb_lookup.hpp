@@ -102,6 +102,30 @@ __device__ __forceinline__ bool pair_hit(const PairView &pf, uint64_t key) {
     }
     return bits_lookup(pf.bits, pf.mod, pf.num_hash, pf.kmul, key);
 }
+// ... and of two keys in two pair filters at once (a walked k-mer's read-paired and fragment-paired partner, rb_extend.hip): with two hash
+// functions in both, the up to four words are loaded before any is tested.  key_a() / key_b() give the keys, each called only where it is
+// asked (ask_a / ask_b); a key that is not asked loads nothing and misses.
+template <class KA, class KB>
+__device__ __forceinline__ void pair_hit2(const PairView &pa, KA key_a, bool ask_a, const PairView &pb, KB key_b, bool ask_b, bool &hit_a, bool &hit_b) {
+    if (pa.num_hash == 2 && pb.num_hash == 2) {
+        uint32_t wa0 = 0, wa1 = 0, wb0 = 0, wb1 = 0, sh = 0;                                  // a probe's word; its bit's place in it, a byte of sh each
+        if (ask_a) {
+            const uint64_t key = key_a(), i0 = index_of(key, pa.mod), i1 = index_of(multi_hash(key, 1u, pa.kmul), pa.mod);
+            wa0 = pa.bits[i0 >> 5]; wa1 = pa.bits[i1 >> 5];
+            sh = ((uint32_t)i0 & 31u) | (((uint32_t)i1 & 31u) << 8);
+        }
+        if (ask_b) {
+            const uint64_t key = key_b(), i0 = index_of(key, pb.mod), i1 = index_of(multi_hash(key, 1u, pb.kmul), pb.mod);
+            wb0 = pb.bits[i0 >> 5]; wb1 = pb.bits[i1 >> 5];
+            sh |= (((uint32_t)i0 & 31u) << 16) | (((uint32_t)i1 & 31u) << 24);
+        }
+        hit_a = ((wa0 >> (sh & 31u)) & (wa1 >> ((sh >> 8) & 31u)) & 1u) != 0u;
+        hit_b = ((wb0 >> ((sh >> 16) & 31u)) & (wb1 >> (sh >> 24)) & 1u) != 0u;
+        return;
+    }
+    hit_a = ask_a && pair_hit(pa, key_a());
+    hit_b = ask_b && pair_hit(pb, key_b());
+}
 
 // ---- order statistics of count codes by a whole wavefront ----
 // Common.getMedian (R/util/Common.java:41-50) / getMedianKmerCoverage (R/util/GraphUtils.java:229-247): sorted[n / 2], or the float32 mean of

@@ -629,6 +629,34 @@ class BloomFilterDeBruijnGraph:
         bases, recs, _ = self.extendStepSEFlat(seq, off, direction, minKmerCov)
         return [bases[i, :rc["out_len"]].tobytes() if rc["outcome"] != self.EXT_NONE else None for i, rc in enumerate(recs)], recs
 
+    EXT_PE_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("n_candidates", "<i4"), ("out_len", "<i4"), ("read_pairs", "<i4"),
+                             ("frag_pairs", "<i4"), ("last_partnered", "<i4"), ("winner", "<i4"), ("score", "<f4"), ("max_ext", "<i4")])
+    EXT_PE_WHYS = EXT_WHYS + ("repeat_throws",)
+
+    def extendStepPEFlat(self, seq, offsets, direction, minKmerCov, counts=False):
+        """rb_graph_extend_pe on flat host text (GraphUtils.extendRightPE / extendLeftPE, R/util/GraphUtils.java:6206-6414): as extendStepSEFlat,
+        with the fragment-paired k-mer distance d_f in the place of d.  Returns (bases[n, d_f + 2], recs, count[n, d_f + 2] or None): one
+        EXT_PE_DTYPE record per sequence, the bases the returned k-mers add in walking order at bases[i, :recs[i]["out_len"]]."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        floors = np.ascontiguousarray(np.broadcast_to(np.asarray(minKmerCov, np.float32), (n,)))
+        width = max(self.getFragPairedKmerDistance(), 0) + 2
+        bases = np.zeros((n, width), np.uint8)
+        cnt = np.zeros((n, width), np.float32) if counts else None
+        recs = np.zeros(n, self.EXT_PE_DTYPE)
+        check(lib.rb_graph_extend_pe(self.h, _ptr(seq), _ptr(off), n, direction, _ptr(floors), _ptr(bases), _ptr(cnt), _ptr(recs)))
+        return bases, recs, cnt
+
+    def extendStepPE(self, seqs, direction, minKmerCov):
+        """GraphUtils.extendRightPE (direction 0) / extendLeftPE (direction 1) of each sequence's getKmers list, with that sequence's own
+        floor: (extensions, recs) as extendStepSE — None where the reference returns null, and also where its isRepeat throws
+        (recs[i]["why"] == 5); recs is the EXT_PE_DTYPE record array."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        bases, recs, _ = self.extendStepPEFlat(seq, off, direction, minKmerCov)
+        return [bases[i, :rc["out_len"]].tobytes() if rc["outcome"] != self.EXT_NONE else None for i, rc in enumerate(recs)], recs
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and

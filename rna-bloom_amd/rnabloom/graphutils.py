@@ -193,8 +193,21 @@ def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
     k-mers * 0.1), lowered by a further * 0.1 while the step returns nothing; the counts come from graph.getKmers of the sequences' ends.
     Returns (extended sequences, [leftExtLen, leftExtLen + origLen] per sequence, in k-mers).  The reference's loop has no bound;
     max_rounds raises instead of looping forever."""
+    return _extend_loop(graph, seqs, minKmerCov, max_rounds, graph.getReadPairedKmerDistance(), graph.extendStepSE, "extendSE")
+
+
+def extendPE(graph, seqs, minKmerCov, max_rounds=100000):
+    """GraphUtils.extendPE (R/util/GraphUtils.java:6567-6678), the loop the transcript stage runs whenever fragment-paired k-mers exist
+    (R/RNABloom.java:1846-1851): extendSE's loop with d = the FRAGMENT-paired k-mer distance and extendLeftPE / extendRightPE as the step
+    (graph.extendStepPE, one call per round).  A step the reference's isRepeat would throw in counts as one that returns nothing."""
+    return _extend_loop(graph, seqs, minKmerCov, max_rounds, graph.getFragPairedKmerDistance(), graph.extendStepPE, "extendPE")
+
+
+def _extend_loop(graph, seqs, minKmerCov, max_rounds, d, step, who):
+    """the loop extendSE (:6454-6565) and extendPE (:6567-6678) share: d is the distance of the floor, of the usedKmers test and of
+    hasDuplicatedKmerPair; step(seqs, direction, floors) -> (extensions or None, records) is the batched step"""
     F = np.float32
-    d, k = graph.getReadPairedKmerDistance(), graph.k
+    k = graph.k
     floor = F(minKmerCov)
     texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
     n0 = [max(len(t) - k + 1, 0) for t in texts]
@@ -210,13 +223,13 @@ def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
         while active:
             rounds += 1
             if rounds > max_rounds:
-                raise RuntimeError("extendSE: %d sequences still grow after %d rounds" % (len(active), max_rounds))
+                raise RuntimeError("%s: %d sequences still grow after %d rounds" % (who, len(active), max_rounds))
             fresh = [i for i in active if i not in thr]
             if fresh:                                                                               # :6468 / :6519 and the first :6473
                 ko, _, _, c = graph.getKmers([texts[i][:d + k - 1] if direction else texts[i][-(d + k - 1):] for i in fresh])
                 for j, i in enumerate(fresh):
                     thr[i] = max(floor, F(F(c[int(ko[j]):int(ko[j + 1])].min()) * F(0.1)))
-            ext, _ = graph.extendStepSE([texts[i] for i in active], direction, np.array([thr[i] for i in active], F))
+            ext, _ = step([texts[i] for i in active], direction, np.array([thr[i] for i in active], F))
             nxt = []
             for i, e in zip(active, ext):
                 if not e:
