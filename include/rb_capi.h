@@ -476,6 +476,65 @@ typedef struct rb_extend_pe_rec {       /* 40 bytes */
 } rb_extend_pe_rec;
 int rb_graph_extend_pe(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
                        char *out_bases /* n * (frag_d + 2) */, float *out_count /* n * (frag_d + 2), may be NULL */, rb_extend_pe_rec *recs);
+/* The fragment screens of the transcript assembler's worker (TranscriptAssemblyWorker.run, R/RNABloom.java:1816-1927) for n host sequences:
+ * GraphUtils.isBranchFree (R/util/GraphUtils.java:7651-7672), isChimera (:7674-7760) and isBluntEndArtifact (:8535-8586), with what they
+ * call: the gated getMaxCoveragePath (:1677-1776), the gated greedyExtendRight / Left (:1978-1997, :1940-1959) and the four static
+ * hasDepthRight / hasDepthLeft (:6680-6778).  A wavefront per sequence on the device; the call is read-only on both handles, and every
+ * sequence is judged against the filters as they stood when the call began.  Sequence i is seq[offsets[i], offsets[i+1]); its k-mer list is
+ * getKmers(String)'s.  Lower-case letters are read as upper-case ones and U as T, as everywhere in this library.
+ *   gate: the `BloomFilter assembledKmers` (the worker's screeningBf) — another handle on the same device with the same k whose dbgbf is
+ *   that filter, exactly as rb_graph_greedy_extend's gate.  Required when `what` asks for the chimera or the blunt-end screen; may be NULL
+ *   for the branch-free screen alone.
+ *   what: RB_SCREEN_BRANCH_FREE | RB_SCREEN_CHIMERA | RB_SCREEN_BLUNT_END.  The three predicates are pure: computing them independently
+ *   equals the reference's short-circuit chain, and the caller combines them.  The fields of a screen that was not asked keep 0 / -1.
+ *   isBranchFree calls the MEMBER Kmer.hasDepthRight / hasDepthLeft (R/graph/Kmer.java:407-486), which never consult the graph and always
+ *   answer true (see rb_graph_naive_extend): branch-free = no k-mer has a right or a left variant (Kmer.getRightVariants / getLeftVariants,
+ *   :357-405) with graph.getCount >= 1.
+ *   isChimera: both end k-mers in the gate, else chim_why 0.  The forward scan (:7682-7706) and the backward scan (:7714-7738) over the
+ *   k-mers' gate bits, a gap of d <= 2k k-mers bridged where the gated getMaxCoveragePath(left, right, d, lookahead, gate) is not null: up
+ *   to d steps to the right from `left` — the gated successors (gate.lookup, then graph.getCount > 0), one taken as is, several through the
+ *   gated greedyExtendRightOnce (:535-562 over getMaxMedianCoverageRight :312-373) — ending with a path when the step's k-mer equals
+ *   `right`, and with the right-hand search when it is one the walk has added before; then up to d steps to the left from `right` ending with
+ *   a path at `left` or at a k-mer of the left-hand walk, with null at one the right-hand walk has added before (:1745-1771).  No
+ *   low-complexity test.  Kmer.equals is equality of the bases: the device compares forward hashes and confirms on the bases.
+ *   chim_why 1: the forward scan reached the last k-mer (:7708); 2: j - i > 2k at :7742; else the two gated greedy walks of at most 1000
+ *   k-mers, to the right from k-mer i and to the left from k-mer j: 3 if they share a k-mer, 4 if not (the chimera).
+ *   isBluntEndArtifact: max_depth (the worker's maxEdgeClipLength) <= 0 answers false (:8536).  Minima and medians are the reference's
+ *   float32 values (getMinimumKmerCoverage(kmers, start, end) :133-145, getMedianKmerCoverage(kmers, start, end) :208-217); d is the graph's
+ *   read-paired k-mer distance.  blunt_why 0: neither arm entered; 1 / 2: the left / right arm returned at its range test (:8555, :8574);
+ *   3 / 4: the arm's three-clause test (:8559-8561, :8578-8580) failed; 5 / 6: it held (the artifact).  The clauses are evaluated in the
+ *   reference's order and not past the first that fails.  The static hasDepth* are depth-first searches over getSuccessors /
+ *   getPredecessors (count >= 1; the gated form: gate.lookup, then count > 0) whose test `frontier.size() >= depth` follows every push and
+ *   every removal of an empty level.
+ *   max_visits: the budget of ONE hasDepth* search, counted in getSuccessors / getPredecessors calls (the first one, of the source, counts).
+ *   The reference's search is unbounded and exponential on a tangled graph; the device stops a search that would make call number
+ *   max_visits + 1 and reports the sequence as not judged (RB_SCREEN_OVER_BUDGET: the blunt-end bit is clear, blunt_why is 0, boundary is
+ *   the arm's; the other two screens are reported as usual).  0 selects RB_SCREEN_DEFAULT_VISITS.
+ *   out[8 i ..]: rb_screen_rec.  A sequence without a k-mer is flagged RB_SCREEN_NO_KMER, one with a k-mer and a letter outside ACGTU
+ *   RB_SCREEN_BAD_LETTER; neither is judged (every other field 0 / -1) — they stay with the caller.
+ * The call works in pieces through the shared driver (RB_QUERY_PIECE k-mers); results do not depend on the cuts.  Device scratch of a piece:
+ * 21 bytes per k-mer, 40 per sequence, and 19 P + 2 k bytes of walk rows for each of at most 2048 wavefronts (fewer, down to 16, where
+ * that would pass 512 MB), P = max(1000, min(max(max_depth, the longest sequence's k-mers), max_visits)).  With rb_graph_profile_enable on
+ * the kernels' device time is added to the profile entry "screen_fragments".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf or counting filter; `what` 0 or with other
+ * bits; no gate where bit 1 or 2 is asked; a gate that is a shard handle, on another device, with another k or without its dbgbf;
+ * lookahead outside [0, 16]; max_depth above 2^20; max_visits < 0; n < 0; with n > 0: a null offsets / out, a null seq where there is text, decreasing offsets.
+ * n == 0 succeeds and touches nothing. */
+enum { RB_SCREEN_BRANCH_FREE = 1, RB_SCREEN_CHIMERA = 2, RB_SCREEN_BLUNT_END = 4,                                                /* `what`, and rb_screen_rec.flags */
+       RB_SCREEN_BAD_LETTER = 8, RB_SCREEN_NO_KMER = 16, RB_SCREEN_OVER_BUDGET = 32 };                                            /* rb_screen_rec.flags: not judged */
+enum { RB_CHIM_WHY_ENDS = 0, RB_CHIM_WHY_ASSEMBLED = 1, RB_CHIM_WHY_WIDE_GAP = 2, RB_CHIM_WHY_PATHS_MEET = 3, RB_CHIM_WHY_DISJOINT = 4 };   /* rb_screen_rec.chim_why */
+enum { RB_BLUNT_WHY_NO_ARM = 0, RB_BLUNT_WHY_LEFT_RANGE = 1, RB_BLUNT_WHY_RIGHT_RANGE = 2, RB_BLUNT_WHY_LEFT_FAILED = 3, RB_BLUNT_WHY_RIGHT_FAILED = 4,
+       RB_BLUNT_WHY_LEFT_ARTIFACT = 5, RB_BLUNT_WHY_RIGHT_ARTIFACT = 6 };                                                         /* rb_screen_rec.blunt_why */
+#define RB_SCREEN_DEFAULT_VISITS 65536
+typedef struct rb_screen_rec {          /* 32 bytes */
+    int32_t flags, chim_why;
+    int32_t break_i, break_j;           /* isChimera's i and j as they stand at :7742, or -1 (chim_why 0 or 1, or the screen not asked) */
+    int32_t right_len, left_len;        /* k-mers of the two gated greedy walks (:7746-7748), or 0 */
+    int32_t blunt_why;
+    int32_t boundary;                   /* the entered arm's boundary index (left arm: i, right arm: j + 1), or -1 */
+} rb_screen_rec;
+int rb_graph_screen_fragments(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int what, int lookahead,
+                              int max_depth, int64_t max_visits, rb_screen_rec *out);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

@@ -69,6 +69,11 @@ public class BloomFilter implements BloomFilterInterface {
         this.hashFunction = hashFunction;
     }
 
+    /** the rb_graph handle behind this filter and which of its filters it is — what a native call that takes a filter as its gate needs
+     *  (NativeGraph.greedyExtend, NativeGraph.screenFragments: the gate is the handle's dbgbf) */
+    public long getNativeHandle() { return handle; }
+    public int getNativeWhich() { return which; }
+
     // ---- the .desc text and the raw bytes are the reference's own files (:64-124) ----
     /** {size, numhash} of a filter description file */
     public static long[] readDesc(File desc) throws IOException {

@@ -563,6 +563,29 @@ public class BloomFilterDeBruijnGraph {
         return res;
     }
 
+    public static final int SCREEN_BRANCH_FREE = 1, SCREEN_CHIMERA = 2, SCREEN_BLUNT_END = 4, SCREEN_NOT_JUDGED = 8 | 16 | 32;
+
+    /**
+     * GraphUtils.isBranchFree, isChimera and isBluntEndArtifact (src/rnabloom/util/GraphUtils.java:7651-7672, :7674-7760, :8535-8586) for a batch of
+     * fragments in ONE native call, whichever of them `what` asks for (SCREEN_BRANCH_FREE | SCREEN_CHIMERA | SCREEN_BLUNT_END): the scans, the
+     * gated walks and the depth searches run on the device.  assembledKmers is the worker's screeningBf — a stand-alone BloomFilter; it may be
+     * null for the branch-free screen alone.  maxDepth is maxEdgeClipLength.  records (8 * seqs.length ints) receives the records of
+     * NativeGraph.screenFragments: records[8 i] holds fragment i's predicates in bits 0..2, and a bit of SCREEN_NOT_JUDGED where the fragment
+     * stays with the reference's own code (a letter outside ACGTU, no k-mer, a depth search past the library's budget).
+     */
+    public void screenFragments(String[] seqs, BloomFilter assembledKmers, int what, int lookahead, int maxDepth, int[] records) {
+        final int n = seqs.length;
+        if (records == null || records.length < 8L * n) throw new IllegalArgumentException("screenFragments: records must hold " + 8L * n + " ints");
+        if (assembledKmers != null && (assembledKmers.getNativeWhich() != NativeGraph.DBGBF || assembledKmers.getNativeHandle() == handle))
+            throw new IllegalArgumentException("screenFragments: the gate must be a stand-alone BloomFilter");
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("screenFragments: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        NativeGraph.screenFragments(handle, assembledKmers != null ? assembledKmers.getNativeHandle() : 0L, text, off, n, what, lookahead, maxDepth, 0L, records);
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

@@ -143,6 +143,14 @@ public final class NativeGraph {
      *  at outBases + i * (fragD + 2), in walking order; outCount (may be null) their counts.  Read-only. */
     public static native void extendPE(long h, ByteBuffer seq, long[] offsets, int n, int direction, float[] minKmerCov, byte[] outBases,
                                        float[] outCount, int[] recs);
+    /** The fragment screens of n sequences (rb_graph_screen_fragments; GraphUtils.isBranchFree, isChimera and isBluntEndArtifact,
+     *  R/util/GraphUtils.java:7651-7672, :7674-7760, :8535-8586): what = 1 branch-free | 2 chimera | 4 blunt-end artifact; gateHandleOr0 is the
+     *  handle whose dbgbf is the BloomFilter assembledKmers (0 only for what == 1); maxDepth is maxEdgeClipLength; maxVisits the budget of one
+     *  static hasDepth* search (0: the library's default).  recs holds 8 ints per sequence — flags (the predicates in bits 0..2; not judged:
+     *  8 a letter outside ACGTU, 16 no k-mer, 32 a depth search ran out of its budget), chim_why, isChimera's i and j, the lengths of its two
+     *  greedy walks, blunt_why, the arm's boundary index.  Read-only on both handles. */
+    public static native void screenFragments(long h, long gateHandleOr0, ByteBuffer seq, long[] offsets, int n, int what, int lookahead,
+                                              int maxDepth, long maxVisits, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

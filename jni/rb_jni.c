@@ -454,6 +454,21 @@ void FN(extendPE)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets,
     lr(e, offsets, po, JNI_ABORT); fr(e, minKmerCov, pf, JNI_ABORT); br(e, outBases, ob, 0); fr(e, outCount, oc, 0); ir(e, recs, rc10, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_screen_fragments: a record (rb_screen_rec, 32 bytes) is 8 ints to Java: flags, chim_why, break_i, break_j, right_len, left_len, blunt_why, boundary */
+void FN(screenFragments)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlongArray offsets, jint n, jint what, jint lookahead, jint maxDepth,
+                         jlong maxVisits, jintArray recs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!offsets || !recs || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, recs) / 8 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "screenFragments: an array is too short for n sequences");
+        return;
+    }
+    jlong *po = la(e, offsets);
+    jint *rc8 = ia(e, recs);
+    int rc = rb_graph_screen_fragments(G(h), gate ? G(gate) : NULL, (const char *)direct(e, seq), (const int64_t *)po, n, what, lookahead, maxDepth, maxVisits,
+                                       (rb_screen_rec *)rc8);
+    lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc8, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

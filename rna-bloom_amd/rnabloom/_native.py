@@ -19,6 +19,12 @@ SLOT_REC_KEYS, SLOT_REC_OCC, SLOT_PAIR_IDX, SLOT_DREQ_IDX, SLOT_DREQ_PROBE, SLOT
     SLOT_CONF_EDGES, SLOT_CONF_RUNS, SLOT_CONF_OPS, SLOT_CW_IDX, SLOT_CW_VAL, SLOT_Q_BIDX, SLOT_Q_CIDX, SLOT_CACHE_UPD, SLOT_ORD_IDX = range(17)
 MODE_ADD, MODE_COUNT_IF_PRESENT = 0, 2
 STROBE_CANONICAL, STROBE_SLIDE = 1, 2
+# rb_graph_screen_fragments: `what` and rb_screen_rec.flags, then the flags of a sequence that was not judged; chim_why; blunt_why
+SCREEN_BRANCH_FREE, SCREEN_CHIMERA, SCREEN_BLUNT_END, SCREEN_BAD_LETTER, SCREEN_NO_KMER, SCREEN_OVER_BUDGET = 1, 2, 4, 8, 16, 32
+CHIM_WHY_ENDS, CHIM_WHY_ASSEMBLED, CHIM_WHY_WIDE_GAP, CHIM_WHY_PATHS_MEET, CHIM_WHY_DISJOINT = range(5)
+BLUNT_WHY_NO_ARM, BLUNT_WHY_LEFT_RANGE, BLUNT_WHY_RIGHT_RANGE, BLUNT_WHY_LEFT_FAILED, BLUNT_WHY_RIGHT_FAILED, BLUNT_WHY_LEFT_ARTIFACT, \
+    BLUNT_WHY_RIGHT_ARTIFACT = range(7)
+SCREEN_DEFAULT_VISITS = 65536
 
 
 class GraphParams(C.Structure):
@@ -110,6 +116,7 @@ SYMBOLS = [
     ("rb_graph_overlap_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_extend_se", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -657,6 +657,34 @@ class BloomFilterDeBruijnGraph:
         bases, recs, _ = self.extendStepPEFlat(seq, off, direction, minKmerCov)
         return [bases[i, :rc["out_len"]].tobytes() if rc["outcome"] != self.EXT_NONE else None for i, rc in enumerate(recs)], recs
 
+    SCREEN_DTYPE = np.dtype([("flags", "<i4"), ("chim_why", "<i4"), ("break_i", "<i4"), ("break_j", "<i4"), ("right_len", "<i4"), ("left_len", "<i4"),
+                             ("blunt_why", "<i4"), ("boundary", "<i4")])
+    SCREEN_BRANCH_FREE, SCREEN_CHIMERA, SCREEN_BLUNT_END = N.SCREEN_BRANCH_FREE, N.SCREEN_CHIMERA, N.SCREEN_BLUNT_END
+    SCREEN_NOT_JUDGED = N.SCREEN_BAD_LETTER | N.SCREEN_NO_KMER | N.SCREEN_OVER_BUDGET
+    CHIM_WHYS = ("ends", "assembled", "wide_gap", "paths_meet", "disjoint")
+    BLUNT_WHYS = ("no_arm", "left_range", "right_range", "left_failed", "right_failed", "left_artifact", "right_artifact")
+
+    def screenFragmentsFlat(self, seq, offsets, bf, what, lookahead, maxDepth, maxVisits=0):
+        """rb_graph_screen_fragments on flat host text: GraphUtils.isBranchFree (R/util/GraphUtils.java:7651-7672), isChimera (:7674-7760) and
+        isBluntEndArtifact (:8535-8586) of sequence i = seq[offsets[i]:offsets[i + 1]] (uint8), whichever `what` asks for (SCREEN_BRANCH_FREE |
+        SCREEN_CHIMERA | SCREEN_BLUNT_END).  bf — a rnabloom.bloom.BloomFilter, as in greedyExtend — is the worker's assembledKmers /
+        screeningBf; it may be None for the branch-free screen alone.  maxDepth is maxEdgeClipLength; maxVisits the budget of one static
+        hasDepth* search (0: the library's default).  Returns one SCREEN_DTYPE record per sequence: the predicates in flags' bits 0..2;
+        bits 3..5 (SCREEN_NOT_JUDGED) mark a sequence that stays with the caller."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        recs = np.zeros(n, self.SCREEN_DTYPE)
+        check(lib.rb_graph_screen_fragments(self.h, bf._g.h if bf is not None else None, _ptr(seq), _ptr(off), n, what, lookahead, maxDepth,
+                                            maxVisits, _ptr(recs)))
+        return recs
+
+    def screenFragments(self, seqs, bf, what, lookahead, maxDepth, maxVisits=0):
+        """screenFragmentsFlat over strings (or bytes): the SCREEN_DTYPE record array, one record per sequence"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        return self.screenFragmentsFlat(seq, off, bf, what, lookahead, maxDepth, maxVisits)
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and
