@@ -4,7 +4,8 @@ flags, every gap record.  Reads of random transcripts at k-mer coverage of about
 (isolated, two within k), insertions and deletions of 1-3 bases, erroneous tips shorter and longer than lookahead, foreign letters past a
 transcript's end, N's, and SNV bubbles whose candidate windows were put into the graph.  k 25 / 21, stranded / canonical, min_kmer_cov 1 / 2,
 max_indel_size 1 / 3.  Over the cases every kind x outcome of a gap occurs (checked on the oracle alone).  Then: composition with
-rb_graph_correct_mismatches, many pieces, two threads on one handle, the refusals, the profile entries, 50 000 sequences in one call."""
+rb_graph_correct_mismatches, many pieces, two threads on one handle, the refusals, the profile entries, 50 000 sequences in one call.
+World takes the read length as an argument (read_len, 150 here): tests/correction_worlds.py builds the worlds of k = 16 ... 256 from it."""
 import ctypes as C
 import functools
 import threading
@@ -63,35 +64,41 @@ class OracleSide(MismatchOracle):
 
 
 class World:
-    """an oracle graph from reads of random transcripts, the query sets, and — built on request — the device graph from the same reads"""
+    """an oracle graph from reads of random transcripts, the query sets, and — built on request — the device graph from the same reads.
+    read_len (150 here), tx_len and the sizes of the query sets (n_sets over N_SETS) are arguments for tests/correction_worlds.py, whose reads grow
+    with k; extra_reads go into the graph as they are"""
 
-    def __init__(self, k, stranded, seed, n_tx=20, n_reads=2600, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2)):
+    N_SETS = dict(isolated=30, within_k=30, indels=45, tips=60, letters=12, several=10, clean=20, bubbles=12)
+
+    def __init__(self, k, stranded, seed, n_tx=20, n_reads=2600, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2), read_len=150, tx_len=(600, 1000),
+                 n_sets=None, extra_reads=()):
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.sizes, self.rng, self.hashes = k, stranded, sizes, rng, hashes
-        self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(600, 1000)))].tobytes() for _ in range(n_tx)]
+        self.k, self.stranded, self.sizes, self.rng, self.hashes, self.read_len = k, stranded, sizes, rng, hashes, read_len
+        ns = dict(self.N_SETS, **(n_sets or {}))
+        L = read_len
+        self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(*tx_len)))].tobytes() for _ in range(n_tx)]
         self.reads = []
         for _ in range(n_reads):
             t = self.tx[int(rng.integers(0, len(self.tx)))]
-            a = int(rng.integers(0, len(t) - 150))
-            self.reads.append(t[a:a + 150])
+            a = int(rng.integers(0, len(t) - L))
+            self.reads.append(t[a:a + L])
         for t in self.tx:                                      # the transcripts' ends are covered as well as their middles
-            self.reads += [t[:150]] * 8 + [t[-150:]] * 8
+            self.reads += [t[:L]] * 8 + [t[-L:]] * 8
         q = self.sets = {}
         pick = iter(self.reads[:n_reads])
-        L = 150
-        q["isolated"] = [plant(next(pick), [int(rng.integers(k + 5, L - k - 5))], rng) for _ in range(30)]
+        q["isolated"] = [plant(next(pick), [int(rng.integers(k + 5, L - k - 5))], rng) for _ in range(ns["isolated"])]
         q["within_k"] = []
-        for _ in range(30):
+        for _ in range(ns["within_k"]):
             m = int(rng.integers(k + 5, L - 2 * k - 5))
             q["within_k"].append(plant(next(pick), [m, m + int(rng.integers(1, k))], rng))
         q["insertions"], q["deletions"] = [], []
-        for i in range(45):
+        for i in range(ns["indels"]):
             s, m, j = next(pick), int(rng.integers(k + 5, L - k - 8)), i % 3 + 1
             q["insertions"].append(s[:m] + ACGT[rng.integers(0, 4, j)].tobytes() + s[m:])
             s, m = next(pick), int(rng.integers(k + 5, L - k - 8))
             q["deletions"].append(s[:m] + s[m + j:])
         q["tips"] = []
-        for i in range(60):
+        for i in range(ns["tips"]):
             s, d = next(pick), (1, 2, 3, 4, 6, 9, 14, 20)[i % 8]           # shorter and longer than lookahead
             pos = [d - 1] if i % 2 == 0 else [L - d]
             if i % 10 >= 8:                                    # a tip that is wrong throughout: the identity check fails
@@ -100,24 +107,25 @@ class World:
         q["off_the_end"] = []
         for i, t in enumerate(self.tx):                        # foreign letters before a transcript's first / past its last base
             junk = ACGT[rng.integers(0, 4, int(rng.integers(1, 12)))].tobytes()
-            q["off_the_end"].append(junk + t[:140] if i % 2 == 0 else t[-140:] + junk)
+            q["off_the_end"].append(junk + t[:L - 10] if i % 2 == 0 else t[-(L - 10):] + junk)
         q["letters"] = []
-        for _ in range(12):
+        for _ in range(ns["letters"]):
             b = bytearray(next(pick))
             for p in rng.integers(0, L, 2):
                 b[p] = ord("N")
             q["letters"].append(bytes(b))
-        q["several"] = [plant(next(pick), [2, L // 2, L - 3], rng) for _ in range(10)]
-        q["clean"] = [next(pick) for _ in range(20)] + [b"", b"ACGT", self.tx[0][:k], self.tx[0][:k + 1], ACGT[rng.integers(0, 4, 80)].tobytes()]
+        q["several"] = [plant(next(pick), [2, L // 2, L - 3], rng) for _ in range(ns["several"])]
+        q["clean"] = [next(pick) for _ in range(ns["clean"])] + [b"", b"ACGT", self.tx[0][:k], self.tx[0][:k + 1], ACGT[rng.integers(0, 4, 80)].tobytes()]
         # SNV bubbles that can be refilled: the k + 2 windows of left + n + right of a planted substitution are put into the graph twice
         q["bubbles"] = []
-        for _ in range(12):
+        for _ in range(ns["bubbles"]):
             s, m = next(pick), int(rng.integers(k + 5, L - k - 5))
             bad = plant(s, [m], rng)
             g = m - k + 1
             cand = bad[g:g + k] + ACGT[rng.integers(0, 4, 1)].tobytes() + bad[g + k - 1:g + 2 * k - 1]
             self.reads += [cand] * 2
             q["bubbles"].append(bad)
+        self.reads += list(extra_reads)
         self.og = rbo.Graph(*sizes, *hashes, k, stranded, True, 5)
         self.packed = rbo.pack_reads(self.reads, [b"I" * len(s) for s in self.reads])
         self.og.add_reads(*self.packed, 3, 0)

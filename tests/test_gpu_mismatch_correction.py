@@ -3,7 +3,8 @@ tests/test_mismatch_rules.py) run on the CPU oracle's getKmers / contains, a dev
 Compared exactly: the corrected bytes, n_fixed, koffsets, the final count rows — and those rows against rb_graph_kmers of the output.
 Stranded and canonical graphs, k 25 / 35 / 47, min_kmer_cov 1 / 2 / 0, one threshold for all and coverageStats' se_threshold per
 sequence, many pieces, every refusal, two threads on one handle, and 50 000 sequences in one call.  Before the device is asked each case
-checks on the oracle alone that the fixture is not vacuous: most planted substitutions are replaced, some by the reverse scan only."""
+checks on the oracle alone that the fixture is not vacuous: most planted substitutions are replaced, some by the reverse scan only.
+World takes the read length as an argument (read_len, 250 here): tests/correction_worlds.py builds the worlds of k = 16 ... 256 from it."""
 import ctypes as C
 import threading
 
@@ -59,31 +60,34 @@ class OracleSide:
 class World:
     """an oracle graph from reads of random transcripts (250 bases each, k-mer coverage about 20), plus six copies each of a few erroneous k-mers: the
     k-mer that ENDS with a planted substitution, which makes the forward scan's candidate one window late (it aims at the wrong base) and
-    leaves the substitution to the reverse scan.  The device graph is built from the same reads on request."""
+    leaves the substitution to the reverse scan.  The device graph is built from the same reads on request.  read_len, tx_len and the numbers
+    of planted sequences are arguments for tests/correction_worlds.py, whose reads grow with k; extra_reads go into the graph as they are."""
     T = 3.0
 
-    def __init__(self, k, stranded, seed, n_tx=24, n_reads=3200, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2)):
+    def __init__(self, k, stranded, seed, n_tx=24, n_reads=3200, sizes=(1_600_033, 1_600_033, 1009), hashes=(2, 2, 2), read_len=250, tx_len=(900, 1500),
+                 n_planted=240, n_rev=40, extra_reads=()):
         rng = np.random.default_rng(seed)
-        self.k, self.stranded, self.sizes, self.rng, self.hashes = k, stranded, sizes, rng, hashes
-        self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(900, 1500)))].tobytes() for _ in range(n_tx)]
+        self.k, self.stranded, self.sizes, self.rng, self.hashes, self.read_len = k, stranded, sizes, rng, hashes, read_len
+        self.tx = [ACGT[rng.integers(0, 4, int(rng.integers(*tx_len)))].tobytes() for _ in range(n_tx)]
         self.reads = []
         for _ in range(n_reads):
             t = self.tx[int(rng.integers(0, len(self.tx)))]
-            a = int(rng.integers(0, len(t) - 250))
-            self.reads.append(t[a:a + 250])
+            a = int(rng.integers(0, len(t) - read_len))
+            self.reads.append(t[a:a + read_len])
         # planted-substitution queries: one in the middle, one near each end, two far apart, two within k, three
         self.planted, self.rev_only = [], []
-        for i, s in enumerate(self.reads[:240]):
+        for i, s in enumerate(self.reads[:n_planted]):
             kind = i % 6
             L = len(s)
             pos = ([int(rng.integers(k, L - k))], [int(rng.integers(0, k))], [int(rng.integers(L - k, L))],
                    [k + 2, L - k - 3], [L // 2, L // 2 + int(rng.integers(1, k))], [k + 1, L // 2, L - k - 2])[kind]
             self.planted.append(plant(s, pos, rng))
-        for s in self.reads[240:280]:                       # ... and the ones kept for the reverse scan
+        for s in self.reads[n_planted:n_planted + n_rev]:    # ... and the ones kept for the reverse scan
             m = int(rng.integers(k + 2, len(s) - k - 2))
             bad = plant(s, [m], rng)
             self.rev_only.append(bad)
             self.reads += [bad[m - k + 1:m + 1]] * 6
+        self.reads += list(extra_reads)
         self.og = rbo.Graph(*sizes, *hashes, k, stranded, True, 5)
         self.packed = rbo.pack_reads(self.reads, [b"I" * len(s) for s in self.reads])
         self.og.add_reads(*self.packed, 3, 0)
@@ -100,11 +104,12 @@ class World:
     def query_sets(self):
         k, rng = self.k, self.rng
         reads = self.reads[300:420]
-        chim = []
+        chim, half = [], self.read_len * 4 // 5
+
         for i in range(30):
             a, b = self.tx[i % len(self.tx)], self.tx[(i + 5) % len(self.tx)]
-            x, y = int(rng.integers(0, len(a) - 200)), int(rng.integers(0, len(b) - 200))
-            chim.append(a[x:x + 200] + b[y:y + 200])
+            x, y = int(rng.integers(0, len(a) - half)), int(rng.integers(0, len(b) - half))
+            chim.append(a[x:x + half] + b[y:y + half])
         letters = []
         for s in self.reads[420:520]:
             b = bytearray(s)
