@@ -476,6 +476,62 @@ typedef struct rb_extend_pe_rec {       /* 40 bytes */
 } rb_extend_pe_rec;
 int rb_graph_extend_pe(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
                        char *out_bases /* n * (frag_d + 2) */, float *out_count /* n * (frag_d + 2), may be NULL */, rb_extend_pe_rec *recs);
+/* Joining of read pairs through the graph — GraphUtils.join (R/util/GraphUtils.java:892-1147), the second half of overlapAndConnect (:5065-5090) that
+ * the FragmentAssembler runs on every pair GraphUtils.overlap returned null for (R/RNABloom.java:2148).  A wavefront per pair on the device; the call
+ * is read-only.  Pair i is lseq[loffsets[i], loffsets[i+1]) and rseq[roffsets[i], roffsets[i+1]); each read's k-mer list is getKmers(String)'s
+ * (lower case and U read as everywhere in this library), nkL and nkR k-mers.  d = the read-paired k-mer distance, g = max_cov_gradient, m =
+ * min_kmer_cov.  The reference's lookahead, maxIndelLen and minPercentIdentity are never read by its body and are not part of this call;
+ * max_tip_len is passed on to the branch step, which does not read it either (see rb_graph_naive_extend).
+ *   Neighbours of a k-mer: its successors (right walk: predecessors) with graph.getCount >= m in the order A C G T (the four-argument
+ *   getSuccessors, R/graph/Kmer.java:232-255).  All thresholds are float32, one product each.  Equality of k-mers is Kmer.equals, the k bases:
+ *   hashes are compared first and every hit is confirmed on the bases.
+ *   Left walk (:912-1030): leftPath = the left list, threshold t = max(m, min(left counts) * g).  While |leftPath| < bound + nkL: no neighbour of
+ *   the last k-mer ends the walk.  The only neighbour — or the only one left after dropping those with count < t — is `best`, and t = max(m,
+ *   min(t, best.count * g)).  best in the right list: at index 0 the result is leftPath + right list (JOINED, REACHED_RIGHT); at its FIRST index
+ *   j > 0 the result is leftPath + right[j ..] (JOINED, INSIDE_RIGHT, index = j) when min count of right[0, j) < min count of leftPath[max(0,
+ *   size - j), size), and else the walk goes on to the next test.  best a homopolymer or in leftPath: the walk ends (LOOP).  Else best is added.
+ *   No best (a fork): the branch step extendRightSE(leftPath, floor m) — what rb_graph_extend_se computes from the last min(size, d) k-mers; null
+ *   or empty ends the walk, else each returned k-mer in turn goes through the two right-list tests above, ends the walk if it is a homopolymer
+ *   (EXT_HOMOPOLYMER), and is else added WITHOUT the leftPath test, with c = g * count; if (c < t) t = max(c, m).  The bound is tested at the
+ *   top of the loop only: a step's k-mers may overshoot it.
+ *   Right walk (:1032-1144), when the left walk did not return: rightPath = the right list reversed, threshold from the right counts, predecessors
+ *   and extendLeftSE, bound + nkR.  best in leftPath (as the left walk left it, duplicates included): equal to the left list's last k-mer, the
+ *   result is left list + rightPath reversed (JOINED, REACHED_LEFT); else leftPath is cut behind the LAST k-mer equal to best and rightPath reversed
+ *   is added (JOINED, PATHS_MEET, index = that k-mer's index).  Else best a homopolymer or in rightPath: null (NONE, RIGHT_LOOP).  A step's k-mer in
+ *   leftPath: PATHS_MEET the same way (no REACHED_LEFT test here); a homopolymer: NONE, RIGHT_LOOP; else added without the rightPath test.
+ *   Both walks over: NONE, EXHAUSTED.
+ *   A pair the reference cannot be asked about is NOT_JUDGED: a read with fewer than k letters (SHORT: the reference throws in get(0)), a letter
+ *   outside ACGTU in either read (INVALID_LETTER).
+ *   Output: out_offsets (host, n + 1) is a capacity layout from the lengths, bound, d and k alone: pair i has room for nkL + nkR + 2 * (bound + d +
+ *   2) k-mers' text, that many + k - 1 bytes (a walk adds at most bound - 1 k-mers one at a time and then one step's, at most d + 1).  out_seq ==
+ *   NULL: a size query — only out_offsets is filled, nothing is launched.  out_seq[out_offsets[i] ..] holds the string the returned k-mer list
+ *   spells, upper-case A C G T, and recs[i].out_len its length; zeros behind it; NONE / NOT_JUDGED have out_len 0.  recs[i]: l_end / r_end how each
+ *   walk ended, l_added / r_added the k-mers it added (before a cut), l_forks / r_forks the branch steps it took, index as above (-1 where there
+ *   is none), l_threshold / r_threshold the walks' final thresholds (0 for a walk that did not run).
+ * Every pair is judged against the graph as it stands when the call starts.  The call works in pieces cut by the k-mers of both reads
+ * (RB_QUERY_PIECE, 16 M by default: 20 bytes of device scratch per k-mer, 72 per pair, and the piece's output text); results do not depend on the
+ * cuts.  A pair's paths live in a row of device scratch that a wavefront owns while it works on the pair: 21 bytes for each of the pair's
+ * capacity k-mers; a piece has at most 4096 such rows and fewer when they are large — as many as fit 512 MB, but 64 at least.  RB_JOIN_MAX_BOUND
+ * is the largest bound accepted: with it 64 rows stay below 0.4 GB plus the reads' share.  It leases a query context (re-entrant on one handle).
+ * With rb_graph_profile_enable on the kernels' device time is added to the profile entry "join".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf, counting filter or read-pair filter (or a graph
+ * made without one); d < 2; bound < 0 or above RB_JOIN_MAX_BOUND; a max_cov_gradient or min_kmer_cov that is not finite or is negative; n < 0;
+ * with n > 0: a null loffsets / roffsets / out_offsets (or recs, unless out_seq is NULL too), text missing where offsets say there is some,
+ * decreasing offsets.  n == 0 succeeds and touches nothing. */
+enum { RB_JOIN_NONE = 0, RB_JOIN_JOINED = 1, RB_JOIN_NOT_JUDGED = 2 };                                                         /* rb_join_rec.outcome */
+enum { RB_JOIN_WHY_REACHED_RIGHT = 0, RB_JOIN_WHY_INSIDE_RIGHT = 1, RB_JOIN_WHY_REACHED_LEFT = 2, RB_JOIN_WHY_PATHS_MEET = 3, RB_JOIN_WHY_RIGHT_LOOP = 4,
+       RB_JOIN_WHY_EXHAUSTED = 5, RB_JOIN_WHY_SHORT = 6, RB_JOIN_WHY_INVALID_LETTER = 7 };                                     /* rb_join_rec.why */
+enum { RB_JOIN_END_NOT_RUN = 0, RB_JOIN_END_NO_NEIGHBOR = 1, RB_JOIN_END_LOOP = 2, RB_JOIN_END_STEP_NONE = 3, RB_JOIN_END_EXT_HOMOPOLYMER = 4,
+       RB_JOIN_END_BOUND = 5, RB_JOIN_END_RETURNED = 6 };                                                                      /* rb_join_rec.l_end, r_end */
+#define RB_JOIN_MAX_BOUND 65536
+typedef struct rb_join_rec {            /* 48 bytes */
+    int32_t outcome, why, l_end, r_end;
+    int32_t l_added, r_added, l_forks, r_forks;
+    int32_t index, out_len /* letters */;
+    float l_threshold, r_threshold;
+} rb_join_rec;
+int rb_graph_join_pairs(rb_graph *g, const char *lseq, const int64_t *loffsets, const char *rseq, const int64_t *roffsets, int64_t n, int bound,
+                        float max_cov_gradient, int max_tip_len, float min_kmer_cov, int64_t *out_offsets, char *out_seq, rb_join_rec *recs);
 /* The fragment screens of the transcript assembler's worker (TranscriptAssemblyWorker.run, R/RNABloom.java:1816-1927) for n host sequences:
  * GraphUtils.isBranchFree (R/util/GraphUtils.java:7651-7672), isChimera (:7674-7760) and isBluntEndArtifact (:8535-8586), with what they
  * call: the gated getMaxCoveragePath (:1677-1776), the gated greedyExtendRight / Left (:1978-1997, :1940-1959) and the four static

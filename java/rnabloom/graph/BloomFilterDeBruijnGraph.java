@@ -509,6 +509,37 @@ public class BloomFilterDeBruijnGraph {
     }
 
     /**
+     * GraphUtils.join (src/rnabloom/util/GraphUtils.java:892-1147) for a batch of read pairs in ONE native call — the pairs overlapPairs returned
+     * null for: both walks, their membership tests and the branch steps at forks run on the device, a wavefront per pair, and nothing is
+     * written to the graph.  lookahead, maxIndelLen and minPercentIdentity of the reference's signature are never read by its body and are not
+     * parameters here.  Returns, per pair, the string the reference's returned k-mers spell, or null where the reference returns null and
+     * where the pair cannot be judged (a read shorter than k, a letter outside ACGTU: records[12 i] == 2).  records (optional, 12 *
+     * lefts.length ints) receives the records of NativeGraph.joinPairs.
+     */
+    public String[] joinPairs(String[] lefts, String[] rights, int bound, float maxCovGradient, int maxTipLen, float minKmerCov, int[] records) {
+        final int n = lefts.length;
+        if (rights.length != n) throw new IllegalArgumentException("joinPairs: " + n + " left reads and " + rights.length + " right reads");
+        if (records != null && records.length < 12L * n) throw new IllegalArgumentException("joinPairs: records holds " + records.length + " ints, " + 12L * n + " are needed");
+        if (12L * n > Integer.MAX_VALUE) throw new IllegalArgumentException("joinPairs: " + n + " pairs' records do not fit one array: smaller batches");
+        final long[] lo = new long[n + 1], ro = new long[n + 1], outOff = new long[n + 1];
+        for (int i = 0; i < n; ++i) { lo[i + 1] = lo[i] + lefts[i].length(); ro[i + 1] = ro[i] + rights[i].length(); }
+        if (lo[n] + ro[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("joinPairs: more than 2 GB of text in one batch");
+        final ByteBuffer lt = ByteBuffer.allocateDirect(Math.max((int) lo[n], 1)), rt = ByteBuffer.allocateDirect(Math.max((int) ro[n], 1));
+        for (String s : lefts) for (int i = 0; i < s.length(); ++i) lt.put((byte) s.charAt(i));
+        for (String s : rights) for (int i = 0; i < s.length(); ++i) rt.put((byte) s.charAt(i));
+        final int[] rec = records != null ? records : new int[12 * n];
+        final int cap = NativeGraph.joinPairs(handle, lt, lo, rt, ro, n, bound, maxCovGradient, maxTipLen, minKmerCov, outOff, null, null);
+        final ByteBuffer out = ByteBuffer.allocateDirect(Math.max(cap, 1));
+        NativeGraph.joinPairs(handle, lt, lo, rt, ro, n, bound, maxCovGradient, maxTipLen, minKmerCov, outOff, out, rec);
+        final byte[] b = new byte[cap];
+        out.get(b, 0, cap);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = rec[12 * i] == 1 ? new String(b, (int) outOff[i], rec[12 * i + 9], java.nio.charset.StandardCharsets.ISO_8859_1) : null;
+        return res;
+    }
+
+    /**
      * GraphUtils.extendRightSE (direction 0) / extendLeftSE (direction 1) (src/rnabloom/util/GraphUtils.java:6018-6204) for a batch of sequences in ONE
      * native call: the candidates' naive walks, the read-paired k-mer look-ups and the scores run on the device, a wavefront per sequence, and
      * nothing is written to the graph.  seqs are in their natural orientation, minKmerCov holds one floor per sequence.  Returns, per sequence,

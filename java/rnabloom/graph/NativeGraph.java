@@ -143,6 +143,18 @@ public final class NativeGraph {
      *  at outBases + i * (fragD + 2), in walking order; outCount (may be null) their counts.  Read-only. */
     public static native void extendPE(long h, ByteBuffer seq, long[] offsets, int n, int direction, float[] minKmerCov, byte[] outBases,
                                        float[] outCount, int[] recs);
+    /** Joining of n read pairs through the graph (rb_graph_join_pairs; GraphUtils.join, R/util/GraphUtils.java:892-1147): pair i is lseq[loffsets[i],
+     *  loffsets[i + 1]) and rseq[roffsets[i], roffsets[i + 1]).  outOffsets[n + 1] is filled from the lengths, bound, d and k alone; outSeq == null
+     *  sizes the output only.  Else recs holds 12 ints per pair — outcome (0 none: the reference returns null, 1 joined, 2 not judged), why
+     *  (0 the left walk reached the right read's first k-mer, 1 a k-mer inside the right read, 2 the right walk reached the left read's last
+     *  k-mer, 3 a k-mer of the left path, 4 the right walk met a loop or a homopolymer, 5 both walks ended, 6 a read shorter than k, 7 a letter
+     *  outside ACGTU), how the left and the right walk ended (0 not run, 1 no neighbour, 2 loop or homopolymer, 3 the branch step returned
+     *  nothing, 4 a homopolymer inside a step's k-mers, 5 bound reached, 6 returned), k-mers added by each, branch steps taken by each, the
+     *  index of the meeting k-mer (-1: none), the length of the text, Float.floatToRawIntBits of the two walks' final thresholds — and the
+     *  string the returned k-mers spell is recs[12 i + 9] bytes at outSeq + outOffsets[i].  maxTipLen is not read (the branch step does not
+     *  read it).  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
+    public static native int joinPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int bound,
+                                       float maxCovGradient, int maxTipLen, float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] recs);
     /** The fragment screens of n sequences (rb_graph_screen_fragments; GraphUtils.isBranchFree, isChimera and isBluntEndArtifact,
      *  R/util/GraphUtils.java:7651-7672, :7674-7760, :8535-8586): what = 1 branch-free | 2 chimera | 4 blunt-end artifact; gateHandleOr0 is the
      *  handle whose dbgbf is the BloomFilter assembledKmers (0 only for what == 1); maxDepth is maxEdgeClipLength; maxVisits the budget of one

@@ -454,6 +454,26 @@ void FN(extendPE)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets,
     lr(e, offsets, po, JNI_ABORT); fr(e, minKmerCov, pf, JNI_ABORT); br(e, outBases, ob, 0); fr(e, outCount, oc, 0); ir(e, recs, rc10, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_join_pairs: a record (rb_join_rec, 48 bytes) is 12 ints to Java: outcome, why, l_end, r_end, l_added, r_added, l_forks, r_forks, index, out_len and the
+ * bits of the two float thresholds (Float.intBitsToFloat).  outSeq == null (then recs may be null too) sizes the output: outOffsets is filled and outOffsets[n] returned */
+jint FN(joinPairs)(JNIEnv *e, jclass c, jlong h, jobject lseq, jlongArray loffsets, jobject rseq, jlongArray roffsets, jint n, jint bound, jfloat maxCovGradient,
+                   jint maxTipLen, jfloat minKmerCov, jlongArray outOffsets, jobject outSeq, jintArray recs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!loffsets || !roffsets || !outOffsets || (*e)->GetArrayLength(e, loffsets) <= n || (*e)->GetArrayLength(e, roffsets) <= n ||
+                            (*e)->GetArrayLength(e, outOffsets) <= n || (outSeq && (!recs || (*e)->GetArrayLength(e, recs) / 12 < n))))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "joinPairs: an array is too short for n pairs");
+        return 0;
+    }
+    jlong *lo = la(e, loffsets), *ro = la(e, roffsets), *oo = la(e, outOffsets);
+    jint *rc12 = ia(e, recs);
+    int rc = rb_graph_join_pairs(G(h), (const char *)direct(e, lseq), (const int64_t *)lo, (const char *)direct(e, rseq), (const int64_t *)ro, n, bound,
+                                 maxCovGradient, maxTipLen, minKmerCov, (int64_t *)oo, outSeq ? (char *)direct(e, outSeq) : 0, (rb_join_rec *)rc12);
+    if (rc == 0 && oo && n >= 0 && oo[n] > 0x7fffffffLL) rc = RB_ERR_INVALID;      /* the capacity layout does not fit the int this returns: smaller batches */
+    const jint cap = rc == 0 && oo && n >= 0 ? (jint)oo[n] : 0;
+    lr(e, loffsets, lo, JNI_ABORT); lr(e, roffsets, ro, JNI_ABORT); lr(e, outOffsets, oo, 0); ir(e, recs, rc12, 0);
+    if (rc) throw_rc(e, rc);
+    return cap;
+}
 /* rb_graph_screen_fragments: a record (rb_screen_rec, 32 bytes) is 8 ints to Java: flags, chim_why, break_i, break_j, right_len, left_len, blunt_why, boundary */
 void FN(screenFragments)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlongArray offsets, jint n, jint what, jint lookahead, jint maxDepth,
                          jlong maxVisits, jintArray recs) {

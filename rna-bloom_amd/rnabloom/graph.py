@@ -598,6 +598,40 @@ class BloomFilterDeBruijnGraph:
         return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes() if rc["outcome"] != self.OVL_NONE else None, int(rc["outcome"]),
                  bool(rc["flags"] & self.OVL_SWAPPED)) for i, rc in enumerate(recs)]
 
+    JOIN_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("l_end", "<i4"), ("r_end", "<i4"), ("l_added", "<i4"), ("r_added", "<i4"),
+                           ("l_forks", "<i4"), ("r_forks", "<i4"), ("index", "<i4"), ("out_len", "<i4"), ("l_threshold", "<f4"), ("r_threshold", "<f4")])
+    JOIN_OUTCOMES = ("none", "joined", "not_judged")
+    JOIN_WHYS = ("reached_right", "inside_right", "reached_left", "paths_meet", "right_loop", "exhausted", "short", "invalid_letter")
+    JOIN_ENDS = ("not_run", "no_neighbor", "loop", "step_none", "ext_homopolymer", "bound", "returned")
+    JOIN_NONE, JOIN_JOINED, JOIN_NOT_JUDGED = range(3)
+    JOIN_MAX_BOUND = 65536
+
+    def joinPairsFlat(self, lseq, loffsets, rseq, roffsets, bound, maxCovGradient, maxTipLen, minKmerCov=1.0):
+        """rb_graph_join_pairs on flat host text (GraphUtils.join, R/util/GraphUtils.java:892-1147): pair i is lseq[loffsets[i]:loffsets[i + 1]]
+        and rseq[roffsets[i]:roffsets[i + 1]] (uint8).  Returns (out, out_offsets, recs): one JOIN_DTYPE record per pair, the string the
+        returned k-mer list spells (upper-case A C G T) at out[out_offsets[i]:out_offsets[i] + recs[i]["out_len"]].  Read-only."""
+        flat = lambda a: np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+        lseq, rseq = flat(lseq), flat(rseq)
+        lo, ro = np.ascontiguousarray(loffsets, dtype=np.int64), np.ascontiguousarray(roffsets, dtype=np.int64)
+        n = lo.size - 1
+        oo = np.zeros(n + 1, np.int64)
+        args = (self.h, _ptr(lseq), _ptr(lo), _ptr(rseq), _ptr(ro), n, bound, maxCovGradient, maxTipLen, minKmerCov, _ptr(oo))
+        check(lib.rb_graph_join_pairs(*args, None, None))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        recs = np.zeros(n, self.JOIN_DTYPE)
+        check(lib.rb_graph_join_pairs(*args, _ptr(out), _ptr(recs)))
+        return out, oo, recs
+
+    def joinPairs(self, lefts, rights, bound, maxCovGradient, maxTipLen, minKmerCov=1.0):
+        """GraphUtils.join of each pair's getKmers lists: per pair (bytes or None, outcome, why) — the string the returned k-mers spell
+        (None where the reference returns null, and for a pair that is JOIN_NOT_JUDGED: a read shorter than k, a letter outside ACGTU),
+        the JOIN_* outcome and the index into JOIN_WHYS of the line that returned."""
+        enc = lambda seqs: [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        (lseq, lo), (rseq, ro) = _pack(enc(lefts)), _pack(enc(rights))
+        out, oo, recs = self.joinPairsFlat(lseq, lo, rseq, ro, bound, maxCovGradient, maxTipLen, minKmerCov)
+        return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes() if rc["outcome"] == self.JOIN_JOINED else None, int(rc["outcome"]), int(rc["why"]))
+                for i, rc in enumerate(recs)]
+
     EXT_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("n_candidates", "<i4"), ("out_len", "<i4"), ("pairs", "<i4"),
                           ("last_partnered", "<i4"), ("winner", "<i4"), ("score", "<f4")])
     EXT_OUTCOMES = ("none", "single", "first", "second")

@@ -185,6 +185,22 @@ def getKmersMinCoverage(graph, seqs, minCoverage):
     return out
 
 
+def overlapAndConnect(graph, lefts, rights, bound, minOverlap, maxCovGradient, maxTipLen, minKmerCov=1.0):
+    """GraphUtils.overlapAndConnect (R/util/GraphUtils.java:5065-5090) for many read pairs: graph.overlapPairs of all of them, then ONE
+    graph.joinPairs over the pairs overlap returned null for.  Returns per pair (bytes or None, how): the string the returned k-mers spell
+    and "overlap" / "join"; None with "none" where both return null, with "not_judged" where join cannot be asked (a read shorter than k,
+    a letter outside ACGTU).  A pair overlap would rescue by writing to the graph comes back as (joined text before the rescue, "rescue"),
+    not joined: the caller applies graph.applyOverlapRescue, as with overlapPairs alone."""
+    ov = graph.overlapPairs(lefts, rights, minOverlap, minKmerCov)
+    res = [(text, "rescue" if outcome == graph.OVL_RESCUE else "overlap") for text, outcome, _ in ov]
+    todo = [i for i, (_, outcome, _) in enumerate(ov) if outcome == graph.OVL_NONE]
+    if todo:
+        jn = graph.joinPairs([lefts[i] for i in todo], [rights[i] for i in todo], bound, maxCovGradient, maxTipLen, minKmerCov)
+        for i, (text, outcome, _) in zip(todo, jn):
+            res[i] = (text, "join") if outcome == graph.JOIN_JOINED else (None, "not_judged" if outcome == graph.JOIN_NOT_JUDGED else "none")
+    return res
+
+
 def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
     """GraphUtils.extendSE(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6454-6565) for many sequences: first to the left,
     then to the right, each sequence is extended across branches by extendLeftSE / extendRightSE until the step returns nothing at the
