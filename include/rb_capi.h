@@ -591,6 +591,51 @@ typedef struct rb_screen_rec {          /* 32 bytes */
 } rb_screen_rec;
 int rb_graph_screen_fragments(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int what, int lookahead,
                               int max_depth, int64_t max_visits, rb_screen_rec *out);
+/* GraphUtils.represented(kmers, graph, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity) (R/util/GraphUtils.java:711-824) for
+ * n host sequences: the worker's screen between isBranchFree and isChimera.  A wavefront per sequence on the device; read-only on both
+ * handles, every sequence judged against the filters as they stood when the call began.  Sequences, letters and the gate (required here) are
+ * rb_graph_screen_fragments'; the graph's read-paired k-mer distance d gives maxNumBubbleKmers = d + k.
+ *   The scan (:726-804) takes every run of k-mers in the gate; a run shorter than `lookahead` is skipped over and changes nothing.  The first
+ *   run that counts, if it starts at k-mer startIndex > 0, tests the left edge (:745-753): where startIndex >= max_edge_clip or the ungated
+ *   static hasDepthLeft(kmers[0], max_edge_clip - startIndex) holds, the gated greedyExtendLeft from k-mer startIndex, bound startIndex, must
+ *   add exactly startIndex k-mers whose assembled text has getPercentIdentity >= percent_identity against the sequence's first
+ *   startIndex + k - 1 letters; otherwise the edge is excused.  Every later run tests the gap behind the last run that counted (:756-796):
+ *   wider than d + k k-mers fails; one narrower than k is widened by up to k - width k-mers on each side (:768-782: the index moves BEFORE
+ *   the lookup, so a widening that stops on a k-mer outside the gate stays on it); the gated getMaxCoveragePath(left, right, width +
+ *   max_indel) must give a path of width - max_indel .. width + max_indel k-mers whose assembled text passes the identity test against the
+ *   letters of k-mers left + 1 .. right - 1.  The right edge (:806-818) mirrors the left one.  No run that counts: false (:820).
+ *   getPercentIdentity is SeqUtils' (R/util/SeqUtils.java:164-229), stale last column of getDistance included, with the reference's operands
+ *   in its order: s the assembled walk or path read left to right, t the sequence's letters; the comparison is one in float32.
+ *   max_visits: as rb_graph_screen_fragments' — a hasDepth* search that would pass it leaves the sequence not judged (RB_SCREEN_OVER_BUDGET).
+ *   out[12 i ..]: rb_repr_rec.  flags: RB_REPR_REPRESENTED, or one of RB_SCREEN_BAD_LETTER / RB_SCREEN_NO_KMER / RB_SCREEN_OVER_BUDGET for a
+ *   sequence that is not judged: nothing is guessed for it, every other field is the blank record's (why -1, the five test fields -1, the
+ *   rest 0).  why: the line that returned (RB_REPR_WHY_*).  left, right, expected_len, found_len, distance describe the deciding test — left
+ *   edge: 0 and startIndex; gap: left and right after the widening; right edge: lastRepresentedKmerFoundIndex and numKmers - 1; the expected
+ *   length; the walk's or path's length (-1: no path); the getDistance value where an alignment was made, else -1 — and are all -1 for why
+ *   0, 1 and 4.  tests_passed counts the edge and gap tests that passed before the deciding line, distance_sum adds up their distances,
+ *   tips_skipped counts the edges hasDepth* excused: a true record says how it came to be true.  path_form is the form of the last
+ *   getMaxCoveragePath result: 0 none (or none asked), 1 the left walk arrived, 2 the right walk arrived, 3 spliced (:1748-1763).
+ * Pieces, scratch per k-mer and per sequence as rb_graph_screen_fragments (48 bytes a record); a wavefront's walk rows hold
+ * P = max(the longest sequence's k-mers, max(2 k, d + k) + max_indel, min(max_edge_clip, max_visits)) entries, and 4 bytes per letter of
+ * the longest sequence where that is more than 1024 letters (the alignment row leaves LDS).  Profile entry "represented".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle or gate; a shard handle; a destroyed dbgbf or counting filter; a gate that is a
+ * shard handle, on another device, with another k or without its dbgbf; lookahead outside [0, 16]; max_indel outside [0, 4096];
+ * max_edge_clip outside [0, 2^20]; a percent_identity that is not finite; a sequence of more than 2^24 k-mers; max_visits < 0; n < 0; with n > 0: a null offsets / out, a null seq
+ * where there is text, decreasing offsets.  n == 0 succeeds and touches nothing. */
+enum { RB_REPR_REPRESENTED = 1 };                                                                                                /* rb_repr_rec.flags, beside the not-judged bits of rb_screen_rec */
+enum { RB_REPR_WHY_TRUE = 0, RB_REPR_WHY_NO_RUN = 1, RB_REPR_WHY_LEFT_LENGTH = 2, RB_REPR_WHY_LEFT_IDENTITY = 3, RB_REPR_WHY_WIDE_GAP = 4,
+       RB_REPR_WHY_NO_PATH = 5, RB_REPR_WHY_PATH_LENGTH = 6, RB_REPR_WHY_PATH_IDENTITY = 7, RB_REPR_WHY_RIGHT_LENGTH = 8,
+       RB_REPR_WHY_RIGHT_IDENTITY = 9 };                                                                                         /* rb_repr_rec.why */
+enum { RB_REPR_PATH_NONE = 0, RB_REPR_PATH_LEFT = 1, RB_REPR_PATH_RIGHT = 2, RB_REPR_PATH_SPLICED = 3 };                         /* rb_repr_rec.path_form */
+typedef struct rb_repr_rec {            /* 48 bytes */
+    int32_t flags, why;
+    int32_t left, right, expected_len, found_len, distance;     /* the deciding test, or -1 */
+    int32_t tests_passed, distance_sum, tips_skipped;
+    int32_t path_form;
+    int32_t reserved;                   /* 0 */
+} rb_repr_rec;
+int rb_graph_represented(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                         int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

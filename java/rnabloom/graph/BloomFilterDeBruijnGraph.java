@@ -617,6 +617,30 @@ public class BloomFilterDeBruijnGraph {
         NativeGraph.screenFragments(handle, assembledKmers != null ? assembledKmers.getNativeHandle() : 0L, text, off, n, what, lookahead, maxDepth, 0L, records);
     }
 
+    public static final int REPR_REPRESENTED = 1;
+
+    /**
+     * GraphUtils.represented(kmers, graph, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity)
+     * (src/rnabloom/util/GraphUtils.java:711-824) for a batch of sequences in ONE native call: the scan over the gate bits, the gated walks
+     * and paths, the depth searches and the alignments run on the device.  screeningBf is the worker's screeningBf — a stand-alone
+     * BloomFilter, required.  records (12 * seqs.length ints) receives the records of NativeGraph.represented: records[12 i] holds
+     * REPR_REPRESENTED in bit 0, or a bit of SCREEN_NOT_JUDGED where the sequence stays with the reference's own code; records[12 i + 1]
+     * says which line of the reference returned.
+     */
+    public void represented(String[] seqs, BloomFilter screeningBf, int lookahead, int maxIndelSize, int maxEdgeClipLength, float percentIdentity,
+                            int[] records) {
+        final int n = seqs.length;
+        if (records == null || records.length < 12L * n) throw new IllegalArgumentException("represented: records must hold " + 12L * n + " ints");
+        if (screeningBf == null || screeningBf.getNativeWhich() != NativeGraph.DBGBF || screeningBf.getNativeHandle() == handle)
+            throw new IllegalArgumentException("represented: the gate must be a stand-alone BloomFilter");
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("represented: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        NativeGraph.represented(handle, screeningBf.getNativeHandle(), text, off, n, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, 0L, records);
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

@@ -163,6 +163,15 @@ public final class NativeGraph {
      *  greedy walks, blunt_why, the arm's boundary index.  Read-only on both handles. */
     public static native void screenFragments(long h, long gateHandleOr0, ByteBuffer seq, long[] offsets, int n, int what, int lookahead,
                                               int maxDepth, long maxVisits, int[] recs);
+    /** GraphUtils.represented (rb_graph_represented; R/util/GraphUtils.java:711-824) of n sequences: gateHandle is the handle whose dbgbf is the
+     *  worker's screeningBf (required); maxVisits the budget of one static hasDepth* search (0: the library's default).  recs holds 12 ints
+     *  per sequence — flags (bit 0: represented; not judged: 8 a letter outside ACGTU, 16 no k-mer, 32 a depth search ran out of its budget),
+     *  why (the line that returned: 0 true, 1 no run of assembled k-mers, 2 / 3 the left edge's length / identity, 4 a gap wider than d + k,
+     *  5 no path, 6 / 7 the path's length / identity, 8 / 9 the right edge's length / identity), the deciding test's left, right, expected
+     *  length, found length and distance (-1 where there is none), the tests passed before it, the sum of their distances, the edges
+     *  hasDepth* excused, the form of the last path (0 none, 1 from the left, 2 from the right, 3 spliced), 0.  Read-only on both handles. */
+    public static native void represented(long h, long gateHandle, ByteBuffer seq, long[] offsets, int n, int lookahead, int maxIndelSize,
+                                          int maxEdgeClipLength, float percentIdentity, long maxVisits, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

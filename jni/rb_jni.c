@@ -489,6 +489,22 @@ void FN(screenFragments)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, 
     lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc8, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_represented: a record (rb_repr_rec, 48 bytes) is 12 ints to Java: flags, why, left, right, expected_len, found_len, distance, tests_passed,
+ * distance_sum, tips_skipped, path_form, 0 */
+void FN(represented)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlongArray offsets, jint n, jint lookahead, jint maxIndelSize,
+                     jint maxEdgeClipLength, jfloat percentIdentity, jlong maxVisits, jintArray recs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!offsets || !recs || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, recs) / 12 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "represented: an array is too short for n sequences");
+        return;
+    }
+    jlong *po = la(e, offsets);
+    jint *rc12 = ia(e, recs);
+    int rc = rb_graph_represented(G(h), gate ? G(gate) : NULL, (const char *)direct(e, seq), (const int64_t *)po, n, lookahead, maxIndelSize, maxEdgeClipLength,
+                                  percentIdentity, maxVisits, (rb_repr_rec *)rc12);
+    lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc12, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -19,6 +19,7 @@
 
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
+#include "rb_align.hpp"
 
 using namespace rb;
 
@@ -29,14 +30,11 @@ namespace {
 
 constexpr int CE_TPB = 256;
 constexpr int CE_WAVES = CE_TPB / 64;         // sequences / gaps per workgroup: a wavefront each
-constexpr int LEV_LDS = 1024;                 // columns of a Levenshtein row a wavefront keeps in LDS; longer rows live in device scratch
 constexpr int CE_MAX_INDEL = 4096;               // the largest max_indel_size taken (the reference's default is 1)
 constexpr size_t WALK_CHUNK_BYTES = (size_t)256 << 20;      // device scratch of the walks that run together
 
 static_assert(sizeof(rb_corr_gap) == 20, "rb_corr_gap is 20 bytes");
 
-// a base as the walk kernels write it: upper case, U as T (the letters of a good k-mer are all of ACGTU)
-__device__ __forceinline__ uint8_t ce_norm(uint32_t ch) { const uint32_t c = letter_code(ch); return c < 4u ? code_letter(c) : (uint8_t)ch; }
 __device__ __forceinline__ bool ce_contains(const FilterView &fv, uint64_t h0) { return bits_lookup(fv.dbg, fv.dbg_mod, fv.dbg_h, fv.kmul, h0); }
 // Kmer.getLeftVariants / getRightVariants(k, numHash, graph, minKmerCov) (R/graph/Kmer.java:361-405, CanonicalKmer.java:387-) of the k-mer with
 // getKmers hashes (f, r): is any alternative of the base ch (side 2: the first base, 3: the last) a k-mer with count >= min_cov?  The hashes are
@@ -69,52 +67,6 @@ __device__ __forceinline__ bool ce_has_neighbors(const FilterView &fv, int stran
 // Common.getMedian (R/util/Common.java:41-50) of the n counts get(0 .. n-1), by the whole wavefront
 template <class GET> __device__ __forceinline__ float ce_median(GET get, int n, uint32_t lane) {
     return median_code([&](int p) { return count_code_of(get(p)); }, n, lane);
-}
-
-// SeqUtils.getDistance(String, String) (R/util/SeqUtils.java:190-229) by the whole wavefront.  The reference's System.arraycopy(v1, 0, v0, 0, tLen)
-// copies tLen of the tLen + 1 entries, so v0[tLen] keeps its first value tLen: every column but the last is the Levenshtein matrix D, and the
-// result is min(D[sLen][tLen-1] + 1, tLen + 1, D[sLen-1][tLen-1] + (s[sLen-1] != t[tLen-1])) — reproduced.  Columns 0 .. tLen-1 of a row are held
-// 64 to a step, lane by lane (LDS, or device scratch for tLen > LEV_LDS): new[j] = min(new[j-1] + 1, old[j] + 1, old[j-1] + cost) is
-// tmp[j] = min(old[j] + 1, old[j-1] + cost) followed by new[j] - j = the running minimum of tmp[j'] - j' — a prefix minimum across the lanes.
-// A lane reads back only what it wrote itself; its left neighbour's old value comes by a shuffle.  sLen, tLen >= 1.
-template <class S, class T> __device__ int ce_distance(S s, int slen, T t, int tlen, int *row, uint32_t lane) {
-    bool diff = slen != tlen;
-    if (!diff) {
-        for (int x0 = 0; x0 < slen && !diff; x0 += 64) { const int x = x0 + (int)lane; diff = __ballot(x < slen && s(x) != t(x)) != 0ull; }
-        if (!diff) return 0;                                                    // s.equals(t)
-    }
-    const int ncol = tlen;                                                      // columns 0 .. tLen - 1
-    for (int j = (int)lane; j < ncol; j += 64) row[j] = j;
-    int d_prev_last = ncol - 1, d_last = ncol - 1;                              // D[i][tLen-1] of the previous / this row
-    for (int i = 1; i <= slen; ++i) {
-        const uint32_t sc = s(i - 1);
-        int carry = 0x3fffffff, carry_old = 0;
-        for (int j0 = 0; j0 < ncol; j0 += 64) {
-            const int j = j0 + (int)lane;
-            const bool on = j < ncol;
-            const int o = on ? row[j] : 0x3fffffff;
-            int oprev = __shfl_up(o, 1, 64);
-            if (lane == 0) oprev = carry_old;
-            carry_old = __shfl(o, 63, 64);
-            int v;
-            if (!on) v = 0x3fffffff;
-            else if (j == 0) v = i;
-            else v = min(o + 1, oprev + (sc == (uint32_t)t(j - 1) ? 0 : 1)) - j;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d, 64); if ((int)lane >= d) v = min(v, u); }
-            v = min(v, carry);
-            carry = __shfl(v, 63, 64);
-            if (on) row[j] = v + j;
-            if (j0 + 64 >= ncol) { d_prev_last = d_last; d_last = __shfl(v + j, (ncol - 1) - j0, 64); }
-        }
-    }
-    const int cost = s(slen - 1) == (uint32_t)t(tlen - 1) ? 0 : 1;
-    return min(min(d_last + 1, tlen + 1), d_prev_last + cost);
-}
-// SeqUtils.getPercentIdentity(String, String) :164-175
-__device__ __forceinline__ float ce_identity(int d, int alen, int blen) {
-    if (alen <= blen) return ((float)(blen - d)) / (float)blen;
-    return ((float)(alen - d)) / (float)alen;
 }
 
 // ---- gap scan (:3730-3855, :3857): a wavefront per sequence ballots 64 counts at a time; a run of counts below T that ends at a good k-mer is a gap,

@@ -6,14 +6,19 @@
 // wavefront per sequence: lanes first take the sequence's k-mers side by side (gate bit, variants), the reference's sequential scans then
 // run over ballots of the gate bits, and every walk advances with a lane per neighbour base and — where several neighbours pass — a lane
 // per candidate for the lookahead's depth-first search.  Nothing is written to the graph or the gate (DESIGN.md §5 "Fragment screens").
+//   rb_graph_represented = GraphUtils.represented (:711-824), the worker's screen between isBranchFree and isChimera, is k_represented: the same
+// prologue, rows, walks, paths and depth searches, and SeqUtils.getPercentIdentity (rb_align.hpp) of every edge walk and gap path that has the
+// expected length (DESIGN.md §5 "Represented").
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
 #include "rb_repeat.hpp"
+#include "rb_align.hpp"
 
 using namespace rb;
 
@@ -28,6 +33,8 @@ constexpr int SC_MAX_SLOTS = 2048;        // wavefronts of a launch at the most 
 constexpr int SC_GREEDY_BOUND = 1000;     // isChimera's greedyExtendRight / Left bound (:7746-7748)
 constexpr int SC_MAX_LOOKAHEAD = 16;      // rb_graph_greedy_extend's cap
 constexpr int SC_MAX_DEPTH = 1 << 20;     // the largest max_depth taken (rb_graph_greedy_extend's largest bound)
+constexpr int SC_MAX_ROW = 1 << 24;       // represented's walk rows grow with the longest sequence: entries of one at the most
+constexpr int SC_MAX_INDEL = 4096;        // the largest max_indel taken by represented (rb_graph_correct_errors' cap; the reference's default is 1)
 constexpr size_t SC_ROW_BUDGET = (size_t)512 << 20;   // device scratch all wavefronts' rows may take together (at least 16 wavefronts run whatever a row costs)
 
 // One level of a candidate's depth-first search (getMaxMedianCoverage*): the path's k-mer at this level (both strands' hashes in walking order,
@@ -44,6 +51,8 @@ struct ScArgs {
     ScGate gate;
     uint64_t kmul;
     int stranded, k, what, lookahead, max_depth, read_d, cap, max_visits;   // cap: entries of a walk row
+    int max_indel;                           // represented: maxIndelSize, percentIdentity (max_depth is its maxEdgeClipLength)
+    float percent_identity;
     int64_t pn;
     const int64_t *kof;                      // k-mer offsets of the piece's sequences
     const uint64_t *F, *R;                   // their getKmers rows
@@ -52,6 +61,7 @@ struct ScArgs {
     const uint64_t *codes;                   // the piece's batch: 2-bit codes and usable bits of its letters
     const uint32_t *valid, *woff;
     rb_screen_rec *recs;
+    rb_repr_rec *reprs;                      // represented's records instead
 };
 
 // A wavefront's rows in device scratch, `cap` entries each: two rows of hashes (the forward hashes of the k-mers a walk added — Kmer.equals
@@ -220,22 +230,30 @@ __device__ bool sc_equals_chain(int k, const uint8_t *tc, int c, const uint8_t *
     return __ballot(ne) == 0ull;
 }
 // HashSet.contains: is chain k-mer c of text tc (forward hash f) one of the n k-mers a walk added — entry e is chain k-mer e + 1 of text te with
-// forward hash hrow[e]?  A lane per entry compares the hashes; an equal hash is confirmed on the bases.
-__device__ bool sc_contains(int k, const uint64_t *hrow, const uint8_t *te, int n, const uint8_t *tc, int c, uint64_t f, bool rev, uint32_t lane) {
+// forward hash hrow[e]?  A lane per entry compares the hashes; an equal hash is confirmed on the bases.  *where: the entry (a walk's entries differ).
+__device__ bool sc_contains(int k, const uint64_t *hrow, const uint8_t *te, int n, const uint8_t *tc, int c, uint64_t f, bool rev, uint32_t lane,
+                            int *where = nullptr) {
     for (int e0 = 0; e0 < n; e0 += 64) {
         const int e = e0 + (int)lane;
         unsigned long long m = __ballot(e < n && hrow[e] == f);
         while (m) {
             const int hit = e0 + (int)__builtin_ctzll(m);
             m &= m - 1ull;
-            if (sc_equals_chain(k, tc, c, te, hit + 1, rev, lane)) return true;
+            if (sc_equals_chain(k, tc, c, te, hit + 1, rev, lane)) { if (where) *where = hit; return true; }
         }
     }
     return false;
 }
 
-// getMaxCoveragePath(graph, left, right, bound, lookahead, bf) != null (:1677-1776) for left = k-mer li and right = k-mer ri of the sequence
-__device__ bool sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int li, int ri, int bound, uint32_t lane) {
+// getMaxCoveragePath(graph, left, right, bound, lookahead, bf) (:1677-1776) for left = k-mer li and right = k-mer ri of the sequence.  form 0:
+// null; 1: the left walk arrived, the path is its n0 k-mers (chain k-mers 1 .. n0 of text 0); 2: the right walk arrived, the path is its n1
+// k-mers (chain k-mers n1 .. 1 of text 1, which runs right to left); 3: the right walk met entry idx of the left walk (:1748-1763), the path
+// is the left walk's entries 0 .. idx (the last of them is the k-mer met) and then the right walk's n1 k-mers.
+struct ScPath {
+    int form, n0, n1, idx;
+    __device__ __forceinline__ int size() const { return form == 1 ? n0 : form == 2 ? n1 : form == 3 ? idx + 1 + n1 : -1; }
+};
+__device__ ScPath sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int li, int ri, int bound, uint32_t lane) {
     const int k = a.k;
     const ScDir dr0 = sc_dir(a, 0), dr1 = sc_dir(a, 1);
     uint64_t A, B;
@@ -247,7 +265,7 @@ __device__ bool sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows &
         const uint64_t f = dr0.fwd(p.A, p.B);
         if (lane == 0) { rw.tx[0][k + n0] = (uint8_t)p.base; rw.h[0][n0] = f; }      // entry n0, kept only if the k-mer is added
         SC_FENCE();
-        if (sc_equals_seq(a, sq, dr0, rw.tx[0], n0 + 1, f, ri, lane)) return true;
+        if (sc_equals_seq(a, sq, dr0, rw.tx[0], n0 + 1, f, ri, lane)) return ScPath{1, n0, 0, 0};
         if (sc_contains(k, rw.h[0], rw.tx[0], n0, rw.tx[0], n0 + 1, f, false, lane)) break;
         A = p.A; B = p.B; ++n0;
     }
@@ -259,21 +277,22 @@ __device__ bool sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows &
         const uint64_t f = dr1.fwd(p.A, p.B);
         if (lane == 0) { rw.tx[1][k + n1] = (uint8_t)p.base; rw.h[1][n1] = f; }
         SC_FENCE();
-        if (sc_equals_seq(a, sq, dr1, rw.tx[1], n1 + 1, f, li, lane)) return true;
-        if (sc_contains(k, rw.h[0], rw.tx[0], n0, rw.tx[1], n1 + 1, f, true, lane)) return true;     // right path intersects the left path (:1748-1763)
-        if (sc_contains(k, rw.h[1], rw.tx[1], n1, rw.tx[1], n1 + 1, f, false, lane)) return false;   // :1769-1771
+        if (sc_equals_seq(a, sq, dr1, rw.tx[1], n1 + 1, f, li, lane)) return ScPath{2, n0, n1, 0};
+        int idx = 0;
+        if (sc_contains(k, rw.h[0], rw.tx[0], n0, rw.tx[1], n1 + 1, f, true, lane, &idx)) return ScPath{3, n0, n1, idx};     // right path intersects the left path (:1748-1763)
+        if (sc_contains(k, rw.h[1], rw.tx[1], n1, rw.tx[1], n1 + 1, f, false, lane)) break;          // :1769-1771
         A = p.A; B = p.B; ++n1;
     }
-    return false;
+    return ScPath{0, n0, n1, 0};
 }
 
-// greedyExtendRight / Left(graph, source, lookahead, 1000, bf) from k-mer s of the sequence into rows `side`: the number of k-mers added
-__device__ int sc_greedy_walk(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int side, int s, uint32_t lane) {
+// greedyExtendRight / Left(graph, source, lookahead, bound, bf) from k-mer s of the sequence into rows `side`: the number of k-mers added
+__device__ int sc_greedy_walk(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int side, int s, int bound, uint32_t lane) {
     const ScDir dr = sc_dir(a, side);
     uint64_t A, B;
     int n = 0;
     sc_walk_begin(a, sq, dr, s, rw.tx[side], A, B, lane);
-    while (n < SC_GREEDY_BOUND) {
+    while (n < bound) {
         const ScPick p = sc_greedy_step(a, dr, rw.tx[side], n, A, B, dfs, lane);
         if (!p.any) break;
         if (lane == 0) { rw.tx[side][a.k + n] = (uint8_t)p.base; rw.h[side][n] = dr.fwd(p.A, p.B); }
@@ -334,7 +353,7 @@ __device__ bool sc_chimera(const ScArgs &a, const ScSeq &sq, const ScRows &rw, S
         i = sc_next(sq, i, nk - 1, false, lane);
         if (i >= nk - 1) break;
         const int t = sc_next(sq, i + 1, nk - 1, true, lane);   // check to see if this is a small gap
-        if (t < nk - 1 && t - i <= max_gap && sc_max_cov_path(a, sq, rw, dfs, i - 1, t, t - i, lane)) { i = t + 1; continue; }
+        if (t < nk - 1 && t - i <= max_gap && sc_max_cov_path(a, sq, rw, dfs, i - 1, t, t - i, lane).form) { i = t + 1; continue; }
         break;
     }
     if (i == nk - 1) { rec.chim_why = RB_CHIM_WHY_ASSEMBLED; return false; }
@@ -344,13 +363,13 @@ __device__ bool sc_chimera(const ScArgs &a, const ScSeq &sq, const ScRows &rw, S
         j = sc_prev(sq, i + 1, j + 1, false, lane);              // (i where every k-mer down to i + 1 is in the gate: the loop's own end)
         if (j <= i) break;
         const int t = sc_prev(sq, i + 1, j, true, lane);
-        if (t > i && j - t <= max_gap && sc_max_cov_path(a, sq, rw, dfs, t, j + 1, j - t, lane)) { j = t - 1; continue; }
+        if (t > i && j - t <= max_gap && sc_max_cov_path(a, sq, rw, dfs, t, j + 1, j - t, lane).form) { j = t - 1; continue; }
         break;
     }
     ++j;
     rec.break_i = i; rec.break_j = j;
     if (j - i > max_gap) { rec.chim_why = RB_CHIM_WHY_WIDE_GAP; return false; }
-    const int n0 = sc_greedy_walk(a, sq, rw, dfs, 0, i, lane), n1 = sc_greedy_walk(a, sq, rw, dfs, 1, j, lane);
+    const int n0 = sc_greedy_walk(a, sq, rw, dfs, 0, i, SC_GREEDY_BOUND, lane), n1 = sc_greedy_walk(a, sq, rw, dfs, 1, j, SC_GREEDY_BOUND, lane);
     rec.right_len = n0; rec.left_len = n1;
     const bool meet = sc_walks_meet(a, rw, n0, n1, lane);
     rec.chim_why = meet ? RB_CHIM_WHY_PATHS_MEET : RB_CHIM_WHY_DISJOINT;
@@ -459,6 +478,19 @@ __device__ bool sc_has_variant(const ScArgs &a, const ScSeq &sq, int i) {
     return any;
 }
 
+// a letter outside ACGTU among the sequence's nk + k - 1 (lane l looks at 32 letters at a time)
+__device__ bool sc_bad_letter(const ScArgs &a, int64_t r, int nk, uint32_t lane) {
+    const uint32_t *vw = a.valid + a.woff[r];
+    const int letters = nk + a.k - 1;
+    bool bad = false;
+    for (int w = (int)lane; 32 * w < letters; w += 64) {
+        const int left = letters - 32 * w;
+        const uint32_t want = left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u;
+        bad = bad || (vw[w] & want) != want;
+    }
+    return __ballot(bad) != 0ull;
+}
+
 // the screens of sequence r of the piece, by one wavefront
 __device__ void sc_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, uint32_t lane) {
     const int64_t k0 = a.kof[r];
@@ -470,21 +502,10 @@ __device__ void sc_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *df
         if (lane == 0) a.recs[r] = rec;
         return;
     }
-    // a letter outside ACGTU: not judged (lane l looks at 32 letters at a time)
-    {
-        const uint32_t *vw = a.valid + a.woff[r];
-        const int letters = nk + a.k - 1;
-        bool bad = false;
-        for (int w = (int)lane; 32 * w < letters; w += 64) {
-            const int left = letters - 32 * w;
-            const uint32_t want = left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u;
-            bad = bad || (vw[w] & want) != want;
-        }
-        if (__ballot(bad)) {
-            rec.flags = RB_SCREEN_BAD_LETTER;
-            if (lane == 0) a.recs[r] = rec;
-            return;
-        }
+    if (sc_bad_letter(a, r, nk, lane)) {                         // not judged
+        rec.flags = RB_SCREEN_BAD_LETTER;
+        if (lane == 0) a.recs[r] = rec;
+        return;
     }
     const ScSeq sq{reinterpret_cast<const uint32_t *>(a.codes + a.woff[r]), a.F + k0, a.R + k0, a.cnt + k0, a.gbit + k0, nk, a.stranded};
     // the k-mers side by side: the gate bit of each, and whether it has a variant
@@ -520,7 +541,187 @@ __global__ void __launch_bounds__(SC_TPB) k_screen(ScArgs a, uint8_t *scratch, s
     }
 }
 
+// ---- represented (:711-824) ----
+__host__ __device__ inline rb_repr_rec repr_blank(int flags) { return rb_repr_rec{flags, -1, -1, -1, -1, -1, -1, 0, 0, 0, 0, 0}; }
+
+// getPercentIdentity(s, t) >= percentIdentity for s = the slen letters s(0 ..) of an assembled walk or path and t = the sequence's tlen >= 1
+// letters from t0 on; d: getDistance(s, t).  An empty path assembles to "": d = tLen (:196).  The row is in LDS up to LEV_LDS columns.
+template <class S>
+__device__ bool sc_identity_ok(const ScArgs &a, const ScSeq &sq, S s, int slen, int t0, int tlen, int *lds_row, int *dev_row, int &d, uint32_t lane) {
+    if (slen == 0) d = tlen;
+    else d = ce_distance(s, slen, [&](int x) -> uint32_t { return sq.base(t0 + x); }, tlen, tlen > LEV_LDS ? dev_row : lds_row, lane);
+    SC_FENCE();
+    return !(ce_identity(d, slen, tlen) < a.percent_identity);
+}
+
+// represented of sequence r of the piece, by one wavefront
+__device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, int *lds_row, int *dev_row, uint32_t lane) {
+    const int64_t k0 = a.kof[r];
+    const int nk = (int)(a.kof[r + 1] - k0), k = a.k, clip = a.max_depth, max_indel = a.max_indel;
+    if (nk == 0 || sc_bad_letter(a, r, nk, lane)) {
+        if (lane == 0) a.reprs[r] = repr_blank(nk == 0 ? RB_SCREEN_NO_KMER : RB_SCREEN_BAD_LETTER);
+        return;
+    }
+    const ScSeq sq{reinterpret_cast<const uint32_t *>(a.codes + a.woff[r]), a.F + k0, a.R + k0, a.cnt + k0, a.gbit + k0, nk, a.stranded};
+    for (int i = (int)lane; i < nk; i += 64) {
+        const uint64_t f = sq.F[i];
+        a.gbit[k0 + i] = (uint8_t)bits_lookup(a.gate.bits, a.gate.mod, a.gate.num_hash, a.kmul, a.stranded ? f : smin(f, sq.R[i]));
+    }
+    SC_FENCE();
+    rb_repr_rec rec = repr_blank(0);
+    rec.why = RB_REPR_WHY_TRUE;
+    auto decide = [&](int why, int left, int right, int expected, int found, int d) {
+        rec.why = why; rec.left = left; rec.right = right; rec.expected_len = expected; rec.found_len = found; rec.distance = d;
+    };
+    int last = -1, i = 0;                                        // lastRepresentedKmerFoundIndex
+    bool open = true;                                            // no line has returned yet
+    while (open) {
+        const int start = sc_next(sq, i, nk, true, lane);
+        if (start >= nk) break;
+        const int end = sc_next(sq, start + 1, nk, false, lane) - 1;
+        i = end + 1;
+        if (end - start + 1 < a.lookahead) continue;
+        if (start > 0 && last < 0) {                             // check left edge kmers (:745-753)
+            int v = 1, d = -1;
+            if (start < clip) v = sc_has_depth(a, sq, rw, 1, false, 0, clip - start, lane);
+            if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return; }
+            if (v == 0) ++rec.tips_skipped;
+            else {
+                const int n = sc_greedy_walk(a, sq, rw, dfs, 1, start, start, lane);
+                const uint8_t *tx = rw.tx[1];                    // the walk's letters run right to left
+                if (n != start) { decide(RB_REPR_WHY_LEFT_LENGTH, 0, start, start, n, -1); open = false; }
+                else if (!sc_identity_ok(a, sq, [&](int x) -> uint32_t { return tx[n + k - 1 - x]; }, n + k - 1, 0, start + k - 1, lds_row, dev_row, d, lane)) {
+                    decide(RB_REPR_WHY_LEFT_IDENTITY, 0, start, start, n, d); open = false;
+                } else { ++rec.tests_passed; rec.distance_sum += d; }
+            }
+        } else if (start > 0) {                                  // check gap kmers (:756-796)
+            int expected = start - last - 1, left = last, right = start, d = -1;
+            if (expected > a.read_d + k) { rec.why = RB_REPR_WHY_WIDE_GAP; open = false; continue; }
+            const int missing = k - expected;
+            if (missing > 0) {                                   // --left / ++right come before the lookup: a widening stops ON a k-mer outside the gate
+                const int lo = max(0, left - missing), hi = min(nk - 1, right + missing);
+                const int pl = sc_prev(sq, lo, left, false, lane), pr = sc_next(sq, right + 1, hi + 1, false, lane);
+                left = pl >= lo ? pl : lo; right = pr <= hi ? pr : hi;
+                expected = right - left - 1;
+            }
+            const ScPath p = sc_max_cov_path(a, sq, rw, dfs, left, right, expected + max_indel, lane);
+            const int plen = p.size();
+            rec.path_form = p.form;
+            if (!p.form) { decide(RB_REPR_WHY_NO_PATH, left, right, expected, -1, -1); open = false; continue; }
+            if (plen < expected - max_indel || plen > expected + max_indel) { decide(RB_REPR_WHY_PATH_LENGTH, left, right, expected, plen, -1); open = false; continue; }
+            const uint8_t *t0 = rw.tx[0], *t1 = rw.tx[1];
+            const int slen = plen ? plen + k - 1 : 0, tlen = expected + k - 1, n1 = p.n1, cut = p.idx + k;
+            bool ok;
+            if (p.form == 1) ok = sc_identity_ok(a, sq, [&](int x) -> uint32_t { return t0[1 + x]; }, slen, left + 1, tlen, lds_row, dev_row, d, lane);
+            else if (p.form == 2) ok = sc_identity_ok(a, sq, [&](int x) -> uint32_t { return t1[n1 + k - 1 - x]; }, slen, left + 1, tlen, lds_row, dev_row, d, lane);
+            else ok = sc_identity_ok(a, sq, [&](int x) -> uint32_t { return x < cut ? t0[1 + x] : t1[n1 - (x - cut)]; }, slen, left + 1, tlen, lds_row, dev_row, d, lane);
+            if (!ok) { decide(RB_REPR_WHY_PATH_IDENTITY, left, right, expected, plen, d); open = false; continue; }
+            ++rec.tests_passed; rec.distance_sum += d;
+        }
+        if (open) last = end;
+    }
+    if (open && last < 0) { rec.why = RB_REPR_WHY_NO_RUN; open = false; }
+    if (open && last < nk - 1) {                                 // check right edge kmers (:807-817)
+        const int expected = nk - last - 1;
+        int v = 1, d = -1;
+        if (expected < clip) v = sc_has_depth(a, sq, rw, 0, false, nk - 1, clip - expected, lane);
+        if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return; }
+        if (v == 0) ++rec.tips_skipped;
+        else {
+            const int n = sc_greedy_walk(a, sq, rw, dfs, 0, last, expected, lane);
+            const uint8_t *tx = rw.tx[0];
+            if (n != expected) { decide(RB_REPR_WHY_RIGHT_LENGTH, last, nk - 1, expected, n, -1); open = false; }
+            else if (!sc_identity_ok(a, sq, [&](int x) -> uint32_t { return tx[1 + x]; }, n + k - 1, last + 1, expected + k - 1, lds_row, dev_row, d, lane)) {
+                decide(RB_REPR_WHY_RIGHT_IDENTITY, last, nk - 1, expected, n, d); open = false;
+            } else { ++rec.tests_passed; rec.distance_sum += d; }
+        }
+    }
+    if (open) rec.flags = RB_REPR_REPRESENTED;
+    if (lane == 0) a.reprs[r] = rec;
+}
+
+// as k_screen; the alignment's row is the wavefront's LDS row, or — longer than LEV_LDS columns — the ints at lev_off of its scratch slot
+__global__ void __launch_bounds__(SC_TPB) k_represented(ScArgs a, uint8_t *scratch, size_t row_bytes, size_t lev_off) {
+    __shared__ ScLevel s_dfs[SC_WAVES][4 * SC_LEVELS];
+    __shared__ int s_row[SC_WAVES][LEV_LDS];
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const int64_t slot = (int64_t)blockIdx.x * SC_WAVES + wv, n_slots = (int64_t)gridDim.x * SC_WAVES;
+    uint8_t *mine = scratch + (size_t)slot * row_bytes;
+    const ScRows rw(mine, a.cap, a.k);
+    for (int64_t r = slot; r < a.pn; r += n_slots) {
+        sc_repr_one(a, r, rw, s_dfs[wv], s_row[wv], reinterpret_cast<int *>(mine + lev_off), lane);
+        SC_FENCE();
+    }
+}
+
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// What the two calls share once their arguments are checked: the pieces (rb_pieces.hpp), each with its getKmers rows, gate bits, records and the
+// wavefronts' rows.  REC is the record, `blank` what a sequence no kernel touches gets, `cap` the entries of a walk row, lev_cols the ints of
+// a wavefront's alignment row in device scratch (0: none), `launch` the kernel.
+template <class REC, class LAUNCH>
+void screen_run(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, const char *who, const char *entry, ScArgs a,
+                const std::vector<int64_t> &ko, const REC &blank, size_t lev_cols, REC *out, LAUNCH launch) {
+    for (int64_t i = 0; i < n; ++i) out[i] = blank;
+    if (ko[(size_t)n] == 0) return;
+    // the gate is read too: shared lock on it for the call, in address order with g's (rb_graph_greedy_extend)
+    rb_graph *gm = const_cast<rb_graph *>(gate);
+    std::shared_lock<std::shared_mutex> gate_lk;
+    if (gm && gm != g && gm < g) gate_lk = std::shared_lock<std::shared_mutex>(gm->rw);
+    RB_HIP(hipSetDevice(g->p.device));
+    HostPin pin_r(out, (size_t)n * sizeof(REC));
+    QueryLease q(g);
+    if (gm && gm != g && gm > g) gate_lk = std::shared_lock<std::shared_mutex>(gm->rw);
+    RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
+    if (gate) RB_REQUIRE(gate->dbg.bits, "%s: the gate's filter has been destroyed", who);
+    hipStream_t s = q.c->st;
+    const int k = g->k;
+    const size_t lev_off = sc_row_bytes(a.cap, k), row_bytes = lev_off + up16(lev_cols * sizeof(int));
+    const int64_t max_slots = std::max<int64_t>(16, std::min<int64_t>(SC_MAX_SLOTS, (int64_t)(SC_ROW_BUDGET / row_bytes)));
+    // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, gate bits, records and the
+    // wavefronts' rows; with profiling on the kernels of every piece are timed: entry `entry`
+    std::vector<int64_t> tab;
+    for_each_host_piece(g, s, seq, offsets, ko.data(), n, entry, [&](HostPiece &pc) {
+        const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
+        tab.assign((size_t)pn + 1, 0);
+        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
+        const rb_batch *b = pc.batch();
+        const int64_t slots = std::min<int64_t>(pn, max_slots);
+        const unsigned blocks = blocks_for(slots, SC_WAVES);
+        const size_t o_g = up16((size_t)pt * 4), o_rec = up16(o_g + (size_t)pt), o_row = up16(o_rec + (size_t)pn * sizeof(REC));
+        q.c->b0.reserve(tab.size() * 8);
+        q.c->b1.reserve((size_t)pt * 8);
+        q.c->b2.reserve((size_t)pt * 8);
+        q.c->b3.reserve(o_row + (size_t)blocks * SC_WAVES * row_bytes + 16);
+        uint8_t *base3 = q.c->b3.as<uint8_t>();
+        a.fv = g->view(0, 0);
+        a.gate = ScGate{gate ? gate->dbg.bits : nullptr, gate ? gate->dbg.mod : g->dbg.mod, gate ? gate->dbg.num_hash : 0};
+        a.kmul = kmul_of(k);
+        a.stranded = (int)g->stranded; a.k = k; a.read_d = g->read_d;
+        a.pn = pn;
+        a.kof = q.c->b0.as<int64_t>();
+        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
+        a.cnt = reinterpret_cast<float *>(base3);
+        a.gbit = base3 + o_g;
+        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
+        REC *recs = reinterpret_cast<REC *>(base3 + o_rec);
+        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemsetAsync(base3 + o_g, 0, o_rec - o_g, s));
+        pc.kernels_begin();
+        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        launch(a, recs, blocks, s, base3 + o_row, row_bytes, lev_off);
+        RB_HIP(hipGetLastError());
+        pc.kernels_end();
+        RB_HIP(hipMemcpyAsync(out + ra, recs, (size_t)pn * sizeof(REC), hipMemcpyDeviceToHost, s));
+    });
+}
+
+// the longest k-mer list among the n sequences
+int64_t longest_list(const std::vector<int64_t> &ko, int64_t n) {
+    int64_t longest = 0;
+    for (int64_t i = 0; i < n; ++i) longest = std::max(longest, ko[(size_t)i + 1] - ko[(size_t)i]);
+    return longest;
+}
 
 void screen_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int what, int lookahead, int max_depth,
                  int64_t max_visits, rb_screen_rec *out) {
@@ -540,73 +741,63 @@ void screen_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64
     RB_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
     if (n == 0) return;
     RB_REQUIRE(offsets && out, "%s: null argument", who);
+    std::vector<int64_t> ko((size_t)n + 1);
+    kmer_offsets(offsets, n, g->k, ko.data(), who);
+    RB_REQUIRE(offsets[n] == offsets[0] || seq, "%s: null sequence text", who);
+    const int64_t visits = max_visits ? max_visits : RB_SCREEN_DEFAULT_VISITS;
+    ScArgs a{};
+    a.what = what; a.lookahead = lookahead; a.max_depth = max_depth; a.max_indel = 0; a.percent_identity = 0.0f;
+    a.max_visits = (int)std::min<int64_t>(visits, INT32_MAX);
+    // a walk row: the greedy walks' 1000 k-mers, a gap's 2k <= 512, and a depth search's stack — as deep as the depth asked for (max_depth, or a
+    // stretch of the sequence) and never deeper than its budget, since every level costs a visit
+    a.cap = (int)std::max<int64_t>(SC_GREEDY_BOUND, std::min<int64_t>(std::max<int64_t>(max_depth, longest_list(ko, n)), visits));
+    a.reprs = nullptr;
+    // what no kernel touches: the sequences of pieces without a k-mer
+    const rb_screen_rec blank{RB_SCREEN_NO_KMER, 0, -1, -1, 0, 0, 0, -1};
+    screen_run(g, gate, seq, offsets, n, who, "screen_fragments", a, ko, blank, 0, out,
+               [](ScArgs &a, rb_screen_rec *recs, unsigned blocks, hipStream_t s, uint8_t *rows, size_t row_bytes, size_t) {
+                   a.recs = recs;
+                   hipLaunchKernelGGL(k_screen, dim3(blocks), dim3(SC_TPB), 0, s, a, rows, row_bytes);
+               });
+}
+
+void represented_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                      int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out) {
+    const char *who = "rb_graph_represented";
+    RB_REQUIRE(g && gate, "%s: null handle", who);
+    RB_REQUIRE(!g->shard, "%s: not available on a shard handle", who);
+    RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
+    RB_REQUIRE(gate->dbg.bits && !gate->shard && gate->p.device == g->p.device && gate->k == g->k,
+               "%s: the gate must be a filter on the same device with the same k", who);
+    RB_REQUIRE(lookahead >= 0 && lookahead <= SC_MAX_LOOKAHEAD, "%s: lookahead out of range [0, %d]", who, SC_MAX_LOOKAHEAD);
+    RB_REQUIRE(max_indel >= 0 && max_indel <= SC_MAX_INDEL, "%s: max_indel out of range [0, %d]", who, SC_MAX_INDEL);
+    RB_REQUIRE(max_edge_clip >= 0 && max_edge_clip <= SC_MAX_DEPTH, "%s: max_edge_clip out of range [0, %d]", who, SC_MAX_DEPTH);
+    RB_REQUIRE(std::isfinite(percent_identity), "%s: percent_identity is not finite", who);
+    RB_REQUIRE(max_visits >= 0, "%s: max_visits = %lld", who, (long long)max_visits);
+    RB_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
+    if (n == 0) return;
+    RB_REQUIRE(offsets && out, "%s: null argument", who);
     const int k = g->k;
     std::vector<int64_t> ko((size_t)n + 1);
     kmer_offsets(offsets, n, k, ko.data(), who);
     RB_REQUIRE(offsets[n] == offsets[0] || seq, "%s: null sequence text", who);
-    // what no kernel touches: the sequences of pieces without a k-mer
-    int64_t longest = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        rb_screen_rec &v = out[i];
-        v.flags = RB_SCREEN_NO_KMER; v.chim_why = 0; v.break_i = -1; v.break_j = -1; v.right_len = 0; v.left_len = 0; v.blunt_why = 0; v.boundary = -1;
-        longest = std::max(longest, ko[(size_t)i + 1] - ko[(size_t)i]);
-    }
-    if (ko[(size_t)n] == 0) return;
-    // the gate is read too: shared lock on it for the call, in address order with g's (rb_graph_greedy_extend)
-    rb_graph *gm = const_cast<rb_graph *>(gate);
-    std::shared_lock<std::shared_mutex> gate_lk;
-    if (gm && gm != g && gm < g) gate_lk = std::shared_lock<std::shared_mutex>(gm->rw);
-    RB_HIP(hipSetDevice(g->p.device));
-    HostPin pin_r(out, (size_t)n * sizeof(rb_screen_rec));
-    QueryLease q(g);
-    if (gm && gm != g && gm > g) gate_lk = std::shared_lock<std::shared_mutex>(gm->rw);
-    RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
-    if (gate) RB_REQUIRE(gate->dbg.bits, "%s: the gate's filter has been destroyed", who);
-    hipStream_t s = q.c->st;
-    const int64_t visits = max_visits ? max_visits : RB_SCREEN_DEFAULT_VISITS;
-    // a walk row: the greedy walks' 1000 k-mers, a gap's 2k <= 512, and a depth search's stack — as deep as the depth asked for (max_depth, or a
-    // stretch of the sequence) and never deeper than its budget, since every level costs a visit
-    const int cap = (int)std::max<int64_t>(SC_GREEDY_BOUND, std::min<int64_t>(std::max<int64_t>(max_depth, longest), visits));
-    const size_t row_bytes = sc_row_bytes(cap, k);
-    const int64_t max_slots = std::max<int64_t>(16, std::min<int64_t>(SC_MAX_SLOTS, (int64_t)(SC_ROW_BUDGET / row_bytes)));
-    // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, gate bits, records and the
-    // wavefronts' rows; with profiling on the kernels of every piece are timed: entry "screen_fragments"
-    std::vector<int64_t> tab;
-    for_each_host_piece(g, s, seq, offsets, ko.data(), n, "screen_fragments", [&](HostPiece &pc) {
-        const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
-        tab.assign((size_t)pn + 1, 0);
-        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-        const rb_batch *b = pc.batch();
-        const int64_t slots = std::min<int64_t>(pn, max_slots);
-        const unsigned blocks = blocks_for(slots, SC_WAVES);
-        const size_t o_g = up16((size_t)pt * 4), o_rec = up16(o_g + (size_t)pt), o_row = up16(o_rec + (size_t)pn * sizeof(rb_screen_rec));
-        q.c->b0.reserve(tab.size() * 8);
-        q.c->b1.reserve((size_t)pt * 8);
-        q.c->b2.reserve((size_t)pt * 8);
-        q.c->b3.reserve(o_row + (size_t)blocks * SC_WAVES * row_bytes + 16);
-        uint8_t *base3 = q.c->b3.as<uint8_t>();
-        ScArgs a;
-        a.fv = g->view(0, 0);
-        a.gate = ScGate{gate ? gate->dbg.bits : nullptr, gate ? gate->dbg.mod : g->dbg.mod, gate ? gate->dbg.num_hash : 0};
-        a.kmul = kmul_of(k);
-        a.stranded = (int)g->stranded; a.k = k; a.what = what; a.lookahead = lookahead; a.max_depth = max_depth; a.read_d = g->read_d; a.cap = cap;
-        a.max_visits = (int)std::min<int64_t>(visits, INT32_MAX);
-        a.pn = pn;
-        a.kof = q.c->b0.as<int64_t>();
-        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-        a.cnt = reinterpret_cast<float *>(base3);
-        a.gbit = base3 + o_g;
-        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
-        a.recs = reinterpret_cast<rb_screen_rec *>(base3 + o_rec);
-        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-        RB_HIP(hipMemsetAsync(base3 + o_g, 0, o_rec - o_g, s));
-        pc.kernels_begin();
-        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
-        hipLaunchKernelGGL(k_screen, dim3(blocks), dim3(SC_TPB), 0, s, a, base3 + o_row, row_bytes);
-        RB_HIP(hipGetLastError());
-        pc.kernels_end();
-        RB_HIP(hipMemcpyAsync(out + ra, a.recs, (size_t)pn * sizeof(rb_screen_rec), hipMemcpyDeviceToHost, s));
-    });
+    const int64_t visits = max_visits ? max_visits : RB_SCREEN_DEFAULT_VISITS, longest = longest_list(ko, n);
+    ScArgs a{};
+    a.what = 0; a.lookahead = lookahead; a.max_depth = max_edge_clip; a.max_indel = max_indel; a.percent_identity = percent_identity;
+    a.max_visits = (int)std::min<int64_t>(visits, INT32_MAX);
+    // a walk row: an edge walk is bounded by a stretch of the sequence, a gap's path by max(2k - 1, d + k) + max_indel (a gap narrower than k
+    // widens to 2k - 1 k-mers at the most), a depth search's stack by max_edge_clip and by its budget
+    const int64_t cap = std::max<int64_t>(std::max<int64_t>(longest, std::max<int64_t>(2 * (int64_t)k, (int64_t)g->read_d + k) + max_indel),
+                                          std::min<int64_t>(max_edge_clip, visits));
+    RB_REQUIRE(cap <= SC_MAX_ROW, "%s: a walk row of %lld entries (at most %d: a sequence of that many k-mers)", who, (long long)cap, SC_MAX_ROW);
+    a.cap = (int)cap;
+    a.recs = nullptr;
+    const size_t letters = (size_t)(longest ? longest + k - 1 : 0);
+    screen_run(g, gate, seq, offsets, n, who, "represented", a, ko, repr_blank(RB_SCREEN_NO_KMER), letters > (size_t)LEV_LDS ? letters : 0, out,
+               [](ScArgs &a, rb_repr_rec *recs, unsigned blocks, hipStream_t s, uint8_t *rows, size_t row_bytes, size_t lev_off) {
+                   a.reprs = recs;
+                   hipLaunchKernelGGL(k_represented, dim3(blocks), dim3(SC_TPB), 0, s, a, rows, row_bytes, lev_off);
+               });
 }
 
 }  // namespace
@@ -615,5 +806,9 @@ extern "C" {
 int rb_graph_screen_fragments(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int what, int lookahead,
                               int max_depth, int64_t max_visits, rb_screen_rec *out) {
     return guarded([&] { screen_call(g, gate, seq, offsets, n, what, lookahead, max_depth, max_visits, out); });
+}
+int rb_graph_represented(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                         int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out) {
+    return guarded([&] { represented_call(g, gate, seq, offsets, n, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, out); });
 }
 }  // extern "C"

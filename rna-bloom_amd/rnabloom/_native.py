@@ -25,6 +25,11 @@ CHIM_WHY_ENDS, CHIM_WHY_ASSEMBLED, CHIM_WHY_WIDE_GAP, CHIM_WHY_PATHS_MEET, CHIM_
 BLUNT_WHY_NO_ARM, BLUNT_WHY_LEFT_RANGE, BLUNT_WHY_RIGHT_RANGE, BLUNT_WHY_LEFT_FAILED, BLUNT_WHY_RIGHT_FAILED, BLUNT_WHY_LEFT_ARTIFACT, \
     BLUNT_WHY_RIGHT_ARTIFACT = range(7)
 SCREEN_DEFAULT_VISITS = 65536
+# rb_graph_represented: rb_repr_rec.flags bit 0 (its not-judged bits are SCREEN_BAD_LETTER / SCREEN_NO_KMER / SCREEN_OVER_BUDGET), why, path_form
+REPR_REPRESENTED = 1
+REPR_WHY_TRUE, REPR_WHY_NO_RUN, REPR_WHY_LEFT_LENGTH, REPR_WHY_LEFT_IDENTITY, REPR_WHY_WIDE_GAP, REPR_WHY_NO_PATH, REPR_WHY_PATH_LENGTH, \
+    REPR_WHY_PATH_IDENTITY, REPR_WHY_RIGHT_LENGTH, REPR_WHY_RIGHT_IDENTITY = range(10)
+REPR_PATH_NONE, REPR_PATH_LEFT, REPR_PATH_RIGHT, REPR_PATH_SPLICED = range(4)
 
 
 class GraphParams(C.Structure):
@@ -118,6 +123,7 @@ SYMBOLS = [
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_join_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
+    ("rb_graph_represented", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

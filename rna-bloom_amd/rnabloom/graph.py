@@ -719,6 +719,35 @@ class BloomFilterDeBruijnGraph:
         seq, off = _pack(seqs)
         return self.screenFragmentsFlat(seq, off, bf, what, lookahead, maxDepth, maxVisits)
 
+    REPR_DTYPE = np.dtype([("flags", "<i4"), ("why", "<i4"), ("left", "<i4"), ("right", "<i4"), ("expected_len", "<i4"), ("found_len", "<i4"),
+                           ("distance", "<i4"), ("tests_passed", "<i4"), ("distance_sum", "<i4"), ("tips_skipped", "<i4"), ("path_form", "<i4"),
+                           ("reserved", "<i4")])
+    REPR_REPRESENTED = N.REPR_REPRESENTED
+    REPR_WHYS = ("true", "no_run", "left_length", "left_identity", "wide_gap", "no_path", "path_length", "path_identity", "right_length",
+                 "right_identity")
+    REPR_PATH_FORMS = ("none", "left", "right", "spliced")
+
+    def representedFlat(self, seq, offsets, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits=0):
+        """rb_graph_represented on flat host text: GraphUtils.represented(kmers, graph, bf, lookahead, maxIndelSize, maxEdgeClipLength,
+        percentIdentity) (R/util/GraphUtils.java:711-824) of sequence i = seq[offsets[i]:offsets[i + 1]] (uint8).  bf — a
+        rnabloom.bloom.BloomFilter, as in screenFragments — is the worker's screeningBf and is required; maxVisits is the budget of one
+        static hasDepth* search (0: the library's default).  Returns one REPR_DTYPE record per sequence: the answer in flags' bit 0
+        (REPR_REPRESENTED), bits 3..5 (SCREEN_NOT_JUDGED) for a sequence that stays with the caller, `why` the line that returned
+        (REPR_WHYS) and how the answer came about."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        recs = np.zeros(n, self.REPR_DTYPE)
+        check(lib.rb_graph_represented(self.h, bf._g.h if bf is not None else None, _ptr(seq), _ptr(off), n, lookahead, maxIndelSize,
+                                       maxEdgeClipLength, percentIdentity, maxVisits, _ptr(recs)))
+        return recs
+
+    def represented(self, seqs, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits=0):
+        """representedFlat over strings (or bytes): the REPR_DTYPE record array, one record per sequence"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        return self.representedFlat(seq, off, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits)
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and
