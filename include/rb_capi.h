@@ -636,6 +636,58 @@ typedef struct rb_repr_rec {            /* 48 bytes */
 } rb_repr_rec;
 int rb_graph_represented(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
                          int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out);
+/* GraphUtils.trimReverseComplementArtifact for n host sequences, the last per-sequence step of the transcript worker (R/RNABloom.java:1914), of
+ * the fragment worker (:2206) and of the long-read corrector (:3806).  Each of the three overloads is pure and returns a contiguous sub-list of
+ * the k-mers it was given, so the answer is a range [begin, end) of the sequence's k-mers (the trimmed text is the letters begin .. end + k - 2,
+ * or nothing where the range is empty).  A wavefront per sequence on the device; read-only; the handle's own `stranded` flag is the
+ * reference's argument.  Sequences and letters are rb_graph_screen_fragments'.
+ *   mode RB_TRIM_HASHES: trimReverseComplementArtifact(kmers, graph, stranded) (R/util/GraphUtils.java:8588-8661).  The HashSet of the
+ *   reverse-strand hashes of k-mers 0 .. n/2 - 1; numMatch = the k-mers n/2 .. n - 1 whose forward hash is in it — hashes alone, bases are
+ *   never compared; numMatch >= k returns subList(start, n), after the adjustment loop (:8616-8621, down to index 0 without a break) where
+ *   start == n/2; else null.  The stranded branch reads getHash() / getReverseComplementHash() (the k-mer's own NTP64RC) and the canonical
+ *   one getFHash() / getRHash(): both are the forward and the reverse-strand hash of the k-mer.
+ *   mode RB_TRIM_EDGE: trimReverseComplementArtifact(seqKmers, maxEdgeClip, maxIndelSize, minPercentIdentity, graph) (:7918-8057), two passes,
+ *   the second on the list the first one left.  A pass finds, for a seed among the first (last) max_edge_clip k-mers (the right-to-left pass
+ *   takes max_edge_clip + 1 seeds, :7994), the nearest k-mer whose getHash() equals the seed's getReverseComplementHash() and whose bases are
+ *   the seed's reverse complement; the left-to-right scan stops only at a seed index > 0, so a match of seed 0 is kept and trims nothing
+ *   unless a later seed overwrites it.  cutIndex then runs inward in strides of k and in single steps, is held at the midpoint, and one of
+ *   three lines cuts, two of them chosen by getMinimumKmerCoverage of two windows of k k-mers.
+ *   mode RB_TRIM_LONG: the seven-argument overload (:7762-7916): the same anchor scan, the nested extension of anchor and partner up to the
+ *   midpoint, the test that both are 2 k k-mers long, and the unstranded return or one of four stranded ones chosen by
+ *   getMedianKmerCoverage (float32; an even count is one sum and one quotient) of anchor, middle and partner and by max_cov_gradient.
+ *   maxIndelSize and minPercentIdentity are read by neither body and are no parameters here.  max_edge_clip is read by EDGE and LONG,
+ *   max_cov_gradient by LONG in a stranded graph; the other modes ignore their values (which are checked all the same).
+ *   out[i]: rb_trim_rec, 16 ints.  flags: RB_TRIM_FOUND — a line other than the final fall-through produced the range (HASHES: the result
+ *   is not null; EDGE: a pass cut; LONG: a return inside a pass); RB_TRIM_TRIMMED — begin > 0 or end < the number of k-mers; or
+ *   RB_SCREEN_NO_KMER / RB_SCREEN_BAD_LETTER for a sequence that is not judged (begin 0, end = its k-mers, both passes blank).
+ *   RB_TRIM_NOT_JUDGED is reserved for an input on which the reference throws; the three bodies throw on no list of one or more k-mers,
+ *   so no record carries it.  begin, end: the range kept, in the input's numbering; it may be empty (LONG's unstranded return).  mode: the
+ *   call's.  pass[p]: why and four ints, blank (all -1) for pass[1] of HASHES and of a LONG call whose first pass returned.
+ *     HASHES pass[0]: why 0 null (:8660), 1 :8612, 2 :8622; i0 start (-1: none) and i1 numMatch as they stand at :8610; i2 the start
+ *     returned or -1; i3 -1.
+ *     EDGE pass[p]: why 0 the :7945 / :8012 test is false, 1 2 3 the lines :7978 :7981 :7985 (pass 0) and :8045 :8048 :8052 (pass 1);
+ *     i0, i1 leftIndex and rightIndex as the scan left them; i2 cutIndex after the min / max, i3 cutLength, each -1 where it is not
+ *     computed.  Pass 1's indices are in the numbering of the list pass 0 left.
+ *     LONG pass[p]: why 0 no anchor, 1 the match-length test failed, 2 the unstranded return, 3 .. 6 the four stranded returns in source
+ *     order; i0 .. i3 anchorStart, anchorEnd, partnerStart, partnerEnd as they stand at the :7810 / :7883 test, before the ++ (why 0: as the
+ *     scan left them).
+ * Pieces as rb_graph_kmers (RB_QUERY_PIECE; results do not depend on the cuts).  Device scratch: 20 bytes per k-mer of a piece (two hashes
+ * and a count), 8 per sequence for the k-mer offsets and 64 per sequence for the records; where the call's longest sequence has more than 512
+ * k-mers the wavefronts' hash tables leave LDS: 8 bytes x the next power of two >= twice that sequence's k-mers for each wavefront of the
+ * launch (at most 2048 wavefronts and 512 MB together, never fewer than 4 wavefronts).  Profile entry "trim_artifacts".
+ * Refused (RB_ERR_INVALID, nothing launched): a null or shard handle; a destroyed dbgbf or counting filter; an unknown mode; max_edge_clip
+ * outside [0, 2^20]; a max_cov_gradient that is not finite; a sequence of more than 2^24 k-mers; n < 0; with n > 0: a null offsets / out,
+ * a null seq where there is text, decreasing offsets.  n == 0 succeeds and touches nothing. */
+enum { RB_TRIM_HASHES = 0, RB_TRIM_EDGE = 1, RB_TRIM_LONG = 2 };                 /* mode */
+enum { RB_TRIM_FOUND = 1, RB_TRIM_TRIMMED = 2, RB_TRIM_NOT_JUDGED = 32 };        /* rb_trim_rec.flags, beside RB_SCREEN_BAD_LETTER (8) and RB_SCREEN_NO_KMER (16) */
+typedef struct rb_trim_pass { int32_t why, i0, i1, i2, i3; } rb_trim_pass;
+typedef struct rb_trim_rec {            /* 64 bytes */
+    int32_t flags, begin, end, mode;    /* the k-mers kept: [begin, end) of the INPUT list */
+    rb_trim_pass pass[2];
+    int32_t reserved[2];                /* 0 */
+} rb_trim_rec;
+int rb_graph_trim_rc_artifacts(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int mode, int max_edge_clip,
+                               float max_cov_gradient, rb_trim_rec *out);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

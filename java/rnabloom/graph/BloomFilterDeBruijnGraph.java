@@ -641,6 +641,30 @@ public class BloomFilterDeBruijnGraph {
         NativeGraph.represented(handle, screeningBf.getNativeHandle(), text, off, n, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, 0L, records);
     }
 
+    public static final int TRIM_HASHES = 0, TRIM_EDGE = 1, TRIM_LONG = 2;
+    public static final int TRIM_FOUND = 1, TRIM_TRIMMED = 2, TRIM_NOT_JUDGED = 8 | 16 | 32;
+
+    /**
+     * GraphUtils.trimReverseComplementArtifact for a batch of sequences in ONE native call: mode TRIM_HASHES is
+     * trimReverseComplementArtifact(kmers, graph, stranded) (src/rnabloom/util/GraphUtils.java:8588-8661), TRIM_EDGE
+     * trimReverseComplementArtifact(seqKmers, maxEdgeClip, maxIndelSize, minPercentIdentity, graph) (:7918-8057) and TRIM_LONG the
+     * seven-argument overload (:7762-7916); maxIndelSize and minPercentIdentity are read by neither body.  records (16 * seqs.length ints)
+     * receives the records of NativeGraph.trimArtifacts: sequence i keeps the k-mers subList(records[16 i + 1], records[16 i + 2]) of its
+     * getKmers list, i.e. the letters records[16 i + 1] .. records[16 i + 2] + k - 2; records[16 i] holds TRIM_FOUND where a line of the
+     * reference cut (TRIM_HASHES: where the result is not null), TRIM_TRIMMED where something went, and a bit of TRIM_NOT_JUDGED where the
+     * sequence stays with the reference's own code (a letter outside ACGTU, no k-mer).
+     */
+    public void trimReverseComplementArtifacts(String[] seqs, int mode, int maxEdgeClip, float maxCovGradient, int[] records) {
+        final int n = seqs.length;
+        if (records == null || records.length < 16L * n) throw new IllegalArgumentException("trimReverseComplementArtifacts: records must hold " + 16L * n + " ints");
+        final long[] off = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("trimReverseComplementArtifacts: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        NativeGraph.trimArtifacts(handle, text, off, n, mode, maxEdgeClip, maxCovGradient, records);
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

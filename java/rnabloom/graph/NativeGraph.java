@@ -172,6 +172,13 @@ public final class NativeGraph {
      *  hasDepth* excused, the form of the last path (0 none, 1 from the left, 2 from the right, 3 spliced), 0.  Read-only on both handles. */
     public static native void represented(long h, long gateHandle, ByteBuffer seq, long[] offsets, int n, int lookahead, int maxIndelSize,
                                           int maxEdgeClipLength, float percentIdentity, long maxVisits, int[] recs);
+    /** GraphUtils.trimReverseComplementArtifact (rb_graph_trim_rc_artifacts) of n sequences: mode 0 the (kmers, graph, stranded) overload
+     *  (R/util/GraphUtils.java:8588-8661), 1 the one with maxEdgeClip (:7918-8057), 2 the one with maxEdgeClip and maxCovGradient (:7762-7916);
+     *  the graph's own strandedness is the reference's `stranded`.  recs holds 16 ints per sequence — flags (1: a line of the reference cut,
+     *  for mode 0 the result is not null; 2: something was trimmed; not judged: 8 a letter outside ACGTU, 16 no k-mer, 32 reserved), begin and
+     *  end of the k-mers kept (the list's subList(begin, end)), the mode, then for each of the two passes the line that decided and four
+     *  indices (include/rb_capi.h), 0, 0.  Read-only. */
+    public static native void trimArtifacts(long h, ByteBuffer seq, long[] offsets, int n, int mode, int maxEdgeClip, float maxCovGradient, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

@@ -505,6 +505,20 @@ void FN(represented)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlon
     lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc12, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_trim_rc_artifacts: a record (rb_trim_rec, 64 bytes) is 16 ints to Java: flags, begin, end, mode, then why, i0, i1, i2, i3 of pass 0 and of pass 1, 0, 0 */
+void FN(trimArtifacts)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jint mode, jint maxEdgeClip, jfloat maxCovGradient,
+                       jintArray recs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!offsets || !recs || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, recs) / 16 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "trimArtifacts: an array is too short for n sequences");
+        return;
+    }
+    jlong *po = la(e, offsets);
+    jint *rc16 = ia(e, recs);
+    int rc = rb_graph_trim_rc_artifacts(G(h), (const char *)direct(e, seq), (const int64_t *)po, n, mode, maxEdgeClip, maxCovGradient, (rb_trim_rec *)rc16);
+    lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc16, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -153,5 +153,13 @@ template <class KTH> __device__ __forceinline__ float median_of_kth(KTH kth, int
 template <class CODE> __device__ __forceinline__ float median_code(const CODE &code, int n, uint32_t lane) {
     return median_of_kth([&](int rank) { return kth_code(code, n, rank, lane); }, n);
 }
+// the smallest code of elements [start, end) (getMinimumKmerCoverage(kmers, start, end), R/util/GraphUtils.java:133-145, as a code): code(p) is
+// asked for start <= p < end; 255 for an empty range.  All 64 lanes call; all get the result.
+template <class CODE> __device__ __forceinline__ uint32_t min_code(const CODE &code, int start, int end, uint32_t lane) {
+    uint32_t mn = 255u;
+    for (int p = start + (int)lane; p < end; p += 64) mn = min(mn, code(p));
+    for (int s = 32; s > 0; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s, 64));
+    return mn;
+}
 
 }  // namespace rb

@@ -417,10 +417,7 @@ __device__ int sc_has_depth(const ScArgs &a, const ScSeq &sq, const ScRows &rw, 
 
 // getMinimumKmerCoverage(kmers, start, end) (:133-145) as a count code; getMedianKmerCoverage(kmers, start, end) (:208-217)
 __device__ uint32_t sc_min_code(const ScSeq &sq, int start, int end, uint32_t lane) {
-    uint32_t mn = 255u;
-    for (int p = start + (int)lane; p < end; p += 64) mn = min(mn, sq.code(p));
-    for (int s = 32; s > 0; s >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, s, 64));
-    return mn;
+    return min_code([&](int p) { return sq.code(p); }, start, end, lane);
 }
 __device__ float sc_median(const ScSeq &sq, int start, int end, uint32_t lane) {
     return median_code([&](int p) { return sq.code(start + p); }, end - start, lane);

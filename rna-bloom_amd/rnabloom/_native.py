@@ -30,6 +30,9 @@ REPR_REPRESENTED = 1
 REPR_WHY_TRUE, REPR_WHY_NO_RUN, REPR_WHY_LEFT_LENGTH, REPR_WHY_LEFT_IDENTITY, REPR_WHY_WIDE_GAP, REPR_WHY_NO_PATH, REPR_WHY_PATH_LENGTH, \
     REPR_WHY_PATH_IDENTITY, REPR_WHY_RIGHT_LENGTH, REPR_WHY_RIGHT_IDENTITY = range(10)
 REPR_PATH_NONE, REPR_PATH_LEFT, REPR_PATH_RIGHT, REPR_PATH_SPLICED = range(4)
+# rb_graph_trim_rc_artifacts: mode; rb_trim_rec.flags (a sequence that is not judged carries SCREEN_BAD_LETTER / SCREEN_NO_KMER, or TRIM_NOT_JUDGED)
+TRIM_HASHES, TRIM_EDGE, TRIM_LONG = range(3)
+TRIM_FOUND, TRIM_TRIMMED, TRIM_NOT_JUDGED = 1, 2, 32
 
 
 class GraphParams(C.Structure):
@@ -124,6 +127,7 @@ SYMBOLS = [
     ("rb_graph_join_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
     ("rb_graph_represented", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp]),
+    ("rb_graph_trim_rc_artifacts", _i32, [_vp, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -748,6 +748,35 @@ class BloomFilterDeBruijnGraph:
         seq, off = _pack(seqs)
         return self.representedFlat(seq, off, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits)
 
+    TRIM_DTYPE = np.dtype([("flags", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("mode", "<i4"),
+                           ("pass", [("why", "<i4"), ("i0", "<i4"), ("i1", "<i4"), ("i2", "<i4"), ("i3", "<i4")], (2,)), ("reserved", "<i4", (2,))])
+    TRIM_HASHES, TRIM_EDGE, TRIM_LONG = N.TRIM_HASHES, N.TRIM_EDGE, N.TRIM_LONG
+    TRIM_FOUND, TRIM_TRIMMED = N.TRIM_FOUND, N.TRIM_TRIMMED
+    TRIM_NOT_JUDGED = N.SCREEN_BAD_LETTER | N.SCREEN_NO_KMER | N.TRIM_NOT_JUDGED
+    TRIM_WHYS = (("null", "start_beyond_half", "start_adjusted"),
+                 ("no_artifact", "far_end_cut", "near_end_cut", "inner_cut"),
+                 ("no_anchor", "short_match", "unstranded", "stranded_1", "stranded_2", "stranded_3", "stranded_4"))
+
+    def trimArtifactsFlat(self, seq, offsets, mode, maxEdgeClip=0, maxCovGradient=0.0):
+        """rb_graph_trim_rc_artifacts on flat host text: GraphUtils.trimReverseComplementArtifact of sequence i = seq[offsets[i]:offsets[i + 1]]
+        (uint8) — mode TRIM_HASHES the (kmers, graph, stranded) overload (R/util/GraphUtils.java:8588-8661), TRIM_EDGE the one with
+        maxEdgeClip (:7918-8057), TRIM_LONG the one with maxEdgeClip and maxCovGradient (:7762-7916); the graph's own strandedness is the
+        reference's `stranded`.  Returns one TRIM_DTYPE record per sequence: the k-mers kept are [begin, end) of the sequence's getKmers
+        list, flags say whether a line of the reference cut (TRIM_FOUND; for TRIM_HASHES: the result is not null) and whether anything
+        went (TRIM_TRIMMED); bits of TRIM_NOT_JUDGED mark a sequence that stays with the caller; pass[p] says which line decided."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        recs = np.zeros(n, self.TRIM_DTYPE)
+        check(lib.rb_graph_trim_rc_artifacts(self.h, _ptr(seq), _ptr(off), n, mode, maxEdgeClip, maxCovGradient, _ptr(recs)))
+        return recs
+
+    def trimArtifacts(self, seqs, mode, maxEdgeClip=0, maxCovGradient=0.0):
+        """trimArtifactsFlat over strings (or bytes): the TRIM_DTYPE record array, one record per sequence"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        return self.trimArtifactsFlat(seq, off, mode, maxEdgeClip, maxCovGradient)
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and

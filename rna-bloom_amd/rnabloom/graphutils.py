@@ -288,3 +288,25 @@ def _has_duplicated_kmer_pair(kmers, cursor, d, mate_index):
     if mate == kmers[idx[-1] - d]:
         return True
     return any(i - d >= 0 and mate == kmers[i - d] for i in idx[:-1])
+
+
+def trimReverseComplementArtifact(graph, seqs, mode, maxEdgeClip=0, maxCovGradient=0.0, keepNotJudged=False):
+    """GraphUtils.trimReverseComplementArtifact for many sequences in one rb_graph_trim_rc_artifacts call: mode graph.TRIM_HASHES is the
+    (kmers, graph, stranded) overload (R/util/GraphUtils.java:8588-8661), TRIM_EDGE the one the fragment assembler calls with maxTipLength
+    (:7918-8057), TRIM_LONG the long-read corrector's (:7762-7916).  Returns, per sequence, the string the returned k-mers spell —
+    seq[begin:end + k - 1], "" for an empty list — or None where TRIM_HASHES returns null.  A sequence that is not judged (a letter outside
+    ACGTU, no k-mer) raises ValueError, or is returned as it is with keepNotJudged."""
+    k = graph.k
+    recs = graph.trimArtifacts(seqs, mode, maxEdgeClip, maxCovGradient)
+    out = []
+    for i, (s, rc) in enumerate(zip(seqs, recs)):
+        flags, begin, end = int(rc["flags"]), int(rc["begin"]), int(rc["end"])
+        if flags & graph.TRIM_NOT_JUDGED:
+            if not keepNotJudged:
+                raise ValueError("trimReverseComplementArtifact: sequence %d is not judged (flags %d)" % (i, flags))
+            out.append(s)
+        elif mode == graph.TRIM_HASHES and not flags & graph.TRIM_FOUND:
+            out.append(None)
+        else:
+            out.append(s[begin:end + k - 1] if end > begin else s[:0])
+    return out
