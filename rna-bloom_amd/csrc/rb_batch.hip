@@ -764,6 +764,127 @@ k_hash_windows_resume(const uint64_t *__restrict__ codes, const uint32_t *__rest
     }
 }
 
+// ---- table-driven emit (k <= 32): one lane per kept window, hashed from its own k bases ----
+// The walkers above reach a kept window by rolling through every window before it, and after the prefilter five windows of six are
+// dropped ones.  A kept window is always a usable one (keep bits exist only where all k bases are valid), so its hash needs no rolling
+// and no null bases:   f = XOR_i rotl(seed[c_i], k-1-i),   r = XOR_i rotl(seed[3-c_i], i)   (NTHash.java:332-337, 367-373).
+// Four bases at a time: entry b of the table holds, for the four bases of byte b (base t at bits 2t),
+//   .f = XOR_t rotl(seed[c_t], 3-t)      .r = XOR_t rotl(seed[3-c_t], t)
+// and with n = ceil(k/4) bytes b_0 .. b_(n-1) of the window
+//   f = rotl(F, k-4n),  F = XOR_q rotl(T[b_q].f, 4(n-1-q))      — F <- rotl(F, 4) ^ T[b_q].f, q ascending
+//   r = rotl(R, 4(n-1)), R = XOR_q rotr(T[b_q].r, 4(n-1-q))     — R <- rotr(R, 4) ^ T[b_q].r
+// so a chunk costs two rotations by a constant and the final rotations are by amounts uniform in k (scalar registers).  The 4n-k bases
+// past the window's end in its last byte are masked to code 0; what code 0 adds there depends on k alone and is taken out again.
+struct alignas(16) Emit4 { uint64_t f, r; };
+struct Emit4Tab {
+    Emit4 e[256];
+    static constexpr uint64_t rot(uint64_t v, uint32_t s) { return s ? (v << s) | (v >> (64u - s)) : v; }
+    constexpr Emit4Tab() : e{} {
+        constexpr uint64_t sd[4] = {0x3c8bfbb395c60474ull, 0x3193c18562a02b4cull, 0x20323ed082572324ull, 0x295549f54be24456ull};   // seed_of
+        for (uint32_t b = 0; b < 256u; ++b)
+            for (uint32_t t = 0; t < 4u; ++t) {
+                const uint32_t c = (b >> (2u * t)) & 3u;
+                e[b].f ^= rot(sd[c], 3u - t);
+                e[b].r ^= rot(sd[3u - c], t);
+            }
+    }
+};
+__device__ const Emit4Tab d_emit4 = Emit4Tab();
+__device__ __forceinline__ uint64_t rotl4(uint64_t v) {
+    const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    return ((uint64_t)__builtin_amdgcn_alignbit(hi, lo, 28) << 32) | __builtin_amdgcn_alignbit(lo, hi, 28);
+}
+__device__ __forceinline__ uint64_t rotr4(uint64_t v) {
+    const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+    return ((uint64_t)__builtin_amdgcn_alignbit(lo, hi, 4) << 32) | __builtin_amdgcn_alignbit(hi, lo, 4);
+}
+// position of the rank-th set bit of m (rank < popcount(m))
+__device__ __forceinline__ uint32_t nth_set_bit(uint32_t m, uint32_t rank) {
+    uint32_t pos = 0;
+#pragma unroll
+    for (uint32_t h = 16u; h; h >>= 1) {
+        const uint32_t c = (uint32_t)__popc(m & ((1u << h) - 1u));
+        const bool up = rank >= c;
+        rank = up ? rank - c : rank; pos = up ? pos + h : pos; m = up ? m >> h : m;
+    }
+    return pos;
+}
+// Same interface and result as k_hash_windows_resume (no saved state): records (h0, occ), dense, in read order; the record of kept bit j
+// of word i goes to chunk_off[i] + rank of j in keepmask[i].  A workgroup stages RB_SPARSE_WORDS words (record offsets, keep masks,
+// codes and the occurrence id of each word's first base) in LDS; then every lane takes one record: its word by a search over the
+// staged offsets, its bit by rank, its 2k bits of codes funnel-shifted out of the word and its successor.  Records go out one lane per
+// consecutive record.  n_words: the batch's words (the word after the range's last is read only if it exists).
+constexpr int EMIT_TPB = 256;
+template <int MODE>
+__global__ void __launch_bounds__(EMIT_TPB)
+k_hash_windows_direct(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ word_read, const uint32_t *__restrict__ woff,
+                      int64_t w0, int64_t nw, int64_t n_words, int k, const uint32_t *__restrict__ chunk_off, uint32_t first_read,
+                      uint32_t pos_bits, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, const uint32_t *__restrict__ keepmask) {
+    constexpr uint32_t BW = RB_SPARSE_WORDS;
+    static_assert((BW & (BW - 1u)) == 0u, "the offset search halves a power of two");
+    __shared__ Emit4 s_t4[256];
+    __shared__ uint64_t s_code[BW + 1];
+    __shared__ uint32_t s_off[BW + 1], s_keep[BW], s_base[BW];
+    const uint32_t tid = threadIdx.x;
+    const int64_t blk0 = (int64_t)blockIdx.x * BW;
+    const uint32_t nwb = (uint32_t)((blk0 + BW < nw ? blk0 + BW : nw) - blk0);
+    const uint32_t O0 = chunk_off[blk0], n = chunk_off[blk0 + nwb] - O0;
+    if (n == 0u) return;
+    for (uint32_t i = tid; i < 256u; i += EMIT_TPB) s_t4[i] = d_emit4.e[i];
+    for (uint32_t i = tid; i <= BW; i += EMIT_TPB) {
+        uint32_t o = 0xFFFFFFFFu;                                  // past the block's words: never at or below a record's number
+        uint64_t c = 0;
+        if (i <= nwb) {
+            const int64_t w = w0 + blk0 + i;
+            o = chunk_off[blk0 + i] - O0;
+            if (w < n_words) c = codes[w];
+            if (i < nwb && chunk_off[blk0 + i + 1] - O0 != o) {    // the word keeps something
+                const uint32_t r = word_read[w];
+                s_keep[i] = keepmask[blk0 + i];
+                s_base[i] = ((r - first_read) << pos_bits) + ((uint32_t)w - woff[r]) * 32u;
+            }
+        }
+        s_off[i] = o; s_code[i] = c;
+    }
+    __syncthreads();
+    // uniform in k
+    const uint32_t uk = (uint32_t)k, nq = (uk + 3u) >> 2, pad = 4u * nq - uk;
+    const uint32_t mask_lo = uk >= 16u ? 0xFFFFFFFFu : (1u << (2u * uk)) - 1u;
+    const uint32_t mask_hi = uk >= 32u ? 0xFFFFFFFFu : uk <= 16u ? 0u : (1u << (2u * uk - 32u)) - 1u;
+    uint64_t fx = 0, rx = 0;                                       // what the masked bases (code 0) of the last byte add
+    for (uint32_t t = 4u - pad; t < 4u; ++t) { fx ^= rotl(seed_of(0u), 3u - t); rx ^= rotl(seed_of(3u), t); }
+    const uint32_t sf = (uk - 4u * nq) & 63u, sr = 4u * (nq - 1u);
+    for (uint32_t x = tid; x < n; x += EMIT_TPB) {
+        uint32_t pos = 0;                                          // the largest i with s_off[i] <= x: the word of record x
+#pragma unroll
+        for (uint32_t step = BW >> 1; step; step >>= 1) pos = (s_off[pos + step] <= x) ? pos + step : pos;
+        const uint32_t j = nth_set_bit(s_keep[pos], x - s_off[pos]);
+        const uint64_t c0 = s_code[pos], c1 = s_code[pos + 1u];
+        uint32_t a = (uint32_t)c0, b = (uint32_t)(c0 >> 32), c = (uint32_t)c1;
+        if (j & 16u) { a = b; b = c; c = (uint32_t)(c1 >> 32); }
+        const uint32_t sh = (2u * j) & 31u;
+        const uint32_t wlo = __builtin_amdgcn_alignbit(b, a, sh) & mask_lo, whi = __builtin_amdgcn_alignbit(c, b, sh) & mask_hi;
+        uint64_t f = 0, r = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 8u; ++q) {
+            if (q >= nq) break;
+            const Emit4 e = s_t4[((q < 4u ? wlo : whi) >> (8u * (q & 3u))) & 0xFFu];
+            if (MODE != 2) f = rotl4(f) ^ e.f;
+            if (MODE != 0) r = rotr4(r) ^ e.r;
+        }
+        if (MODE != 2) f = rotl_var(f ^ fx, sf);
+        if (MODE != 0) r = rotl_var(r ^ rx, sr);
+        keys[O0 + x] = (MODE == 0) ? f : (MODE == 2) ? r : canonical(f, r);
+        vals[O0 + x] = s_base[pos] + j;
+    }
+}
+// RB_EMIT_CHECK: records of two emit kernels side by side; res[0] = records that differ, res[1] = the first of them
+__global__ void k_emit_compare(const uint64_t *__restrict__ ka, const uint32_t *__restrict__ va, const uint64_t *__restrict__ kb,
+                               const uint32_t *__restrict__ vb, uint32_t n, uint32_t *__restrict__ res) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (ka[i] != kb[i] || va[i] != vb[i])) { atomicAdd(&res[0], 1u); atomicMin(&res[1], i); }
+}
+
 // ---- one read per lane (k <= 31, uniform batches) ----
 // k_filter_windows_fast / k_hash_windows_fast give every lane one 32-base word: 32 windows for 32 + k-1
 // walker steps, i.e. 1.94 steps per window at k = 25 — and the SQ counters show both kernels bound by
@@ -1424,10 +1545,51 @@ void launch_filter_windows(const rb_batch *b, int64_t w0, int64_t nw, int k, int
 // ... and at 32 <= k <= 63, when the call goes through the read-per-lane kernel with the minimizer-bucketed cache (add_range knows)
 bool filter_saves_state_wide(const rb_batch *b, int64_t nw, int k) { return filter_wide_mpf_ok(b, nw, k) && !(getenv("RB_EMIT_RESUME") && atoi(getenv("RB_EMIT_RESUME")) == 0); }
 bool filter_saves_state(const rb_batch *b, int64_t nw, int k) { return (read_lane_words(b, nw, k) != 0u || read_lanes_ragged(b, k)) && !(getenv("RB_EMIT_RESUME") && atoi(getenv("RB_EMIT_RESUME")) == 0); }
+// does the emit pass after the prefilter hash the kept windows directly (k_hash_windows_direct)?  Then nobody reads the prefilter's rolling
+// states and the callers do not have them saved.  RB_EMIT_DIRECT=0: the walkers, as before.
+bool emit_direct(int k) { return k <= 32 && !(getenv("RB_EMIT_DIRECT") && atoi(getenv("RB_EMIT_DIRECT")) == 0); }
+static void launch_hash_windows_walked(const rb_batch *b, int64_t w0, int64_t nw, int k, int mode, const uint32_t *chunk_off,
+                                       const uint32_t *keepmask, uint32_t first_read, uint32_t pos_bits, uint64_t *keys, uint32_t *vals,
+                                       hipStream_t s, const void *wstate);
 void launch_hash_windows_masked(const rb_batch *b, int64_t w0, int64_t nw, int k, int mode, const uint32_t *chunk_off,
                                 const uint32_t *keepmask, uint32_t first_read, uint32_t pos_bits, uint64_t *keys, uint32_t *vals,
                                 hipStream_t s, const void *wstate) {
     if (nw <= 0) return;
+    if (keepmask && emit_direct(k)) {
+        dim3 gd(blocks_for(nw, RB_SPARSE_WORDS)), td(EMIT_TPB);
+#define RB_LAUNCH_DI(M)                                                                                          \
+    hipLaunchKernelGGL(k_hash_windows_direct<M>, gd, td, 0, s, b->codes, b->word_read, b->woff, w0, nw, b->n_words, k, \
+                       chunk_off, first_read, pos_bits, keys, vals, keepmask)
+        if (mode == 0) RB_LAUNCH_DI(0); else if (mode == 2) RB_LAUNCH_DI(2); else RB_LAUNCH_DI(1);
+#undef RB_LAUNCH_DI
+        if (getenv("RB_EMIT_CHECK") && atoi(getenv("RB_EMIT_CHECK"))) {
+            // Verification (tests, and whoever touches the kernel): the walker this call would have used without the direct kernel (the resuming
+            // one where the prefilter saved its states, else the sparse one) emits the same words into scratch arrays and every key and every
+            // occurrence id is compared on the device; a difference fails the call.
+            uint32_t N = 0;
+            RB_HIP(hipMemcpyAsync(&N, chunk_off + nw, 4, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipStreamSynchronize(s));
+            DevBuf k2, v2, res;
+            k2.reserve((size_t)N * 8 + 8); v2.reserve((size_t)N * 4 + 4); res.reserve(8);
+            RB_HIP(hipMemsetAsync(k2.p, 0xEE, (size_t)N * 8 + 8, s)); RB_HIP(hipMemsetAsync(v2.p, 0xEE, (size_t)N * 4 + 4, s));
+            const uint32_t res0[2] = {0u, 0xFFFFFFFFu};
+            RB_HIP(hipMemcpyAsync(res.p, res0, 8, hipMemcpyHostToDevice, s));
+            launch_hash_windows_walked(b, w0, nw, k, mode, chunk_off, keepmask, first_read, pos_bits, k2.as<uint64_t>(), v2.as<uint32_t>(), s, wstate);
+            if (N) hipLaunchKernelGGL(k_emit_compare, dim3(blocks_for(N)), dim3(TPB), 0, s, keys, vals, k2.as<uint64_t>(), v2.as<uint32_t>(), N, res.as<uint32_t>());
+            uint32_t got[2] = {0, 0};
+            RB_HIP(hipMemcpyAsync(got, res.p, 8, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipStreamSynchronize(s));
+            if (atoi(getenv("RB_EMIT_CHECK")) > 1) fprintf(stderr, "[rb] emit check: %u records, %u differ\n", N, got[0]);
+            RB_REQUIRE(got[0] == 0, "emit check: %u of %u records differ between the direct kernel and the walker (first: record %u)", got[0], N, got[1]);
+        }
+        return;
+    }
+    launch_hash_windows_walked(b, w0, nw, k, mode, chunk_off, keepmask, first_read, pos_bits, keys, vals, s, wstate);
+}
+// the emit kernels that walk: resuming from saved states, else over the list of words that keep something, else every word
+static void launch_hash_windows_walked(const rb_batch *b, int64_t w0, int64_t nw, int k, int mode, const uint32_t *chunk_off,
+                                const uint32_t *keepmask, uint32_t first_read, uint32_t pos_bits, uint64_t *keys, uint32_t *vals,
+                                hipStream_t s, const void *wstate) {
     const bool sparse = !(getenv("RB_SPARSE_EMIT") && atoi(getenv("RB_SPARSE_EMIT")) == 0);
     if (keepmask && wstate) {
         dim3 gs(blocks_for(nw, RB_SPARSE_WORDS)), ts(64);

@@ -24,6 +24,7 @@ void launch_filter_windows(const rb_batch *b, int64_t w0, int64_t nw, int k, int
 bool filter_wide_mpf_ok(const rb_batch *b, int64_t nw, int k);   // 32 <= k <= 63: may the minimizer-bucketed cache be used for this batch?
 bool filter_saves_state(const rb_batch *b, int64_t nw, int k);
 bool filter_saves_state_wide(const rb_batch *b, int64_t nw, int k);
+bool emit_direct(int k);      // launch_hash_windows_masked hashes the kept windows directly and reads no saved state: pass wstate = nullptr to both
 void launch_hash_windows_masked(const rb_batch *b, int64_t w0, int64_t nw, int k, int mode, const uint32_t *chunk_off,
                                 const uint32_t *keepmask, uint32_t first_read, uint32_t pos_bits, uint64_t *keys, uint32_t *vals,
                                 hipStream_t s, const void *wstate = nullptr);
