@@ -688,6 +688,95 @@ typedef struct rb_trim_rec {            /* 64 bytes */
 } rb_trim_rec;
 int rb_graph_trim_rc_artifacts(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int mode, int max_edge_clip,
                                float max_cov_gradient, rb_trim_rec *out);
+/* Windowed correction of long reads — GraphUtils.correctLongSequenceWindowed (R/util/GraphUtils.java:3087-3185), the second step of
+ * LongReadCorrectionWorker.run (R/RNABloom.java:3788-3840), with what it calls: getCoverageStats (:1799-1848), correctInternalErrors
+ * (:3402-3602), the six-argument getMaxCoveragePath (:1591-1675), getMedianKmerCoverage (:208-247) and trimLowCoverageEdgeKmers (:3187-3241).
+ * On the device, a wavefront per window and pass; the call is read-only on the graph.
+ *   Input: sequence i is seq[offsets[i], offsets[i+1]); its k-mer list is getKmers(String)'s, as rb_graph_kmers gives it (nk = max(0, len - k
+ *   + 1); count 0 for a window with a letter outside ACGTU).  Every list the reference builds is a chain of k-mers that overlap by k - 1
+ *   letters (below), so a list is the text it spells and the counts of a pass are getKmers' of that text.
+ *   Solid-k-mer screen (:3099-3110): with min_num_solid > 0 a sequence with fewer than min_num_solid k-mers of count >= min_kmer_cov gives null
+ *   (status RB_LONG_NULL, the text comes back as it went in); min_num_solid <= 0 skips the screen.
+ *   Passes (:3118-3171): up to max_itr.  shift = window_size / 2; toShift starts false and flips after every pass that corrected something.
+ *   Windows [i, end) of k-mers: end = min(i + window_size, nk), for i == 0 of a pass with toShift min(i + shift + window_size, nk); then
+ *   end + shift >= nk makes end = nk.  A window of fewer than lookahead k-mers is copied.  The first pass that corrects nothing ends the loop.
+ *   Threshold of a window (getCoverageStats with calcDropOff, :1799-1848): the sorted counts c; median = c[len/2], for an even len (c[len/2-1] +
+ *   c[len/2]) / 2f; dropoff: last = c[len - lookahead], then for j = len - lookahead - 1 down to 0: c[j] < last * max_cov_gradient (one float32
+ *   product) -> dropoff = last, stop; else last = c[j].  T = median, or max(dropoff, min_kmer_cov) where dropoff > 0.
+ *   correctInternalErrors(window, T) (:3402-3602): a k-mer is bad if count < T.  kmers2 is the output list.  At a good k-mer that ends a run of
+ *   `run` bad ones, in this order:
+ *     kmers2 is empty (the run starts the window): the run is copied.
+ *     run == k - 1, an SNV bubble (:3432-3467): for every Kmer.getLeftVariants(k, numHash, graph, min_kmer_cov) `var` of the LAST bad k-mer
+ *     (the alternatives SeqUtils.getAltNucleotides gives for its first letter, in the order A C G T, whose count >= min_kmer_cov) the counts of
+ *     getKmers(first bad k-mer[0, k-1) + var): 2k - 1 letters, k windows.  A variant wins if its minimum >= min_kmer_cov and its median > best;
+ *     best starts at Float.MIN_VALUE; the winner needs best >= min_kmer_cov.  Its k k-mers stand for the k - 1 bad ones: the text grows by one
+ *     letter (reproduced, not fixed).  Else the run is copied.
+ *     run < k - 1 - max_indel_size (:3468-3471): the run is not closed: the good k-mer counts as one more bad k-mer of it and the scan goes on.
+ *     Else a path (:3472-3571).  maxLengthDifference D = max_indel_size if percent_identity < 1.0f, else 0.  Left anchor: kmers2's last entry,
+ *     then entries last - 2 down to max(0, last - lookahead) (last - 1 is skipped, as in the source), a strictly greater count taking over.
+ *     Right anchor: the good k-mer i, then window k-mers i + 1 .. min(i + lookahead, len - 1), a strictly greater count taking over.
+ *     path = getMaxCoveragePath(graph, L, R, run + D, lookahead, min_kmer_cov) (:1591-1675: the walk to the right of at most run + D maximum-
+ *     coverage successors — the first strictly largest count >= min_kmer_cov among A C G T — that returns when it reaches R and stops at a k-mer
+ *     it has added; then the walk back from R, which returns when it reaches L, gives null at a k-mer it has added and, at a k-mer the first walk
+ *     added, null if SeqUtils.isLowComplexityShort (:499-543) of it, else the first walk up to that k-mer and its own k-mers; null otherwise).
+ *     null or empty: the run is copied.  leftAdjust = kmers2.size() - 1 - L's index, rightAdjust = R's index - i, oriPathLen = run + leftAdjust +
+ *     rightAdjust.  A run with a k-mer of count 0: accepted if |oriPathLen - |path|| <= D.  Any other run: altCov = median of the path's counts,
+ *     oriCov = median of the run's; accepted if 2 * oriCov <= altCov and the same length test and ((oriCov < min_kmer_cov and altCov >= 10 *
+ *     oriCov) or getPercentIdentity(assemble(path), assemble(window k-mers [i - run - leftAdjust, i + rightAdjust))) >= percent_identity) — the
+ *     indices are the WINDOW's although leftAdjust was counted in kmers2 (reproduced); where i - run - leftAdjust < 0 the reference throws and
+ *     the run is copied here.  getPercentIdentity / getDistance as rb_graph_correct_errors states them (the stale column included).  Accepted:
+ *     kmers2 is cut back to L, the path is appended, the scan continues at R.  Else the run is copied.
+ *   A run still open at the window's end is copied unless it is the whole window.  A window in which nothing was accepted returns null: its
+ *   original k-mers are used.  Medians are float32 ((a + b) / 2f), all comparisons float32.
+ *   Chains: a copied run, the k k-mers of getKmers(2k - 1 letters) between the good k-mers before and behind a bubble, and a path from L to R
+ *   each overlap their neighbours by k - 1 letters, so kmers2 spells a text and the next pass's list is getKmers of it.
+ *   trim_low_cov_edges != 0 (:3173-3179): if the median count of the final list >= 2 * min_kmer_cov, trimLowCoverageEdgeKmers(list, graph,
+ *   min_kmer_cov) (:3187-3241): headIndex = the first i whose k-mers i - 1 and i both have count >= min_kmer_cov (0: none); tailIndex = i + 2 for
+ *   the last i > headIndex whose k-mers i and i + 1 (i + 1 < nk) both have (nk: none).  headIndex > 0 or tailIndex < nk: the list becomes
+ *   [headIndex, tailIndex) if tailIndex - headIndex > 1, else empty (RB_LONG_TRIMMED_TO_NOTHING).  The reference's caller sets the flag per
+ *   read (minKmerCov > 1 && !hasPolyA): it is per call here, a split by flag is the caller's.
+ *   Letters outside ACGTU follow the existing primitives, exactly as the rb_graph_correct_errors comment states: such windows count 0; the
+ *   anchors of a path have a count above 0 and so no such letter; letters taken from a path come out as upper-case A C G T, copied letters as
+ *   they went in.
+ *   Output: out_offsets (host, n + 1) is an INPUT, the caller's capacity layout: the final text of sequence i is written to out_seq +
+ *   out_offsets[i] if its length <= out_offsets[i+1] - out_offsets[i]; else nothing is written for it and recs[i].flags has RB_LONG_OVERFLOW.
+ *   recs[i].out_len is the length needed either way; the computation is deterministic, so a second call with room gives the text.  There is no
+ *   closed capacity formula (growth compounds over passes; in practice a few letters).
+ *   recs[i], 16 ints: status (RB_LONG_NULL the screen failed; RB_LONG_UNCHANGED; RB_LONG_CHANGED a pass corrected or the edge trim cut;
+ *   RB_LONG_NO_KMER nk == 0, nothing done — the reference's caller never passes it); passes that corrected; out_len; trim_begin, trim_end: the
+ *   k-mers [headIndex, tailIndex) of the final list where the edge trim cut, else -1, -1; then, summed over all passes and windows: snv_replaced,
+ *   snv_kept, path_none (null or empty), zero_accepted, zero_kept (runs with a k-mer of count 0), accepted_10x (oriCov < min_kmer_cov and
+ *   altCov >= 10 * oriCov held), accepted_identity, cov_kept, short_skipped (good k-mers swallowed by a short run), anchor_moved (path events
+ *   whose left or right anchor left its default); flags.
+ * Window slots: a window of len k-mers may return at most len + (len / 2) * max(max_indel_size, 1) k-mers (accepted events are at least two
+ * input k-mers apart and add at most that many each); a window has at most 2 window_size k-mers (the first window of a shifted pass merged with
+ * the rest), and a slot may hold 2^30 k-mers, so window_size * (2 + max(max_indel_size, 1)) <= 2^30 is required: RB_LONG_MAX_WINDOW is admitted
+ * with max_indel_size <= 1022, 4096 with any.  RB_ERR_STATE, in the middle of the call (earlier sequences' records may be written, none is
+ * complete): a slot is outgrown (an internal error), a sequence grows beyond 2^30 letters, or one pass over a piece has 2^31 windows or more.
+ * The call works in pieces (RB_QUERY_PIECE input k-mers, by default 4 M); results do not depend on the cuts.  Texts and counts stay on the
+ * device between passes; only the final texts and 5 ints a sequence come back.  Device scratch of a piece: 2 x (1 byte a letter + 1 byte a
+ * k-mer) of its live sequences, the windows' slots (above) and, for each of at most 2048 wavefronts, rows bounded by the longest window W of
+ * the pass, not by the read: 25 (W + max_indel_size) + 5 W + 2 k bytes or so.  It leases a query context (re-entrant on one handle).  Profile
+ * entry "correct_long": the interval from a piece's first to its last kernel, the host's work between the passes included.
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle / offsets / p / out_offsets / out_seq / recs (n > 0), seq where there is text; a
+ * shard handle; a destroyed dbgbf or counting filter; max_cov_gradient or percent_identity not finite; decreasing offsets (input or capacity);
+ * k < 2; window_size < 1 (the reference would loop forever) or > RB_LONG_MAX_WINDOW (2^20); lookahead < 1 or > RB_LONG_MAX_WINDOW; max_itr < 0;
+ * max_indel_size outside 0..4096; window_size * (2 + max(max_indel_size, 1)) > 2^30.  n == 0 succeeds and touches nothing; a null seq is taken
+ * where no sequence has a letter. */
+enum { RB_LONG_NULL = 0, RB_LONG_UNCHANGED = 1, RB_LONG_CHANGED = 2, RB_LONG_NO_KMER = 3 };     /* rb_long_rec.status */
+enum { RB_LONG_OVERFLOW = 1, RB_LONG_TRIMMED_TO_NOTHING = 2 };                                  /* rb_long_rec.flags */
+#define RB_LONG_MAX_WINDOW (1 << 20)
+typedef struct rb_long_params {
+    int32_t max_itr, lookahead, max_indel_size, min_kmer_cov, min_num_solid, trim_low_cov_edges, window_size;
+    float max_cov_gradient, percent_identity;
+} rb_long_params;
+typedef struct rb_long_rec {            /* 64 bytes */
+    int32_t status, passes, out_len, trim_begin, trim_end;
+    int32_t snv_replaced, snv_kept, path_none, zero_accepted, zero_kept, accepted_10x, accepted_identity, cov_kept, short_skipped, anchor_moved;
+    int32_t flags;
+} rb_long_rec;
+int rb_graph_correct_long(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const rb_long_params *p,
+                          const int64_t *out_offsets, char *out_seq, rb_long_rec *recs);
 /* Kmer.getSuccessors/getPredecessors R/graph/Kmer.java:210-255, CanonicalKmer.java:226-270:
  * for each (f, r, char_out) the 4 neighbours in order A,C,G,T: forward hash, reverse hash and
  * graph.getCount.  direction 0 = successors (char_out = first base), 1 = predecessors

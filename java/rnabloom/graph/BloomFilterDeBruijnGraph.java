@@ -665,6 +665,51 @@ public class BloomFilterDeBruijnGraph {
         NativeGraph.trimArtifacts(handle, text, off, n, mode, maxEdgeClip, maxCovGradient, records);
     }
 
+    public static final int LONG_NULL = 0, LONG_UNCHANGED = 1, LONG_CHANGED = 2, LONG_NO_KMER = 3;
+    public static final int LONG_OVERFLOW = 1, LONG_TRIMMED_TO_NOTHING = 2;
+
+    /**
+     * GraphUtils.correctLongSequenceWindowed (src/rnabloom/util/GraphUtils.java:3087-3185) for a batch of sequences in ONE native call (and a
+     * second one for the few whose text outgrew length + 16).  Returns the strings the reference's lists spell: null where it returns null
+     * (the solid-k-mer screen) or the sequence has no k-mer, "" for a list trimmed to nothing.  records (16 * seqs.length ints) receives the
+     * records of NativeGraph.correctLong.
+     */
+    public String[] correctLongSequencesWindowed(String[] seqs, int maxErrCorrItr, float maxCovGradient, int lookahead, int maxIndelSize,
+                                                 float percentIdentity, int minKmerCov, int minNumSolidKmers, boolean trimLowCovEdges,
+                                                 int windowSize, int[] records) {
+        final int n = seqs.length;
+        if (records == null || records.length < 16L * n) throw new IllegalArgumentException("correctLongSequencesWindowed: records must hold " + 16L * n + " ints");
+        final int[] params = {maxErrCorrItr, lookahead, maxIndelSize, minKmerCov, minNumSolidKmers, trimLowCovEdges ? 1 : 0, windowSize};
+        final String[] result = new String[n];
+        final int[] room = new int[n];
+        for (int i = 0; i < n; ++i) room[i] = seqs[i].length() + 16;
+        int[] todo = new int[n];
+        for (int i = 0; i < n; ++i) todo[i] = i;
+        for (int round = 0; round < 2 && todo.length > 0; ++round) {
+            final int m = todo.length;
+            final long[] off = new long[m + 1], oo = new long[m + 1];
+            for (int j = 0; j < m; ++j) { off[j + 1] = off[j] + seqs[todo[j]].length(); oo[j + 1] = oo[j] + room[todo[j]]; }
+            if (off[m] > Integer.MAX_VALUE || oo[m] > Integer.MAX_VALUE) throw new IllegalArgumentException("correctLongSequencesWindowed: more than 2 GB of text in one batch");
+            final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[m], 1)), out = ByteBuffer.allocateDirect(Math.max((int) oo[m], 1));
+            for (int j = 0; j < m; ++j) { final String s = seqs[todo[j]]; for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i)); }
+            final int[] recs = new int[16 * m];
+            NativeGraph.correctLong(handle, text, off, m, params, maxCovGradient, percentIdentity, oo, out, recs);
+            int again = 0;
+            for (int j = 0; j < m; ++j) {
+                System.arraycopy(recs, 16 * j, records, 16 * todo[j], 16);
+                if ((recs[16 * j + 15] & LONG_OVERFLOW) != 0) { room[todo[j]] = recs[16 * j + 2]; todo[again++] = todo[j]; continue; }
+                final int status = recs[16 * j];
+                if (status == LONG_NULL || status == LONG_NO_KMER) continue;
+                final byte[] b = new byte[recs[16 * j + 2]];
+                for (int i = 0; i < b.length; ++i) b[i] = out.get((int) oo[j] + i);
+                result[todo[j]] = new String(b, java.nio.charset.StandardCharsets.ISO_8859_1);
+            }
+            todo = java.util.Arrays.copyOf(todo, again);
+        }
+        if (todo.length > 0) throw new IllegalStateException("correctLongSequencesWindowed: " + todo.length + " sequences overflowed the room their own records asked for");
+        return result;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

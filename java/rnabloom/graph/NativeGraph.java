@@ -179,6 +179,14 @@ public final class NativeGraph {
      *  end of the k-mers kept (the list's subList(begin, end)), the mode, then for each of the two passes the line that decided and four
      *  indices (include/rb_capi.h), 0, 0.  Read-only. */
     public static native void trimArtifacts(long h, ByteBuffer seq, long[] offsets, int n, int mode, int maxEdgeClip, float maxCovGradient, int[] recs);
+    /** GraphUtils.correctLongSequenceWindowed (rb_graph_correct_long, R/util/GraphUtils.java:3087-3185) of n sequences.  params: maxErrCorrItr,
+     *  lookahead, maxIndelSize, minKmerCov, minNumSolidKmers, trimLowCovEdges (0 / 1), windowSize.  outOffsets (n + 1) is the caller's capacity
+     *  layout of `out`: the final text of sequence i is written at outOffsets[i] if it fits.  recs holds 16 ints per sequence — status (0 the
+     *  reference returns null, 1 unchanged, 2 changed, 3 no k-mer), the passes that corrected, the final length (the room needed, where it did
+     *  not fit), the k-mers the edge trim kept or -1, -1, ten event counters (include/rb_capi.h), flags (1: the text did not fit and was not
+     *  written, 2: trimmed to nothing).  Read-only. */
+    public static native void correctLong(long h, ByteBuffer seq, long[] offsets, int n, int[] params, float maxCovGradient, float percentIdentity,
+                                          long[] outOffsets, ByteBuffer out, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

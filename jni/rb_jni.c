@@ -519,6 +519,25 @@ void FN(trimArtifacts)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray off
     lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc16, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_correct_long: params holds the seven ints of rb_long_params in its order; a record (rb_long_rec, 64 bytes) is 16 ints to Java */
+void FN(correctLong)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jintArray params, jfloat maxCovGradient, jfloat percentIdentity,
+                     jlongArray outOffsets, jobject out, jintArray recs) {
+    (void)c;
+    if (n < 0 || !params || (*e)->GetArrayLength(e, params) < 7 ||
+        (n > 0 && (!offsets || !outOffsets || !recs || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, outOffsets) <= n ||
+                   (*e)->GetArrayLength(e, recs) / 16 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "correctLong: an array is too short for n sequences");
+        return;
+    }
+    jint *pp = ia(e, params);
+    rb_long_params p = {pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], pp[6], maxCovGradient, percentIdentity};
+    ir(e, params, pp, JNI_ABORT);
+    jlong *po = la(e, offsets), *poo = la(e, outOffsets);
+    jint *rc16 = ia(e, recs);
+    int rc = rb_graph_correct_long(G(h), (const char *)direct(e, seq), (const int64_t *)po, n, &p, (const int64_t *)poo, (char *)direct(e, out), (rb_long_rec *)rc16);
+    lr(e, offsets, po, JNI_ABORT); lr(e, outOffsets, poo, JNI_ABORT); ir(e, recs, rc16, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

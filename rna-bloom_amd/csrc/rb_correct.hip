@@ -265,26 +265,6 @@ __global__ void __launch_bounds__(CE_TPB) k_resolve_snv(FilterView fv, int stran
     }
 }
 
-// SeqUtils.isLowComplexityShort (R/util/SeqUtils.java:499-543) of the k letters get(0 .. k-1) (all of ACGT): lane l counts trinucleotide l, lanes
-// 0..15 the dinucleotides, lanes 0..3 the letters; the thresholds are tested on the increments of letter 3 onwards, as the reference tests them
-template <class GET> __device__ bool ce_low_complexity(GET get, int k, uint32_t lane) {
-    if (k < 3) return false;
-    const int t1 = min(32767, (int)floorf((float)k * 0.95f + 0.5f)), t2 = min(32767, (int)floorf((float)(k / 2) * 0.95f + 0.5f)),
-              t3 = min(32767, (int)floorf((float)(k / 3) * 0.95f + 0.5f));
-    uint32_t c3 = letter_code(get(0)) & 3u, c2 = letter_code(get(1)) & 3u, c1 = letter_code(get(2)) & 3u;
-    int n1 = (lane == c3) + (lane == c2) + (lane == c1), n2 = (lane == c3 * 4u + c2) + (lane == c2 * 4u + c1), n3 = lane == c3 * 16u + c2 * 4u + c1;
-    for (int q = 3; q < k; ++q) {
-        c3 = c2; c2 = c1; c1 = letter_code(get(q)) & 3u;
-        bool hit = false;
-        if (lane == c1) hit = ++n1 >= t1;
-        if (lane == c2 * 4u + c1) hit = hit || ++n2 >= t2;
-        if (lane == c3 * 16u + c2 * 4u + c1) hit = hit || ++n3 >= t3;
-        if (__ballot(hit)) return true;
-    }
-    const int a0 = __shfl(n1, 0, 64), a1 = __shfl(n1, 1, 64), a2 = __shfl(n1, 2, 64), a3 = __shfl(n1, 3, 64);
-    return a0 + a1 >= t1 || a0 + a2 >= t1 || a0 + a3 >= t1 || a1 + a2 >= t1 || a1 + a3 >= t1 || a2 + a3 >= t1;
-}
-
 // ---- path gaps (:3819-3845): a wavefront per gap joins the two walks as getMaxCoveragePath does (:1591-1675).  Walk w of the L arrays went right from
 // the good k-mer before gap list[w], walk w of the R arrays back from the good k-mer behind it (bound 0 where the first arrived).  k-mer j of a walk is
 // seq[j+1 .. j+k] in walk orientation (a left walk's letters run right to left).  The path is the left walk if it arrived; else the right walk's

@@ -33,6 +33,9 @@ REPR_PATH_NONE, REPR_PATH_LEFT, REPR_PATH_RIGHT, REPR_PATH_SPLICED = range(4)
 # rb_graph_trim_rc_artifacts: mode; rb_trim_rec.flags (a sequence that is not judged carries SCREEN_BAD_LETTER / SCREEN_NO_KMER, or TRIM_NOT_JUDGED)
 TRIM_HASHES, TRIM_EDGE, TRIM_LONG = range(3)
 TRIM_FOUND, TRIM_TRIMMED, TRIM_NOT_JUDGED = 1, 2, 32
+# rb_graph_correct_long: rb_long_rec.status, rb_long_rec.flags
+LONG_NULL, LONG_UNCHANGED, LONG_CHANGED, LONG_NO_KMER = range(4)
+LONG_OVERFLOW, LONG_TRIMMED_TO_NOTHING = 1, 2
 
 
 class GraphParams(C.Structure):
@@ -78,6 +81,15 @@ class CorrParams(C.Structure):
 
 
 assert C.sizeof(CorrParams) == 16
+
+
+class LongParams(C.Structure):
+    _fields_ = [("max_itr", C.c_int32), ("lookahead", C.c_int32), ("max_indel_size", C.c_int32), ("min_kmer_cov", C.c_int32),
+                ("min_num_solid", C.c_int32), ("trim_low_cov_edges", C.c_int32), ("window_size", C.c_int32),
+                ("max_cov_gradient", C.c_float), ("percent_identity", C.c_float)]
+
+
+assert C.sizeof(LongParams) == 36
 
 
 class Profile(C.Structure):
@@ -128,6 +140,7 @@ SYMBOLS = [
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
     ("rb_graph_represented", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp]),
     ("rb_graph_trim_rc_artifacts", _i32, [_vp, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp]),
+    ("rb_graph_correct_long", _i32, [_vp, _vp, _vp, _i64, C.POINTER(LongParams), _vp, _vp, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),
     ("rb_graph_walk", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_greedy_extend", _i32, [_vp, _vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

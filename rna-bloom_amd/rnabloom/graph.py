@@ -777,6 +777,68 @@ class BloomFilterDeBruijnGraph:
         seq, off = _pack(seqs)
         return self.trimArtifactsFlat(seq, off, mode, maxEdgeClip, maxCovGradient)
 
+    LONG_DTYPE = np.dtype([(f, "<i4") for f in (
+        "status", "passes", "out_len", "trim_begin", "trim_end", "snv_replaced", "snv_kept", "path_none", "zero_accepted", "zero_kept",
+        "accepted_10x", "accepted_identity", "cov_kept", "short_skipped", "anchor_moved", "flags")])
+    LONG_NULL, LONG_UNCHANGED, LONG_CHANGED, LONG_NO_KMER = N.LONG_NULL, N.LONG_UNCHANGED, N.LONG_CHANGED, N.LONG_NO_KMER
+    LONG_OVERFLOW, LONG_TRIMMED_TO_NOTHING = N.LONG_OVERFLOW, N.LONG_TRIMMED_TO_NOTHING
+    LONG_DEFAULTS = dict(maxItr=2, maxCovGradient=0.5, lookahead=5, maxIndelSize=1, percentIdentity=0.9, minKmerCov=1, minNumSolidKmers=0,
+                         trimLowCovEdges=False, windowSize=500)
+
+    def _long_params(self, params):
+        unknown = set(params) - set(self.LONG_DEFAULTS)
+        if unknown:
+            raise TypeError("correctLong: unknown parameters %s" % sorted(unknown))
+        a = dict(self.LONG_DEFAULTS, **params)
+        return N.LongParams(a["maxItr"], a["lookahead"], a["maxIndelSize"], a["minKmerCov"], a["minNumSolidKmers"], int(bool(a["trimLowCovEdges"])),
+                            a["windowSize"], a["maxCovGradient"], a["percentIdentity"])
+
+    def correctLongFlat(self, seq, offsets, outOffsets, **params):
+        """rb_graph_correct_long on flat host text: GraphUtils.correctLongSequenceWindowed (R/util/GraphUtils.java:3087-3185) of sequence i =
+        seq[offsets[i]:offsets[i + 1]] (uint8).  outOffsets is the caller's capacity layout (n + 1).  params: the keys of LONG_DEFAULTS, named as
+        the reference names them.  Returns (out, recs): the uint8 text buffer laid out by outOffsets and one LONG_DTYPE record per sequence;
+        the text of sequence i is out[outOffsets[i]:outOffsets[i] + recs[i]["out_len"]] unless recs[i]["flags"] has LONG_OVERFLOW, in which
+        case nothing was written for it and out_len is the room it needs."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        oo = np.ascontiguousarray(outOffsets, dtype=np.int64)
+        n = off.size - 1
+        if oo.size != n + 1:
+            raise ValueError("correctLongFlat: outOffsets needs %d entries" % (n + 1))
+        p = self._long_params(params)
+        out = np.zeros(max(1, int(oo[-1]) if n else 0), np.uint8)
+        recs = np.zeros(n, self.LONG_DTYPE)
+        check(lib.rb_graph_correct_long(self.h, _ptr(seq), _ptr(off), n, C.byref(p), _ptr(oo), _ptr(out), _ptr(recs)))
+        return out, recs
+
+    def correctLong(self, seqs, slack=16, **params):
+        """correctLongFlat over strings (or bytes) -> (texts, recs).  Every sequence gets room for its length + slack; the sequences that outgrew
+        it (LONG_OVERFLOW) are corrected once more with the room their records ask for — the computation is deterministic, so that call has
+        their answer.  texts[i] is the final text as bytes (the input where recs[i]["status"] is LONG_NULL or LONG_NO_KMER)."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        recs = np.zeros(len(seqs), self.LONG_DTYPE)
+        texts = [None] * len(seqs)
+        todo, room = list(range(len(seqs))), [len(s) + slack for s in seqs]
+        for _ in range(2):
+            if not todo:
+                break
+            seq, off = _pack([seqs[i] for i in todo])
+            oo = np.zeros(len(todo) + 1, np.int64)
+            np.cumsum([room[i] for i in todo], out=oo[1:])
+            out, rc = self.correctLongFlat(seq, off, oo, **params)
+            again = []
+            for j, i in enumerate(todo):
+                recs[i] = rc[j]
+                if int(rc[j]["flags"]) & self.LONG_OVERFLOW:
+                    room[i] = int(rc[j]["out_len"])
+                    again.append(i)
+                else:
+                    texts[i] = out[oo[j]:oo[j] + int(rc[j]["out_len"])].tobytes()
+            todo = again
+        if todo:
+            raise RuntimeError("correctLong: %d sequences overflowed the room their own records asked for" % len(todo))
+        return texts, recs
+
     def applyOverlapRescue(self, left, right, rec, minKmerCov=1.0):
         """What the reference does to the graph for one pair that overlapPairs reported as OVL_RESCUE (R/util/GraphUtils.java:5018-5056), through
         calls that exist: addDbgOnly of the spanning k-mers of count 0, correctMismatches of the joined k-mer list with threshold 2, and

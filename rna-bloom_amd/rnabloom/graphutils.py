@@ -310,3 +310,56 @@ def trimReverseComplementArtifact(graph, seqs, mode, maxEdgeClip=0, maxCovGradie
         else:
             out.append(s[begin:end + k - 1] if end > begin else s[:0])
     return out
+
+
+def correctLongSequenceWindowed(graph, seqs, **params):
+    """GraphUtils.correctLongSequenceWindowed (R/util/GraphUtils.java:3087-3185) for many sequences in one rb_graph_correct_long call (and a
+    second one for the few that outgrew their room).  params: graph.LONG_DEFAULTS' keys, named as the reference's arguments.  Returns, per
+    sequence, the string the returned k-mers spell ("" for a list trimmed to nothing), or None where the reference returns null (the
+    solid-k-mer screen) and for a sequence without a k-mer, which the reference's caller never passes."""
+    texts, recs = graph.correctLong(seqs, **params)
+    return [None if int(rc["status"]) in (graph.LONG_NULL, graph.LONG_NO_KMER) else t for t, rc in zip(texts, recs)]
+
+
+def assembleValidKmers(graph, seqs):
+    """GraphUtils.assembleValidKmers (R/util/GraphUtils.java:3626-3654) of each sequence's getKmers list, on the host from one rb_graph_kmers
+    call: the strings of the maximal runs of k-mers that have a count above 0 or no letter outside ACGTU."""
+    k = graph.k
+    seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    ko, _, _, cnt = graph.getKmers(seqs)
+    out = []
+    for i, s in enumerate(seqs):
+        c = cnt[ko[i]:ko[i + 1]]
+        bad = np.frombuffer(s, np.uint8)[:, None] != np.frombuffer(b"ACGTUacgtu", np.uint8)[None, :]
+        bad = np.concatenate(([0], np.cumsum(bad.all(axis=1))))                       # letters outside ACGTU before each position
+        valid = (c > 0) | (bad[k:k + len(c)] - bad[:len(c)] == 0)
+        segs, start = [], -1
+        for j, v in enumerate(valid):
+            if v:
+                if start < 0:
+                    start = j
+            elif start >= 0:
+                segs.append(s[start:j - 1 + k])
+                start = -1
+        if start >= 0:
+            segs.append(s[start:])
+        out.append(segs)
+    return out
+
+
+def correctLongReads(graph, seqs, trimArtifact=True, **params):
+    """What LongReadCorrectionWorker.run does to every segment (R/RNABloom.java:3788-3840), as three batched calls: correctLongSequenceWindowed;
+    the seven-argument trimReverseComplementArtifact (mode TRIM_LONG, maxEdgeClip 150, the call's maxCovGradient), whose result is taken only
+    if it is not empty and shorter (a sequence that call does not judge — a letter outside ACGTU — stays as it is); assembleValidKmers.
+    Returns, per sequence, the list of strings the worker would put out: [] for a segment it discards."""
+    corrected = correctLongSequenceWindowed(graph, seqs, **params)
+    alive = [i for i, t in enumerate(corrected) if t]
+    texts = [corrected[i] for i in alive]
+    if trimArtifact and texts:
+        grad = params.get("maxCovGradient", graph.LONG_DEFAULTS["maxCovGradient"])
+        trimmed = trimReverseComplementArtifact(graph, texts, graph.TRIM_LONG, 150, grad, keepNotJudged=True)
+        texts = [t if t and len(t) < len(s) else s for s, t in zip(texts, trimmed)]
+    out = [[] for _ in seqs]
+    for i, segs in zip(alive, assembleValidKmers(graph, texts)):
+        out[i] = segs
+    return out
