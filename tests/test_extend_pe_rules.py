@@ -102,7 +102,8 @@ class StepPE(Step):
 
 def extend_step_pe(g, seq, direction, min_cov, d_r, d_f, k):
     """extendRightPE (direction 0, :6206-6309) / extendLeftPE (1, :6311-6414) of getKmers(seq); for the left-hand direction the list is
-    reversed here, as the reference's callers reverse it.  max_ext of the record is max(bound of the first-level walks, 0)."""
+    reversed here, as the reference's callers reverse it.  max_ext of the record is max(bound of the first-level walks, 0).  Lower-case
+    letters are read as upper-case ones, as everywhere in the library; the reference's isRepeat would throw on them."""
     n = len(seq) - k + 1
     m0 = d_f - 2
     if n < 1:
@@ -131,7 +132,7 @@ def extend_step_pe(g, seq, direction, min_cov, d_r, d_f, k):
         return StepPE(SINGLE, WHY_FOUND, 1, [(c, F32(c4[b]), b)] + walk(c, max_ext), winner=b, max_ext=m0, tags=tags)
     try:
         for i in range(n - 1, -1, -1):                                    # :6226-6233
-            if is_repeat(kmers[i]):
+            if is_repeat(kmers[i].upper()):                               # (lower case is read as upper case: include/rb_capi.h, rb_graph_extend_pe)
                 max_ext -= 1
             else:
                 break
@@ -392,14 +393,16 @@ class WorldPE:
     add_reads call; a fragment given with a transcript replaces the one-in-three rule for it."""
     FSIZE = 2_400_011
 
-    def __init__(self, k, stranded, seed, d_r, d_f, extra=(), **kw):
+    def __init__(self, k, stranded, seed, d_r, d_f, extra=(), fsize=None, second_level_lengths=None, frag_part=0.6, **kw):
         from oracle import rbo
+        if fsize is not None:
+            self.FSIZE = fsize
         self.w = w = World(k, stranded, seed, d=d_r, **kw)
         self.k, self.stranded, self.d_r, self.d_f, self.hashes, self.sizes = k, stranded, d_r, d_f, w.hashes, w.sizes
         self.og, self.packed = w.og, w.packed
         tx, queries, floors = list(w.tx), list(w.queries), list(w.floors)
         self.extra_packed = None
-        extra, pieces = list(extra) + second_level_by_fragments(k, d_f, seed + 1), {}
+        extra, pieces = list(extra) + second_level_by_fragments(k, d_f, seed + 1, second_level_lengths), {}
         if extra:
             reads = []
             read_len, tile = kw.get("read_len", 100), kw.get("tile", 10)
@@ -429,7 +432,7 @@ class WorldPE:
         self.og.init_fragment_pairs(self.FSIZE, self.frag_h, d_f)
         frags = []
         for i, (t, _) in enumerate(tx):
-            piece = pieces[i] if i in pieces else t if i % 3 == 0 else t[:int(len(t) * 0.6)] if i % 3 == 1 else b""
+            piece = pieces[i] if i in pieces else t if i % 3 == 0 else t[:int(len(t) * frag_part)] if i % 3 == 1 else b""
             if len(piece) >= k + d_f:
                 frags += [piece, piece[::-1]]
         self.frags = frags
@@ -461,7 +464,10 @@ class WorldPE:
             assert NEED_TAGS <= tags, (direction, NEED_TAGS - tags)
 
 
-def second_level_by_fragments(k, d_f, seed):
+SECOND_LEVEL_LENGTHS = dict(prefix=100, branch=50)      # letters beyond d_f of the shared prefix and of each branch, as at k = 25
+
+
+def second_level_by_fragments(k, d_f, seed, lengths=None):
     """(transcript, multiplicity, queries, fragment): a fork, a second one five letters on, and fragments of the two far branches that begin
     so late that the first stretch's partners have no fragment pair and the chain's k-mers from the eighth on have one: the first stretch
     goes to the second level with read pairs alone and wins there with both kinds.  Nothing for d_f < 12 (the chain is too short)."""
@@ -469,7 +475,8 @@ def second_level_by_fragments(k, d_f, seed):
         return []
     rng = np.random.default_rng(seed)
     rnd = lambda n: np.frombuffer(ACGT, np.uint8)[rng.integers(0, 4, n)].tobytes()
-    p, a, bb, c1, c2 = rnd(d_f + 100), rnd(d_f + 50), rnd(5), rnd(d_f + 50), rnd(d_f + 50)
+    ln = dict(SECOND_LEVEL_LENGTHS, **(lengths or {}))
+    p, a, bb, c1, c2 = rnd(d_f + ln["prefix"]), rnd(d_f + ln["branch"]), rnd(5), rnd(d_f + ln["branch"]), rnd(d_f + ln["branch"])
     other = lambda x, y: ACGT[(ACGT.index(y[0:1]) + 1) % 4:][:1] + x[1:]          # x with a first letter that is not y's: the forks are forks
     bb, c2 = other(bb, a), other(c2, c1)
     s0 = len(p) - k + 1 - d_f + 8                             # the first k-mer with a fragment pair d_f on is the chain's k-mer 8
@@ -477,26 +484,31 @@ def second_level_by_fragments(k, d_f, seed):
     return [(p + a, 1, [("frag-second", p), ("frag-second-short", p[-(k + 3):])], p + a), (t1, 1, [], t1[s0:]), (t2, 2, [], t2[s0:])]
 
 
-def extras(k, d_f, seed):
+EXTRAS_LENGTHS = dict(flank=150, circle_unit=40, circle_reps=8)     # as at k = 25; tests/pair_worlds.py derives them from k
+
+
+def extras(k, d_f, seed, lengths=None):
     """what R.World has not: forks behind a short homopolymer stretch with queries whose trailing repeats end at a k-mer with an N (the
     reference's isRepeat throws) — within the d_f - 2 k-mers the device scans; the restatement, like the reference, would throw on an N
     further back in an unbroken run of repeats, where the device has stopped (rb_capi.h), so the worlds hold no such query —; forks behind
     more than d_f - 2 repeat k-mers (the bound is not positive); a circle of 40 k-mers (a walk meets its start again)"""
     rng = np.random.default_rng(seed)
     rnd = lambda n: np.frombuffer(ACGT, np.uint8)[rng.integers(0, 4, n)].tobytes()
+    ln = dict(EXTRAS_LENGTHS, **(lengths or {}))
+    flank, reps = ln["flank"], ln["circle_reps"]
     out = []
     for i in range(2):
-        w, a, b = rnd(150), rnd(150), rnd(150)
+        w, a, b = rnd(flank), rnd(flank), rnd(flank)
         run = b"ACGT"[i:i + 1] * (k + 6)
         p = w + run
         qs = [("rep-fork", p), ("rep-fork-n", R.put(p, len(w) - 3, "N")), ("rep-fork-n-far", R.put(p, 20, "N")), ("rep-fork-short", p[len(w) - 4:])]
         out += [(p + a, 1, qs), (p + b, 2, [])]
     for run in (b"C" * (k + d_f + 5), b"AG" * ((k + d_f + 6) // 2)):
-        w, a, b = rnd(150), rnd(150), rnd(150)
+        w, a, b = rnd(flank), rnd(flank), rnd(flank)
         p = w + run
         out += [(p + a, 1, [("rep-long", p), ("rep-long-short", p[-(k + 40):])]), (p + b, 2, [])]
-    c = rnd(40)
-    out.append((c * 8, 1, [("circle-40", (c * 8)[5:5 + k + 10])]))
+    c = rnd(ln["circle_unit"])
+    out.append((c * reps, 1, [("circle-40", (c * reps)[5:5 + k + 10])]))
     return out
 
 

@@ -396,11 +396,20 @@ class World:
     """Transcripts tiled with reads (every k-mer counts about 8 times its transcript's multiplicity) and the sequences to extend.  Everything
     is made for the right-hand direction and mirrored: the reversed transcripts are inserted too and the reversed queries go left."""
     FLOORS = (1.0, 2.0, 5.0, 1.0e6)
+    SIZES = (4_800_011, 4_800_011, 4_800_017)
+    # the lengths that do not follow from k by themselves (letters, or repeats of a unit), as the worlds at k = 25 have them; tests/pair_worlds.py
+    # derives them from k: flanks of the tandem repeats and homopolymers, the tandem units, how often they repeat in the transcript, in the
+    # `tandem` query and in the text the `circle` query is cut from, the homopolymer run inside a transcript, the transcript that is nothing else
+    # and the run the `poly` query ends in, how far `mid` reaches behind the fork, the long transcript and its query
+    LENGTHS = dict(flank=100, units=(14, 20), unit_reps=12, tandem_query_reps=2, circle_reps=4, poly_run=60, poly_tx=120, poly_query=30, mid=100,
+                   long_tx=3000, long_query=2900)
 
-    def __init__(self, k, stranded, seed, d=30, n_iso=6, read_len=100, tile=10, tx_len=500, hashes=(2, 2, 2)):
+    def __init__(self, k, stranded, seed, d=30, n_iso=6, read_len=100, tile=10, tx_len=500, hashes=(2, 2, 2), sizes=None, lengths=None, extra_tx=()):
+        """extra_tx: (transcript, multiplicity, [(kind, query)]) behind the world's own, tiled and mirrored as they are"""
         from oracle import rbo
         rng = np.random.default_rng(seed)
         self.k, self.stranded, self.d, self.hashes = k, stranded, d, hashes
+        self.lengths = ln = dict(self.LENGTHS, **(lengths or {}))
         rnd = lambda n: np.frombuffer(ACGT, np.uint8)[rng.integers(0, 4, n)].tobytes()
         half = tx_len // 2
         tx, q = [], []                                        # (transcript, multiplicity), (kind, sequence)
@@ -415,7 +424,7 @@ class World:
             q.append(("fork-one-kmer", p[half - k:]))
             q.append(("fork-n-back", put(p, half - k - 4, "N")))                              # an N inside the last d k-mers
             q.append(("fork-n-seed", put(p, half - 3, "N")))                                  # ... inside the last k-mer
-            q.append(("mid", (p + a)[:half + 100]))
+            q.append(("mid", (p + a)[:half + ln["mid"]]))
             q.append(("dead-end", p + a))
         for i in range(n_iso):                                # a second fork g k-mers after the first
             g2 = max(1, (5, 20, d - 3, d - 2, d - 1, 12)[i % 6])
@@ -432,21 +441,24 @@ class World:
             tx += [(p1 + s1, 1), (p2 + j + s2, 1 + i % 3), (p3 + j, 1)]
             q += [("junction-1", p1), ("junction-2", p2 + j), ("junction-3", p3 + j)]
         for i in range(2):                                    # a tandem repeat whose period is below d k-mers, and a homopolymer
-            w, z, unit = rnd(100), rnd(100), rnd(14 + 6 * i)
-            tx += [(w + unit * 12 + z, 1), (unit[::-1] * 12, 1)]             # ... and one that is nothing else: every k-mer has one successor
-            q += [("tandem", w + unit * 2), ("circle", (unit[::-1] * 4)[3:3 + k + 8])]
-            w, z = rnd(100), rnd(100)
-            tx += [(w + b"A" * 60 + z, 1), (b"C" * 120, 1)]
-            q += [("poly", w + b"A" * 30), ("poly-in", b"A" * (k + 3)), ("poly-only", b"C" * (k + 3))]
+            w, z, unit = rnd(ln["flank"]), rnd(ln["flank"]), rnd(ln["units"][i])
+            tx += [(w + unit * ln["unit_reps"] + z, 1), (unit[::-1] * ln["unit_reps"], 1)]             # ... and one that is nothing else: every k-mer has one successor
+            q += [("tandem", w + unit * ln["tandem_query_reps"]), ("circle", (unit[::-1] * ln["circle_reps"])[3:3 + k + 8])]
+            w, z = rnd(ln["flank"]), rnd(ln["flank"])
+            tx += [(w + b"A" * ln["poly_run"] + z, 1), (b"C" * ln["poly_tx"], 1)]
+            q += [("poly", w + b"A" * ln["poly_query"]), ("poly-in", b"A" * (k + 3)), ("poly-only", b"C" * (k + 3))]
         self.hot = []
         for i in range(2):                                    # a fork behind 100 letters that are covered 150 times more: extendSE's floor falls twice
             p, a, b = rnd(half), rnd(half), rnd(half)
             tx += [(p + a, 1), (p + b, 1), (p[half - read_len:], 150)]
             self.hot.append(p[half - k - 4:])
-        big = rnd(3000)
+        big = rnd(ln["long_tx"])
         tx.append((big, 1))
-        q.append(("long", big[:2900]))
+        q.append(("long", big[:ln["long_query"]]))
         q += [("too-short", tx[0][0][:k - 1]), ("empty", b"")]
+        for t, m, qs in extra_tx:
+            tx.append((t, m))
+            q += list(qs)
         self.tx = tx
         self.queries = [(kind, s, 0) for kind, s in q] + [(kind, s[::-1], 1) for kind, s in q]
         self.floors = [self.FLOORS[i % 4] if kind.startswith(("fork", "junction")) and i % 3 == 0 else 1.0 for i, (kind, _, _) in enumerate(self.queries)]
@@ -458,7 +470,7 @@ class World:
                     starts.append(len(tt) - read_len)
                 reads += [tt[a:a + read_len] for a in starts] * m
         self.reads = reads
-        self.sizes = (4_800_011, 4_800_011, 4_800_017)
+        self.sizes = tuple(sizes or self.SIZES)
         self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
         self.og.set_read_pair_distance(d)
         self.packed = rbo.pack_reads(reads, [b"I" * len(s) for s in reads])

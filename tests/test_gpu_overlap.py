@@ -58,21 +58,31 @@ class World:
     """transcripts tiled with reads (every k-mer counts about 10), `single` transcripts of which only the two reads of one pair are inserted
     — once each, so that their k-mers count 1 and the k-mers across the junction are absent — and the pairs to ask about"""
     D = 30                          # read-paired k-mer distance
+    SIZES = (2_400_011, 2_400_011, 400_009)
+    # the lengths that do not follow from k by themselves, as the worlds at k = 25 and 21 have them (tests/pair_worlds.py derives them from k):
+    # transcripts and the reads that tile them, the singleton transcripts and their two reads, the reads of the pairs cut from the covered
+    # transcripts and where they may begin, the containments (left read, where the right read inside it begins at the latest and ends; the
+    # read that is a prefix or lies in the middle of the other, and how far in), the long-* pairs (the overlap of k or more and the one
+    # below k, the short read), how much longer than k the reads of the dovetail below k may be
+    LENGTHS = dict(tx=500, long_tx=3000, read=100, tile=10, single_tx=300, single_read=(60, 110), pair_read=(40, 150), pair_start=150,
+                   inside_left=150, inside_shift=40, inside_end=110, contained=60, middle_at=20, dovetail_span=7, long_merge=30, long_span=15, long_read=100)
 
-    def __init__(self, k, stranded, seed, n_tx=40, n_single=48, hashes=(2, 2, 2)):
+    def __init__(self, k, stranded, seed, n_tx=40, n_single=48, hashes=(2, 2, 2), sizes=None, lengths=None, n_pairs=260, extra_reads=(), extra_pairs=()):
+        """extra_reads go into the graph once each behind the world's own; extra_pairs: (kind, left, right) behind the world's own"""
         rng = np.random.default_rng(seed)
         self.k, self.stranded, self.rng, self.hashes = k, stranded, rng, hashes
+        self.lengths = ln = dict(self.LENGTHS, **(lengths or {}))
         rnd = lambda n: ACGT[rng.integers(0, 4, n)].tobytes()
-        self.tx = [rnd(500) for _ in range(n_tx)] + [rnd(3000) for _ in range(2)]
-        reads = [t[a:a + 100] for t in self.tx for a in range(0, len(t) - 99, 10)]
+        self.tx = [rnd(ln["tx"]) for _ in range(n_tx)] + [rnd(ln["long_tx"]) for _ in range(2)]
+        reads = [t[a:a + ln["read"]] for t in self.tx for a in range(0, len(t) - ln["read"] + 1, ln["tile"])]
         self.pairs, self.kind = [], []
         add = lambda kind, left, right: (self.pairs.append((left, right)), self.kind.append(kind))
         ri = lambda a, b: int(rng.integers(a, b + 1))
         # ---- singleton reads around a junction that no read covers ----
         for j in range(n_single):
-            t, kind = rnd(300), j % 8
+            t, kind = rnd(ln["single_tx"]), j % 8
             small = kind == 6                                                   # the dovetail with fewer than k bases: reads of at most 4 (k - 1) / 3
-            ll, rl = (ri(k + 3, k + 6), ri(k + 3, k + 6)) if small else (ri(60, 110), ri(60, 110))
+            ll, rl = (ri(k + 3, k + 6), ri(k + 3, k + 6)) if small else (ri(*ln["single_read"]), ri(*ln["single_read"]))
             o = k - 2 if small else ri(MO, k - 1)
             if kind == 4:
                 t = t[:ll - o] + (b"AC" * k)[:o] + t[ll:]                      # the shared bases are a dinucleotide repeat
@@ -82,11 +92,12 @@ class World:
             reads += [left, right] + ([right] if kind == 2 else []) + ([left] if kind == 3 else [])
             add("single%d" % kind, *((right, left) if small else (left, right)))
         # ---- pairs from the covered transcripts ----
-        for i in range(260):
+        c_left, c_in, c_end, c_len, c_at = ln["inside_left"], ln["inside_shift"], ln["inside_end"], ln["contained"], ln["middle_at"]
+        for i in range(n_pairs):
             t = self.tx[i % n_tx]
             kind = i % 13
-            ll, rl = ri(40, 150), ri(40, 150)
-            a = ri(0, 150)
+            ll, rl = ri(*ln["pair_read"]), ri(*ln["pair_read"])
+            a = ri(0, ln["pair_start"])
             if kind in (0, 1):
                 o = ri(k, min(ll, rl) - 1)                                      # merged
             elif kind in (2, 3):
@@ -98,11 +109,11 @@ class World:
             elif kind == 5:
                 add("other", t[a:a + ll], self.tx[(i + 7) % n_tx][a:a + rl])
             elif kind == 6:
-                add("inside", t[a:a + 150], t[a + ri(1, 40):a + 110])          # right in the middle of left
-                add("suffix", t[a:a + 150], t[a + 150 - rl:a + 150])
+                add("inside", t[a:a + c_left], t[a + ri(1, c_in):a + c_end])   # right in the middle of left
+                add("suffix", t[a:a + c_left], t[a + c_left - rl:a + c_left])
             elif kind == 7:
-                add("prefix", t[a:a + 60], t[a:a + 60 + rl])                    # left is a prefix of right
-                add("middle", t[a + 20:a + 80], t[a:a + 150])                   # left in the middle of right: the `contains` fallback
+                add("prefix", t[a:a + c_len], t[a:a + c_len + rl])              # left is a prefix of right
+                add("middle", t[a + c_at:a + c_at + c_len], t[a:a + c_left])    # left in the middle of right: the `contains` fallback
             elif kind == 8:
                 add("equal", t[a:a + ll], t[a:a + ll])
             elif kind == 9:
@@ -110,7 +121,7 @@ class World:
                 o = ri(max(k, n * 3 // 4 - 2), n - 1)                           # the dovetail around the 3/4 boundary, k bases or more
                 add("dovetail", t[a + ll - o:a + ll - o + rl], t[a:a + ll])
             elif kind == 10:
-                ll, rl = ri(k + 1, k + 7), ri(k + 1, k + 7)                     # the dovetail with fewer than k bases shared
+                ll, rl = ri(k + 1, k + ln["dovetail_span"]), ri(k + 1, k + ln["dovetail_span"])      # the dovetail with fewer than k bases shared
                 o = ri(min(ll, rl) * 3 // 4 - 1, k - 1)
                 add("dovetail-span", t[a + ll - o:a + ll - o + rl], t[a:a + ll])
             elif kind == 11:
@@ -126,15 +137,18 @@ class World:
         # one k-mer each; a read below max(k, min_overlap); pairs longer than the LDS row in each role, the match at the far end
         t, big = self.tx[0], self.tx[-1]
         add("one-kmer", t[0:k], t[5:5 + k])
-        add("short", t[0:k - 1], t[0:60])
-        add("short", t[0:60], b"")
-        add("long-left", big[0:1500], big[1470:1570])
-        add("long-left-span", big[100:1500], big[1485:1600])
-        add("long-right", big[100:200], big[170:1700])
-        add("long-both", big[0:1400], big[1385:2900])
+        add("short", t[0:k - 1], t[0:c_len])
+        add("short", t[0:c_len], b"")
+        om, os_, lr = ln["long_merge"], ln["long_span"], ln["long_read"]
+        add("long-left", big[0:1500], big[1500 - om:1500 - om + lr])
+        add("long-left-span", big[100:1500], big[1500 - os_:1500 + lr])
+        add("long-right", big[100:100 + lr], big[100 + lr - om:1700])
+        add("long-both", big[0:1400], big[1400 - os_:2900])
         add("long-none", big[0:1400], self.tx[-2][0:1400])
-        self.reads = reads
-        self.sizes = (2_400_011, 2_400_011, 400_009)
+        for kind, left, right in extra_pairs:
+            add(kind, left, right)
+        self.reads = reads = reads + list(extra_reads)
+        self.sizes = tuple(sizes or self.SIZES)
         self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
         self.og.set_read_pair_distance(self.D)
         self.packed = rbo.pack_reads(reads, [b"I" * len(s) for s in reads])

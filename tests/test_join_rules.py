@@ -360,8 +360,15 @@ class JoinWorld:
     forks on either branch, a substitution near the start of the right read or the end of the left read, pairs inside the tandem repeats and
     the homopolymers, pairs in the wrong order, a read with an N, a lower-case read, a short read."""
     BOUND, GRAD, MIN_COV, TIP = 20, 0.5, 1.0, 10
+    # the lengths that do not follow from k by themselves, as the worlds at k = 25 have them (tests/pair_worlds.py derives them from k): the
+    # shortest transcript that has a fork or junction in its middle; the homopolymer runs a transcript is recognised by (A, C), how many of
+    # the run's letters end the left read of the first pair, where its right read and the left read of the second pair begin in the run
+    PAIR_LENGTHS = dict(fork_tx=260, a_run=40, c_run=100, run_left=5, run_right=55, run_second=20)
 
-    def __init__(self, k, stranded, seed, d=30, n_pairs=700, read_len=None, **kw):
+    def __init__(self, k, stranded, seed, d=30, n_pairs=700, read_len=None, world_read_len=None, pair_lengths=None, extra_pairs=(), **kw):
+        if world_read_len is not None:                                    # (read_len is the length of the pairs' reads, not of the world's)
+            kw["read_len"] = world_read_len
+        pl = dict(self.PAIR_LENGTHS, **(pair_lengths or {}))
         self.w = w = R.World(k, stranded, seed, d=d, **kw)
         self.k, self.d, self.stranded, self.og, self.o, self.sizes, self.hashes, self.packed = k, d, stranded, w.og, w.o, w.sizes, w.hashes, w.packed
         rng = np.random.default_rng(seed + 1)
@@ -375,7 +382,7 @@ class JoinWorld:
             kind = int(rng.integers(0, 10))
             gap = int(rng.integers(1, self.BOUND + 6))                    # missing k-mers between the reads
             a = int(rng.integers(0, max(1, len(t) - 2 * L - gap)))
-            if kind < 2 and len(t) > 260:                                 # across the fork / junction in the middle of the transcript
+            if kind < 2 and len(t) > pl["fork_tx"]:                       # across the fork / junction in the middle of the transcript
                 a = max(0, min(len(t) - 2 * L - gap, len(t) // 2 - L - int(rng.integers(0, gap + 1))))
             b = a + L - k + 1 + gap
             left, right = t[a:a + L], t[b:b + L]
@@ -390,16 +397,17 @@ class JoinWorld:
             elif kind == 5:
                 right = sub(right, int(rng.integers(k, len(right))))
             pairs.append((left, right))
-        for t in [t for t, _ in w.tx if b"A" * 40 in t or b"C" * 100 in t]:       # homopolymer runs
-            p = t.find(b"A" * 40) if b"A" * 40 in t else 10
-            pairs += [(t[max(0, p - L + 5):p + 5][:L], t[p + 55:p + 55 + L] if len(t) > p + 55 + k else t[-L:]), (t[p + 20:p + 20 + L], t[-L:])]
+        a_run, c_run, r_l, r_r, r_s = b"A" * pl["a_run"], b"C" * pl["c_run"], pl["run_left"], pl["run_right"], pl["run_second"]
+        for t in [t for t, _ in w.tx if a_run in t or c_run in t]:                # homopolymer runs
+            p = t.find(a_run) if a_run in t else 10
+            pairs += [(t[max(0, p - L + r_l):p + r_l][:L], t[p + r_r:p + r_r + L] if len(t) > p + r_r + k else t[-L:]), (t[p + r_s:p + r_s + L], t[-L:])]
         for kind, s, direction in w.queries:
             if kind in ("tandem", "circle") and direction == 0 and len(s) >= k + 4:
                 pairs += [(s[:k + 4], s[-(k + 4):]), (s[-(k + 4):], s[:k + 4])]
         t0 = w.tx[0][0]
         pairs += [(R.put(t0[:L], 7, "N"), t0[L + 5:2 * L + 5]), (t0[:L].lower(), t0[L + 5:2 * L + 5].replace(b"T", b"U")), (t0[:k - 1], t0[L:2 * L]), (t0[:L], b""),
                   (t0[:L], t0[L + 3:L + 3 + k])]
-        self.pairs = pairs
+        self.pairs = pairs + list(extra_pairs)
         self._want = None
 
     def want(self):
