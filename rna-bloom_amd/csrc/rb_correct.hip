@@ -20,6 +20,7 @@
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
 #include "rb_align.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -411,8 +412,6 @@ __global__ void __launch_bounds__(CE_TPB) k_text_kmers(FilterView fv, int strand
         }
     }
 }
-
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // a bump allocator over one device buffer
 struct Arena {

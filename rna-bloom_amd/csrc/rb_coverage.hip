@@ -10,6 +10,7 @@
 
 #include "rb_pieces.hpp"
 #include "rb_repeat.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -21,9 +22,6 @@ namespace {
 constexpr int COV_BINS = 129;            // a bin per count code (count_code_of, rb_device.hpp): every count getCount can return
 constexpr int COV_TPB = 256;
 constexpr int64_t COV_LONG = 4096;       // segments of at least this many windows get a workgroup of their own
-
-// Math.round(float): floor(x + 1/2), exact in double for every float this file rounds
-__device__ __forceinline__ int64_t java_round(float x) { return (int64_t)floor((double)x + 0.5); }
 
 __device__ __forceinline__ bool window_usable(const uint32_t *vw, uint32_t b0, int k) {
     for (uint32_t b = b0; b < b0 + (uint32_t)k; ++b)

@@ -37,14 +37,9 @@ __global__ void __launch_bounds__(EX_TPB) k_extend(ExArgsT<PE> a, uint8_t *scrat
     if constexpr (LDS_ROW) row = s_row[wv]; else row = scratch + (size_t)slot * row_bytes;
     for (int64_t r = slot; r < a.pn; r += n_slots) {
         ex_one<PE>(a, r, row, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
     }
 }
-
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// Math.round(float) of the thresholds of SeqUtils.isRepeat: floor(x + 1/2), exact in double
-inline int java_round(float x) { return (int)std::floor((double)x + 0.5); }
 
 template <bool PE> void ex_blank(std::conditional_t<PE, rb_extend_pe_rec, rb_extend_rec> &v, int d) {
     v.outcome = RB_EXT_NONE; v.why = RB_EXT_WHY_SHORT; v.n_candidates = 0; v.out_len = 0; v.last_partnered = -1; v.winner = -1; v.score = 0.0f;
@@ -98,30 +93,18 @@ void extend_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n
     const size_t row_bytes = ex_row_bytes(lds ? EX_LDS_D : d);
     // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, floors, records, results and — for a
     // distance past the LDS row — the wavefronts' walk rows; with profiling on the kernels of every piece are timed: entry "extend_se" / "extend_pe"
-    std::vector<int64_t> tab;
     for_each_host_piece(g, s, text.data(), to.data(), ko.data(), n, PE ? "extend_pe" : "extend_se", [&](HostPiece &pc) {
         const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
-        tab.assign((size_t)pn + 1, 0);
-        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-        const rb_batch *b = pc.batch();
         const int64_t slots = lds ? pn : std::min<int64_t>(pn, EX_SCRATCH_SLOTS);
         const unsigned blocks = blocks_for(slots, EX_WAVES);
         const size_t o_fl = up16((size_t)pt * 4), o_rec = up16(o_fl + (size_t)pn * 4), o_b = o_rec + (size_t)pn * sizeof(Rec),
                      o_c = up16(o_b + (size_t)(pn * stride)), o_row = up16(o_c + (out_count ? (size_t)(pn * stride) * 4 : 0));
-        q.c->b0.reserve(tab.size() * 8);
-        q.c->b1.reserve((size_t)pt * 8);
-        q.c->b2.reserve((size_t)pt * 8);
         q.c->b3.reserve(o_row + (lds ? 0 : (size_t)blocks * EX_WAVES * row_bytes) + 16);
         uint8_t *base3 = q.c->b3.as<uint8_t>();
         ExArgsT<PE> a;
         a.fv = g->view(0, 0);
         a.pf = PairView{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
         a.stranded = (int)g->stranded; a.k = k; a.d = d; a.direction = direction; a.D = lds ? EX_LDS_D : d;
-        a.pn = pn;
-        a.kof = q.c->b0.as<int64_t>();
-        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-        a.cnt = reinterpret_cast<float *>(base3);
-        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
         a.floors = reinterpret_cast<float *>(base3 + o_fl);
         Rec *d_recs = reinterpret_cast<Rec *>(base3 + o_rec);
         if constexpr (PE) {
@@ -129,16 +112,14 @@ void extend_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n
             a.ff = PairView{g->fpk.bits, g->fpk.mod, g->fpk.num_hash, kmul_of(k)};
             a.d_r = d_r;
             // isRepeat keeps its counters in signed bytes: a threshold above 127 is never reached (t1 from k = 142 on; t2, t3 stay below for k <= RB_MAX_K)
-            const int t1 = java_round((float)k * 0.9f);
-            a.t1 = t1 > 127 ? INT32_MAX : t1; a.t2 = java_round((float)(k / 2) * 0.9f); a.t3 = java_round((float)(k / 3) * 0.9f);
+            const int t1 = (int)java_round((float)k * 0.9f);
+            a.t1 = t1 > 127 ? INT32_MAX : t1; a.t2 = (int)java_round((float)(k / 2) * 0.9f); a.t3 = (int)java_round((float)(k / 3) * 0.9f);
         } else a.recs = d_recs;
         a.out_b = base3 + o_b;
         a.out_c = out_count ? reinterpret_cast<float *>(base3 + o_c) : nullptr;
-        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
         RB_HIP(hipMemcpyAsync(base3 + o_fl, min_kmer_cov + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
         RB_HIP(hipMemsetAsync(base3 + o_b, 0, o_row - o_b, s));        // (what no wavefront writes comes back as zeros, whatever the cuts)
-        pc.kernels_begin();
-        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        PieceRows(g, *q.c, pc).into(a);
         if (lds) hipLaunchKernelGGL((k_extend<PE, true>), dim3(blocks), dim3(EX_TPB), 0, s, a, (uint8_t *)nullptr, row_bytes);
         else hipLaunchKernelGGL((k_extend<PE, false>), dim3(blocks), dim3(EX_TPB), 0, s, a, base3 + o_row, row_bytes);
         RB_HIP(hipGetLastError());

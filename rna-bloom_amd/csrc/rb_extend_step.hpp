@@ -11,6 +11,7 @@
 #include "rb_pipeline.hpp"
 #include "rb_lookup.hpp"
 #include "rb_repeat.hpp"
+#include "rb_wave.hpp"
 
 // Java float arithmetic: the score is one float32 product and one float32 quotient, the median of an even number of counts one sum and one quotient
 #pragma clang fp contract(off)
@@ -40,10 +41,6 @@ __device__ __forceinline__ void ex_put2(uint8_t *row, int i, uint32_t c) {
     const uint32_t s = 2u * ((uint32_t)i & 3u);
     row[i >> 2] = (uint8_t)(((uint32_t)row[i >> 2] & ~(3u << s)) | (c << s));
 }
-__device__ __forceinline__ uint64_t ex_shfl64(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // The text a walk's k-mers are windows of, in walking order (for the left-hand direction the reverse of the sequence's orientation): the
 // k bases of the sequence's last k-mer, then the bases of a first-level walk (its first `gap` k-mers; all of them when there is no second
@@ -64,21 +61,6 @@ struct ExChain {
     }
 };
 
-// Both strands of a k-mer, in walking order: A rolls like a forward hash along the walk, B like a reverse-strand hash.  A right-hand walk
-// has (f, r) = (A, B) with A over the bases' seeds and B over their complements'; a left-hand walk adds bases at the k-mer's front, so its
-// A is the k-mer's reverse-strand hash and its B the forward one: xm / ym turn a base into the code whose seed A / B take.
-struct ExDir {
-    int stranded, left;
-    uint32_t uk, xm, ym;
-    __device__ __forceinline__ uint64_t fwd(uint64_t A, uint64_t B) const { return left ? B : A; }
-    __device__ __forceinline__ uint64_t hash(uint64_t A, uint64_t B) const { return stranded ? fwd(A, B) : smin(A, B); }
-    // the neighbour that drops base `out` and takes base `in` (Successors / PredecessorsNTHashIterator)
-    __device__ __forceinline__ void step(uint64_t A, uint64_t B, uint32_t out, uint32_t in, uint64_t &nA, uint64_t &nB) const {
-        nA = rotl(A, 1) ^ rotl(seed_of(out ^ xm), uk) ^ seed_of(in ^ xm);
-        nB = rotr(B, 1) ^ rotr(seed_of(out ^ ym), 1) ^ rotl(seed_of(in ^ ym), uk - 1u);
-    }
-};
-
 // One naive walk (naiveExtend{Right,Left}NoBackChecks) as its four lanes hold it: lane (lane & 3) looks at neighbour base lane & 3.
 struct ExWalk {
     uint64_t A, B, start_f;      // the k-mer the walk stands on; forward hash of the k-mer it started from
@@ -90,7 +72,7 @@ struct ExWalk {
 // Advances the wavefront's walks side by side until none is alive.  Per step and walk: the neighbours with count >= min_cov (hasDepth* is
 // always true: rb_capi.h, rb_graph_naive_extend); none or several end it; the only one ends it, not added, when it equals the k-mer the
 // walk started from or the one added last (:6919); else it is added and the walk ends once ++extensionLength > bound (:6925).
-__device__ void ex_run_walks(const FilterView &fv, const ExDir &dr, float min_cov, const ExChain &ch, uint8_t *crow, uint8_t *brow, ExWalk &w, uint32_t lane) {
+__device__ void ex_run_walks(const FilterView &fv, const WaveDir<> &dr, float min_cov, const ExChain &ch, uint8_t *crow, uint8_t *brow, ExWalk &w, uint32_t lane) {
     const uint32_t in = lane & 3u;
     while (__ballot(w.alive)) {
         uint64_t nA = 0, nB = 0;
@@ -105,7 +87,7 @@ __device__ void ex_run_walks(const FilterView &fv, const ExDir &dr, float min_co
         const uint32_t m4 = (uint32_t)(__ballot(pass) >> (lane & ~3u)) & 0xFu;
         const uint32_t bi = m4 ? (uint32_t)__builtin_ctz(m4) : 0u;
         const int src = (int)((lane & ~3u) | bi);
-        const uint64_t bA = ex_shfl64(nA, src), bB = ex_shfl64(nB, src);
+        const uint64_t bA = wave_shfl64(nA, src), bB = wave_shfl64(nB, src);
         const uint32_t bcode = (uint32_t)__shfl((int)code, src, 64);
         if (w.alive) {
             if (__popc(m4) != 1) w.alive = false;
@@ -125,7 +107,7 @@ __device__ void ex_run_walks(const FilterView &fv, const ExDir &dr, float min_co
                 }
             }
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
     }
 }
 
@@ -149,7 +131,7 @@ struct ExTail {
 // stretch's own count gave for them (the same i, the same slots: min(d - 1, n - 1) only grows with n).
 struct ExPairs { int pairs, fpairs, last; };
 template <bool PE>
-__device__ ExPairs ex_count_pairs(const PairView &pf, const PairView &ff, int d_r, const ExDir &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane) {
+__device__ ExPairs ex_count_pairs(const PairView &pf, const PairView &ff, int d_r, const WaveDir<> &dr, const ExChain &ch, const ExTail &tl, int d, int n, int i0, uint32_t lane) {
     const int hi = min(d - 1, n - 1), k = (int)dr.uk;
     ExPairs res{0, 0, -1};
     for (int base = i0; base <= hi; base += 64) {
@@ -301,7 +283,7 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
     }
     const int S1 = ex_l1b_stride(D), S2 = ex_l2b_stride(D), C2 = ex_l2_cap(D);
     uint8_t *l1c = row, *l2c = l1c + 4 * D, *l1b = l2c + 16 * C2, *l2b = l1b + 4 * S1, *seed = l2b + 16 * S2;
-    const ExDir dr{a.stranded, a.direction, (uint32_t)k, a.direction ? 3u : 0u, a.direction ? 0u : 3u};
+    const WaveDir<> dr = wave_dir(a.stranded, k, a.direction);
     const ExTail tl{a.F + k0, a.R + k0, nt, a.direction};
     const uint32_t in = lane & 3u;
     int d_r = d;
@@ -330,7 +312,7 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
             return;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     // PE: the repeat scan, used below only where there are two or more candidates.  It runs here, for every sequence, because nothing of the
     // walks is held in registers yet (behind the candidates' probes it costs the kernel a dozen registers); one round of a lane per k-mer as a rule
     int rep = 0;
@@ -370,14 +352,14 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
     // first level: candidate c's walk is held by lanes 4 c .. 4 c + 3 and fills first-level row c, bound M
     const uint32_t c1 = (lane >> 2) & 3u;
     ExWalk w1;
-    w1.A = ex_shfl64(nA, (int)c1); w1.B = ex_shfl64(nB, (int)c1);
+    w1.A = wave_shfl64(nA, (int)c1); w1.B = wave_shfl64(nB, (int)c1);
     const uint32_t code1 = (uint32_t)__shfl((int)code, (int)c1, 64);
     w1.alive = lane < 16u && ((mask0 >> c1) & 1u);
     w1.start_f = dr.fwd(w1.A, w1.B);
     w1.len = 1; w1.added = 0; w1.bound = M; w1.cap = D; w1.off = 0;
     uint8_t *crow1 = l1c + c1 * D, *brow1 = l1b + c1 * S1;
     if (w1.alive && in == 0u) { crow1[0] = (uint8_t)code1; ex_put2(brow1, 0, c1); }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
     const ExChain ch1{seed, brow1, brow1, k, EX_NO_GAP};
     ex_run_walks(a.fv, dr, min_cov, ch1, crow1, brow1, w1, lane);
     int len1[4];
@@ -433,13 +415,13 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
             code = count_code(a.fv, dr.hash(nA, nB));
         }
         mask2 = (uint32_t)__ballot(probe && code >= 1u) & 0xFFFFu;
-        w2.A = ex_shfl64(nA, (int)wid); w2.B = ex_shfl64(nB, (int)wid);
+        w2.A = wave_shfl64(nA, (int)wid); w2.B = wave_shfl64(nB, (int)wid);
         const uint32_t code2 = (uint32_t)__shfl((int)code, (int)wid, 64);
         w2.alive = (mask2 >> wid) & 1u;
         w2.start_f = dr.fwd(w2.A, w2.B);
         w2.len = 1; w2.added = 0; w2.bound = (PE ? M : d) - gap; w2.cap = C2; w2.off = gap;
         if (w2.alive && in == 0u) { crow2[0] = (uint8_t)code2; ex_put2(brow2, 0, wid & 3u); }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         ex_run_walks(a.fv, dr, min_cov, ch2, crow2, brow2, w2, lane);
     }
 

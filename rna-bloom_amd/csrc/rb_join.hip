@@ -28,8 +28,6 @@ constexpr int64_t JN_MAX_ROWS = 4096;            // wavefronts of a launch (each
 constexpr int64_t JN_MIN_ROWS = 64;
 constexpr size_t JN_ROWS_BYTES = (size_t)512 << 20;   // ... fewer when the rows are large: as many as fit this, JN_MIN_ROWS at the least
 
-__host__ __device__ inline size_t jn_up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // A row, for K k-mers of paths (a pair's capacity: nkL + nkR + 2 A, A = bound + d + 2 the most one walk adds) — F[K], R[K], count[K], the
 // letters' codes [K + 2 (k - 1)] — and what the branch step reads and writes for ONE sequence: its k-mer offsets {0, nt}, its record, the packed
 // codes of the letters it asks for (the last k-mer's), its result's bases and counts, and for d > EX_LDS_D the rows of its walks.
@@ -38,11 +36,11 @@ struct JnLayout {
     int words;                                   // 64-bit words of packed codes: d + k - 1 letters
     __host__ __device__ JnLayout(int64_t K, int k, int d, bool lds) {
         words = (d + k - 1 + 31) / 32 + 1;
-        o_f = 0; o_r = o_f + (size_t)K * 8; o_c = o_r + (size_t)K * 8; o_t = jn_up16(o_c + (size_t)K * 4);
-        o_kof = jn_up16(o_t + (size_t)K + 2 * (size_t)(k - 1));
-        o_rec = o_kof + 16; o_codes = o_rec + jn_up16(sizeof(rb_extend_rec)); o_ob = o_codes + (size_t)words * 8;
-        o_oc = jn_up16(o_ob + (size_t)d + 2); o_walk = jn_up16(o_oc + ((size_t)d + 2) * 4);
-        bytes = jn_up16(o_walk + (lds ? 0 : ex_row_bytes(d)));
+        o_f = 0; o_r = o_f + (size_t)K * 8; o_c = o_r + (size_t)K * 8; o_t = up16(o_c + (size_t)K * 4);
+        o_kof = up16(o_t + (size_t)K + 2 * (size_t)(k - 1));
+        o_rec = o_kof + 16; o_codes = o_rec + up16(sizeof(rb_extend_rec)); o_ob = o_codes + (size_t)words * 8;
+        o_oc = up16(o_ob + (size_t)d + 2); o_walk = up16(o_oc + ((size_t)d + 2) * 4);
+        bytes = up16(o_walk + (lds ? 0 : ex_row_bytes(d)));
     }
 };
 
@@ -80,34 +78,13 @@ __device__ __forceinline__ bool jn_equal(const uint8_t *x, const uint8_t *y, int
     for (int q = 0; q < k && eq; ++q) eq = x[q] == y[q];
     return eq;
 }
-// the first (or last) position in [lo, hi) whose k-mer equals the k-mer at cand — forward hashes first, every hit confirmed on the k bases — or INT_MIN
-constexpr int JN_NOWHERE = INT32_MIN;
+// the first (or last) position in [lo, hi) whose k-mer equals the k-mer at cand (forward hash bf), or WAVE_NOWHERE: a path's entries go by their start in its text
 __device__ __forceinline__ int jn_find(const JnPath &p, int lo, int hi, uint64_t bf, const uint8_t *cand, int k, bool last, uint32_t lane) {
-    int res = JN_NOWHERE;
-    for (int base = lo; base < hi; base += 64) {
-        const int j = base + (int)lane;
-        bool hit = j < hi && p.F[j] == bf;
-        if (hit) hit = jn_equal(p.T + j, cand, k);
-        const unsigned long long m = __ballot(hit);
-        if (m) {
-            if (!last) return base + (int)__builtin_ctzll(m);
-            res = base + 63 - (int)__builtin_clzll(m);
-        }
-    }
-    return res;
+    return wave_find(lo, hi, k, [&](int j) { return p.F[j]; }, bf, [&](int j, int q) { return p.T[j + q]; }, [&](int q) { return cand[q]; }, last, lane);
 }
 // getMinimumKmerCoverage over positions [lo, hi), lo < hi
 __device__ __forceinline__ float jn_min(const float *c, int lo, int hi, uint32_t lane) {
-    float mn = INFINITY;
-    for (int j = lo + (int)lane; j < hi; j += 64) mn = fminf(mn, c[j]);
-    for (int s = 32; s > 0; s >>= 1) mn = fminf(mn, __shfl_xor(mn, s, 64));
-    return mn;
-}
-// SeqUtils.isHomopolymer(byte[]) :354-368
-__device__ __forceinline__ bool jn_homopolymer(const uint8_t *x, int k, uint32_t lane) {
-    bool same = true;
-    for (int q = (int)lane; q < k; q += 64) same = same && x[q] == x[0];
-    return __ballot(!same) == 0ull;
+    return wave_min(lo, hi, [&](int j) { return c[j]; }, lane);
 }
 
 struct JnResult { int why, index, left_keep, right_from; };   // a returned list: leftPath[0, left_keep) + the right text's k-mers from position right_from
@@ -119,7 +96,7 @@ __device__ __forceinline__ int jn_walk(const JnArgs &a, ExArgs &ea, uint8_t *xro
                        const uint8_t *left_last, float &thr, int &end, int &forks, JnResult &res, uint32_t lane) {
     const int k = a.k, d = a.d;
     const float g = a.grad, m = a.min_cov;
-    const ExDir dr{a.stranded, rw ? 1 : 0, (uint32_t)k, rw ? 3u : 0u, rw ? 0u : 3u};
+    const WaveDir<> dr = wave_dir(a.stranded, k, rw ? 1 : 0);
     const int max_size = a.bound + own.n;
     auto pos_of = [&](int i) { return rw ? own.nk0 - 1 - i : i; };
     // One k-mer offered to the path — `best` (ext false) or a k-mer of a step's result (ext true): base in, count cf.  0: added; 1: the walk ends
@@ -132,7 +109,7 @@ __device__ __forceinline__ int jn_walk(const JnArgs &a, ExArgs &ea, uint8_t *xro
         dr.step(rw ? lr : lf, rw ? lf : lr, own.T[rw ? lp + k - 1 : lp], in, nA, nB);
         const uint64_t bf = dr.fwd(nA, nB), br = rw ? nA : nB;
         if (lane == 0) own.T[rw ? np : np + k - 1] = (uint8_t)in;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         const uint8_t *cand = own.T + np;
         if (!rw) {
             const int j = jn_find(other, 0, other_n, bf, cand, k, false, lane);                                  // :946-967, :987-1008
@@ -141,22 +118,22 @@ __device__ __forceinline__ int jn_walk(const JnArgs &a, ExArgs &ea, uint8_t *xro
                 const float path_cov = jn_min(own.C, max(0, own.n - j), own.n, lane), dangling = jn_min(other.C, 0, j, lane);
                 if (dangling < path_cov) { res = JnResult{RB_JOIN_WHY_INSIDE_RIGHT, j, own.n, j}; return 2; }
             }
-            const bool homo = jn_homopolymer(cand, k, lane);
+            const bool homo = wave_all_equal(cand, k, lane);
             if (ext) { if (homo) { end = RB_JOIN_END_EXT_HOMOPOLYMER; return 1; } }                             // :1010
-            else if (homo || jn_find(own, 0, own.n, bf, cand, k, false, lane) != JN_NOWHERE) { end = RB_JOIN_END_LOOP; return 1; }   // :969
+            else if (homo || jn_find(own, 0, own.n, bf, cand, k, false, lane) != WAVE_NOWHERE) { end = RB_JOIN_END_LOOP; return 1; }   // :969
         } else {
             const int i = jn_find(other, 0, other_n, bf, cand, k, true, lane);                                  // :1068-1094, :1113-1128
-            if (i != JN_NOWHERE) {
+            if (i != WAVE_NOWHERE) {
                 if (!ext && jn_equal(cand, left_last, k)) res = JnResult{RB_JOIN_WHY_REACHED_LEFT, -1, -1, pos_of(own.n - 1)};
                 else res = JnResult{RB_JOIN_WHY_PATHS_MEET, i, i + 1, pos_of(own.n - 1)};
                 return 2;
             }
-            if (jn_homopolymer(cand, k, lane)) { end = ext ? RB_JOIN_END_EXT_HOMOPOLYMER : RB_JOIN_END_LOOP; return 3; }   // :1096, :1129
-            if (!ext && jn_find(own, pos_of(own.n - 1), own.nk0, bf, cand, k, false, lane) != JN_NOWHERE) { end = RB_JOIN_END_LOOP; return 3; }
+            if (wave_all_equal(cand, k, lane)) { end = ext ? RB_JOIN_END_EXT_HOMOPOLYMER : RB_JOIN_END_LOOP; return 3; }   // :1096, :1129
+            if (!ext && jn_find(own, pos_of(own.n - 1), own.nk0, bf, cand, k, false, lane) != WAVE_NOWHERE) { end = RB_JOIN_END_LOOP; return 3; }
         }
         if (lane == 0) { own.F[np] = bf; own.R[np] = br; own.C[np] = cf; }
         ++own.n;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         if (ext) {                                                                                              // :1018-1021, :1136-1139
             const float c = g * cf;
             if (c < thr) thr = fmaxf(c, m);
@@ -204,9 +181,9 @@ __device__ __forceinline__ int jn_walk(const JnArgs &a, ExArgs &ea, uint8_t *xro
             }
             if (lane == 0) reinterpret_cast<int64_t *>(row + lay.o_kof)[1] = nt;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         ex_one<false>(ea, 0, xrow, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
         const rb_extend_rec *er = reinterpret_cast<const rb_extend_rec *>(row + lay.o_rec);
         const int ne = er->outcome == RB_EXT_NONE ? 0 : er->out_len;
         if (ne == 0) { end = RB_JOIN_END_STEP_NONE; return 0; }                                                 // :980, :1108
@@ -241,26 +218,20 @@ __device__ __forceinline__ void jn_one(const JnArgs &a, ExArgs &ea, uint8_t *xro
     L.nk0 = L.n = nkL; L.cap = nkL + a.A;
     R.F = L.F + L.cap + a.A; R.R = L.R + L.cap + a.A; R.C = L.C + L.cap + a.A; R.T = L.T + (L.cap + k - 1) + a.A;
     R.nk0 = R.n = nkR; R.cap = nkR + a.A;
-    // the reads' letters as codes, a byte each; a letter outside ACGTU: the pair is not judged
-    bool bad = false;
-    for (int s = 0; s < 2; ++s) {
-        const uint32_t w0 = a.woff[2 * r + s];
-        const uint64_t *cw = a.codes + w0;
-        const uint32_t *vw = a.valid + w0;
-        uint8_t *t = s ? R.T : L.T;
-        for (int p = (int)lane; p < (s ? lenR : lenL); p += 64) {
-            bad = bad || !((vw[p >> 5] >> (p & 31)) & 1u);
-            t[p] = (uint8_t)((cw[p >> 5] >> (2 * (p & 31))) & 3u);
-        }
-    }
-    if (__ballot(bad)) {
+    // a letter outside ACGTU in either read: the pair is not judged; else the reads' letters as codes, a byte each
+    if (wave_bad_letter(a.valid + a.woff[2 * r], lenL, lane) || wave_bad_letter(a.valid + a.woff[2 * r + 1], lenR, lane)) {
         v.why = RB_JOIN_WHY_INVALID_LETTER;
         if (lane == 0) a.recs[r] = v;
         return;
     }
+    for (int s = 0; s < 2; ++s) {
+        const uint64_t *cw = a.codes + a.woff[2 * r + s];
+        uint8_t *t = s ? R.T : L.T;
+        for (int p = (int)lane; p < (s ? lenR : lenL); p += 64) t[p] = (uint8_t)((cw[p >> 5] >> (2 * (p & 31))) & 3u);
+    }
     for (int j = (int)lane; j < nkL; j += 64) { L.F[j] = a.F[k0 + j]; L.R[j] = a.R[k0 + j]; L.C[j] = a.cnt[k0 + j]; }
     for (int j = (int)lane; j < nkR; j += 64) { R.F[j] = a.F[k1 + j]; R.R[j] = a.R[k1 + j]; R.C[j] = a.cnt[k1 + j]; }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_fence();
 
     // the left walk, then — unless it returned — the right walk: one body, run twice
     JnResult res{RB_JOIN_WHY_EXHAUSTED, -1, 0, 0};
@@ -314,7 +285,7 @@ __global__ void __launch_bounds__(JN_TPB) k_join(JnArgs a) {
     if (lane == 0) reinterpret_cast<int64_t *>(row + lay.o_kof)[0] = 0;
     for (int64_t r = slot; r < a.pn; r += n_slots) {
         jn_one(a, ea, xrow, lay, row, r, lane);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        wave_fence();
     }
 }
 
@@ -362,41 +333,32 @@ void join_call(rb_graph *g, const char *lseq, const int64_t *lo, const char *rse
     HostPin pin_out(out_seq, (size_t)out_offsets[n]), pin_rec(recs, (size_t)n * sizeof(rb_join_rec));
     QueryLease q(g);
     hipStream_t s = q.c->st;
-    const bool lds = d <= EX_LDS_D, timing = g->prof_on;
-    Event ev[2];
-    if (timing) for (Event &e : ev) RB_HIP(hipEventCreate(&e.e));
-    double ms = 0;
-    int64_t launches = 0;
-    // piece by piece (rb_pieces.hpp), cut by the k-mers of both reads: b0 the piece's tables, b1 / b2 the getKmers hashes, b3 counts, records, the text
-    // out, the step's constants and the wavefronts' rows
-    const std::vector<int64_t> cut = piece_cuts([&](int64_t i) { return ko[(size_t)(2 * i)]; }, n, query_piece_max((int64_t)16 << 20));
-    std::vector<int64_t> tab;
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        const int64_t ra = cut[c], rb_ = cut[c + 1], pn = rb_ - ra, pt = ko[(size_t)(2 * rb_)] - ko[(size_t)(2 * ra)];
+    const bool lds = d <= EX_LDS_D;
+    // what no kernel touches: the pairs of pieces without a k-mer (a pair without one comes back like this from the kernel too)
+    for (int64_t i = 0; i < n; ++i) {
+        if (ko[(size_t)(2 * i + 2)] > ko[(size_t)(2 * i)]) continue;
+        rb_join_rec v;
+        memset(&v, 0, sizeof v);
+        v.outcome = RB_JOIN_NOT_JUDGED; v.why = RB_JOIN_WHY_SHORT; v.index = -1;
+        recs[i] = v;
+        memset(out_seq + out_offsets[i], 0, (size_t)(out_offsets[i + 1] - out_offsets[i]));
+    }
+    // piece by piece (rb_pieces.hpp), a pair a record, cut by the k-mers of both reads: b0 the piece's tables, b1 / b2 the getKmers hashes, b3 counts,
+    // records, the text out, the step's constants and the wavefronts' rows; with profiling on the kernels of every piece are timed: entry "join"
+    std::vector<int64_t> oof;
+    for_each_host_piece(g, s, text.data(), off.data(), ko.data(), n, "join", [&](HostPiece &pc) {
+        const int64_t ra = pc.ra, rb_ = pc.rb, pn = pc.pn, pt = pc.pt;
         const int64_t ot = out_offsets[rb_] - out_offsets[ra];
-        if (pt == 0) {                                        // no read of the piece has a k-mer: nothing to upload
-            rb_join_rec v;
-            memset(&v, 0, sizeof v);
-            v.outcome = RB_JOIN_NOT_JUDGED; v.why = RB_JOIN_WHY_SHORT; v.index = -1;
-            for (int64_t i = ra; i < rb_; ++i) recs[i] = v;
-            memset(out_seq + out_offsets[ra], 0, (size_t)ot);
-            continue;
-        }
         int64_t rowK = 0;
-        tab.assign((size_t)(3 * pn + 2), 0);
-        for (int64_t i = 0; i <= 2 * pn; ++i) tab[(size_t)i] = ko[(size_t)(2 * ra + i)] - ko[(size_t)(2 * ra)];
-        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)(2 * pn + 1 + i)] = out_offsets[ra + i] - out_offsets[ra];
+        oof.resize((size_t)pn + 1);
+        for (int64_t i = 0; i <= pn; ++i) oof[(size_t)i] = out_offsets[ra + i] - out_offsets[ra];
         for (int64_t i = ra; i < rb_; ++i) rowK = std::max(rowK, cap_kmers(i));
         const JnLayout lay(rowK, k, d, lds);
         const int64_t rows = std::min(std::min(pn, JN_MAX_ROWS), std::max(JN_MIN_ROWS, (int64_t)(JN_ROWS_BYTES / lay.bytes)));
         const unsigned blocks = blocks_for(rows, JN_WAVES);
         const size_t n_ones = (size_t)lay.words * 2 + 2;
-        const size_t o_rec = jn_up16((size_t)pt * 4), o_txt = o_rec + (size_t)pn * sizeof(rb_join_rec), o_const = jn_up16(o_txt + (size_t)ot),
-                     o_rows = jn_up16(o_const + 16 + n_ones * 4);
-        BatchPtr b = upload_text_batch(g->p.device, text.data(), off.data(), 2 * ra, 2 * pn, s);
-        q.c->b0.reserve(tab.size() * 8);
-        q.c->b1.reserve((size_t)pt * 8);
-        q.c->b2.reserve((size_t)pt * 8);
+        const size_t o_rec = up16((size_t)pt * 4), o_txt = o_rec + (size_t)pn * sizeof(rb_join_rec), o_const = up16(o_txt + (size_t)ot),
+                     o_rows = up16(o_const + 16 + n_ones * 4);
         q.c->b3.reserve(o_rows + (size_t)blocks * JN_WAVES * lay.bytes + 16);
         uint8_t *base3 = q.c->b3.as<uint8_t>();
         JnArgs a;
@@ -404,37 +366,25 @@ void join_call(rb_graph *g, const char *lseq, const int64_t *lo, const char *rse
         a.pf = PairView{g->rpk.bits, g->rpk.mod, g->rpk.num_hash, kmul_of(k)};
         a.stranded = (int)g->stranded; a.k = k; a.d = d; a.bound = bound; a.A = A;
         a.grad = grad; a.min_cov = min_cov;
-        a.pn = pn; a.rowK = rowK;
-        a.kof = q.c->b0.as<int64_t>();
-        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-        a.cnt = reinterpret_cast<float *>(base3);
-        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
-        a.oof = a.kof + 2 * pn + 1;
+        a.rowK = rowK;
         a.out = base3 + o_txt;
         a.recs = reinterpret_cast<rb_join_rec *>(base3 + o_rec);
         a.rows = base3 + o_rows;
         a.floor1 = reinterpret_cast<float *>(base3 + o_const);
         a.zero = reinterpret_cast<uint32_t *>(base3 + o_const + 4);
         a.ones = reinterpret_cast<uint32_t *>(base3 + o_const + 16);
-        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
         RB_HIP(hipMemsetAsync(base3 + o_txt, 0, o_const + 16 - o_txt, s));          // (what no pair writes comes back as zeros, whatever the cuts)
         RB_HIP(hipMemsetAsync(base3 + o_const + 16, 0xFF, n_ones * 4, s));
         RB_HIP(hipMemcpyAsync(base3 + o_const, &min_cov, 4, hipMemcpyHostToDevice, s));
-        if (timing) RB_HIP(hipEventRecord(ev[0], s));
-        rb::launch_get_kmers(g, b.get(), a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        PieceRows(g, *q.c, pc, oof.data(), oof.size()).into(a);
+        a.oof = a.kof + 2 * pn + 1;
         if (lds) hipLaunchKernelGGL((k_join<true>), dim3(blocks), dim3(JN_TPB), 0, s, a);
         else hipLaunchKernelGGL((k_join<false>), dim3(blocks), dim3(JN_TPB), 0, s, a);
         RB_HIP(hipGetLastError());
-        if (timing) RB_HIP(hipEventRecord(ev[1], s));
+        pc.kernels_end();
         RB_HIP(hipMemcpyAsync(recs + ra, a.recs, (size_t)pn * sizeof(rb_join_rec), hipMemcpyDeviceToHost, s));
         RB_HIP(hipMemcpyAsync(out_seq + out_offsets[ra], a.out, (size_t)ot, hipMemcpyDeviceToHost, s));
-        RB_HIP(hipStreamSynchronize(s));                    // the piece's results are on the host: its tables, batch and scratch may go
-        if (timing) { float t = 0; RB_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); ms += t; ++launches; }
-    }
-    if (launches) {
-        std::lock_guard<std::mutex> lk(g->qm);              // (queries share the handle: the profile table is written under the context lock)
-        g->prof_add("join", ms, launches);
-    }
+    }, 2);
 }
 
 }  // namespace

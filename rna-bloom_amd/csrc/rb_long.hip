@@ -20,7 +20,7 @@
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
 #include "rb_align.hpp"
-#include "rb_extend_step.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -41,10 +41,7 @@ enum { C_SNV_REPLACED = 0, C_SNV_KEPT, C_PATH_NONE, C_ZERO_ACCEPTED, C_ZERO_KEPT
 
 static_assert(sizeof(rb_long_rec) == 64, "rb_long_rec is 16 ints");
 
-#define LW_FENCE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
 #define LW_FENCE_LDS() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup")
-
-__host__ __device__ inline size_t lw_up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 struct LwSeq { int64_t toff, koff; int32_t len, nk; };                       // a sequence in the current text / count buffers
 struct LwWin { int64_t toff, koff, ooff; int32_t n, cap; };                  // a window: its first letter, its first count, its slot (bytes into the slots), its k-mers, the slot's k-mers
@@ -57,9 +54,9 @@ struct LwOut { int32_t out_len, trim_begin, trim_end, flags, trimmed; };
 struct LwLayout {
     size_t o_c2, o_tl, o_tr, o_hl, o_hr, o_cl, o_cr, o_lev, bytes;
     __host__ __device__ LwLayout(int64_t cap, int64_t B, int64_t W, int k) {
-        o_c2 = 0; o_tl = lw_up16(o_c2 + (size_t)cap); o_tr = lw_up16(o_tl + (size_t)(k + B + 1)); o_hl = lw_up16(o_tr + (size_t)(k + B + 1));
-        o_hr = o_hl + (size_t)B * 8; o_cl = o_hr + (size_t)B * 8; o_cr = lw_up16(o_cl + (size_t)B); o_lev = lw_up16(o_cr + (size_t)B);
-        bytes = lw_up16(o_lev + (size_t)(W + k) * 4);
+        o_c2 = 0; o_tl = up16(o_c2 + (size_t)cap); o_tr = up16(o_tl + (size_t)(k + B + 1)); o_hl = up16(o_tr + (size_t)(k + B + 1));
+        o_hr = o_hl + (size_t)B * 8; o_cl = o_hr + (size_t)B * 8; o_cr = up16(o_cl + (size_t)B); o_lev = up16(o_cr + (size_t)B);
+        bytes = up16(o_lev + (size_t)(W + k) * 4);
     }
 };
 
@@ -75,11 +72,6 @@ struct LwArgs {
     uint8_t *rows;
     int64_t capmax, B, W;
 };
-
-__device__ __forceinline__ uint64_t lw_shfl64(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // the largest count code among the lanes' and the lowest lane that holds it, as code * 64 + (63 - lane); all lanes get it
 __device__ __forceinline__ uint32_t lw_max_key(uint32_t code, uint32_t lane) {
@@ -140,28 +132,17 @@ __global__ void __launch_bounds__(LW_TPB) k_long_solid(const LwSeq *__restrict__
 
 // the first index in [from, n) whose k-mer is bad (count < T) / good, else n
 __device__ __forceinline__ int lw_next(const uint8_t *c, int from, int n, float T, bool want_bad, uint32_t lane) {
-    for (int base = from; base < n; base += 64) {
-        const int j = base + (int)lane;
-        const unsigned long long m = __ballot(j < n && ((count_code_value(c[j]) < T) == want_bad));
-        if (m) return base + (int)__builtin_ctzll(m);
-    }
-    return n;
+    return wave_first(from, n, [&](int j) { return (count_code_value(c[j]) < T) == want_bad; }, lane);
 }
 
 // a walk's rows: T the k codes of its first k-mer in walking order and a code per k-mer added, H / C the forward hash and count code of those
 struct LwRow { uint8_t *T; uint64_t *H; uint8_t *C; };
 
-// HashSet.contains / indexOf: the entry of the n a walk added that equals the candidate (k codes at cand, forward hash fh), else -1.  A lane per
-// entry compares the hashes; an equal hash is confirmed on the bases.  rev: the row's walk runs the other way.
+// HashSet.contains / indexOf: the entry of the n a walk added that equals the candidate (k codes at cand, forward hash fh), else WAVE_NOWHERE — entry j
+// is the k codes at row.T + j + 1.  rev: the row's walk runs the other way.
 __device__ __forceinline__ int lw_find(const LwRow &row, int n, const uint8_t *cand, uint64_t fh, bool rev, int k, uint32_t lane) {
-    for (int base = 0; base < n; base += 64) {
-        const int j = base + (int)lane;
-        bool hit = j < n && row.H[j] == fh;
-        if (hit) for (int q = 0; q < k && hit; ++q) hit = row.T[j + 1 + q] == (rev ? cand[k - 1 - q] : cand[q]);
-        const unsigned long long m = __ballot(hit);
-        if (m) return base + (int)__builtin_ctzll(m);
-    }
-    return -1;
+    return wave_find(0, n, k, [&](int j) { return row.H[j]; }, fh, [&](int j, int q) { return row.T[j + 1 + q]; },
+                     [&](int q) { return rev ? cand[k - 1 - q] : cand[q]; }, false, lane);
 }
 
 // One walk of getMaxCoveragePath (:1604-1623 to the right, :1630-1672 back): up to `bound` steps of Kmer.getMaxCovSuccessor / getMaxCovPredecessor
@@ -170,7 +151,7 @@ __device__ __forceinline__ int lw_find(const LwRow &row, int n, const uint8_t *c
 // bound; 4: (other != nullptr) it is entry `met` of the other walk — tested after 2, as the reference tests it.  n: the k-mers added.
 enum { LW_END_NONE = 0, LW_END_TARGET = 1, LW_END_LOOP = 2, LW_END_BOUND = 3, LW_END_MET = 4 };
 template <class TGT>
-__device__ int lw_walk(const LwArgs &a, const ExDir &dr, const LwRow &own, int bound, TGT tgt, const LwRow *other, int other_n, int &n, int &met,
+__device__ int lw_walk(const LwArgs &a, const WaveDir<> &dr, const LwRow &own, int bound, TGT tgt, const LwRow *other, int other_n, int &n, int &met,
                        uint32_t lane) {
     const int k = a.k;
     uint64_t A = 0, B = 0;
@@ -194,9 +175,9 @@ __device__ int lw_walk(const LwArgs &a, const ExDir &dr, const LwRow &own, int b
             if (count_code_value(cb) >= a.min_cov && (bi < 0 || cb > bcode)) { bi = b; bcode = cb; }
         }
         if (bi < 0) { n = len; return LW_END_NONE; }
-        nA = lw_shfl64(nA, bi); nB = lw_shfl64(nB, bi);
+        nA = wave_shfl64(nA, bi); nB = wave_shfl64(nB, bi);
         if (lane == 0) own.T[len + k] = (uint8_t)bi;
-        LW_FENCE();
+        wave_fence();
         const uint8_t *cand = own.T + len + 1;
         bool ne = false;
         for (int q = (int)lane; q < k; q += 64) ne = ne || cand[q] != tgt(q);
@@ -210,7 +191,7 @@ __device__ int lw_walk(const LwArgs &a, const ExDir &dr, const LwRow &own, int b
         if (lane == 0) { own.H[len] = fh; own.C[len] = (uint8_t)bcode; }
         A = nA; B = nB;
         ++len;
-        LW_FENCE();
+        wave_fence();
     }
     n = len;
     return LW_END_BOUND;
@@ -283,7 +264,7 @@ __device__ void lw_window(const LwArgs &a, int64_t w, uint8_t *row, int *hist, u
         if (m + cnt > cap) { outgrown = true; return; }
         for (int x = (int)lane; x < cnt; x += 64) { out[m + x] = tx[from + x + k - 1]; C2[m + x] = c[from + x]; }
         m += cnt;
-        LW_FENCE();
+        wave_fence();
     };
     int i = 0, rs = 0;                                                          // the cursor; the first k-mer of the open run (numBadKmersSince = i - rs)
     while (i < n && !outgrown) {
@@ -340,7 +321,7 @@ __device__ void lw_window(const LwArgs &a, int64_t w, uint8_t *row, int *hist, u
                 if (m + k > cap) { outgrown = true; break; }
                 for (int x = (int)lane; x < k; x += 64) { out[m + x] = x == 0 ? code_letter((uint32_t)besta) : tx[e + x - 1]; C2[m + x] = snv[besta][x]; }
                 m += k;
-                LW_FENCE();
+                wave_fence();
                 corrected = true;
                 ++ctr[C_SNV_REPLACED];
             } else { append_orig(rs, e); ++ctr[C_SNV_KEPT]; }
@@ -374,12 +355,12 @@ __device__ void lw_window(const LwArgs &a, int64_t w, uint8_t *row, int *hist, u
             const int bound = run + a.maxld;
             // L = slot[bl .. bl + k), R = tx[br .. br + k): both have a count above 0 and so letters of ACGTU only
             for (int q = (int)lane; q < k; q += 64) { WL.T[q] = (uint8_t)(letter_code(slot[bl + q]) & 3u); WR.T[q] = (uint8_t)(letter_code(tx[br + k - 1 - q]) & 3u); }
-            LW_FENCE();
+            wave_fence();
             // form 0: null; 1: the walk to the right arrived, the path is its nl k-mers; 2: the walk back met entry idx of it, the path is entries
             // 0 .. idx and the nr k-mers of the walk back; 3: the walk back arrived, the path is its nr k-mers
             int form = 0, nl = 0, nr = 0, idx = 0, plen = 0;
             {
-                const ExDir dl{a.stranded, 0, (uint32_t)k, 0u, 3u}, drr{a.stranded, 1, (uint32_t)k, 3u, 0u};
+                const WaveDir<> dl = wave_dir(a.stranded, k, 0), drr = wave_dir(a.stranded, k, 1);
                 int met = -1;
                 const int endl = lw_walk(a, dl, WL, bound, [&](int q) -> uint8_t { return WR.T[k - 1 - q]; }, nullptr, 0, nl, met, lane);
                 if (endl == LW_END_TARGET) { form = 1; plen = nl; }
@@ -419,7 +400,7 @@ __device__ void lw_window(const LwArgs &a, int64_t w, uint8_t *row, int *hist, u
                                     return code_letter(form == 1 ? WL.T[1 + x] : form == 2 ? (x < idx + k ? WL.T[1 + x] : WR.T[mm - (x - (idx + k))]) : WR.T[mm + k - x]);
                                 };
                                 const int d = ce_distance(s, slen, [&](int x) -> uint32_t { return tx[t0 + x]; }, tlen, lev, lane);
-                                LW_FENCE();
+                                wave_fence();
                                 if (ce_identity(d, slen, tlen) >= a.pid) { accept = true; ++ctr[C_IDENTITY]; }
                             }
                         }
@@ -432,7 +413,7 @@ __device__ void lw_window(const LwArgs &a, int64_t w, uint8_t *row, int *hist, u
                 if (m + plen > cap) { outgrown = true; break; }
                 for (int x = (int)lane; x < plen; x += 64) { out[m + x] = p_letter(x); C2[m + x] = (uint8_t)p_code(x); }
                 m += plen;
-                LW_FENCE();
+                wave_fence();
                 corrected = true;
                 nxt = br;
             } else append_orig(rs, e);
@@ -455,7 +436,7 @@ __global__ void __launch_bounds__(LW_TPB) k_long_window(LwArgs a, size_t row_byt
     uint8_t *row = a.rows + (size_t)slot * row_bytes;
     for (int64_t w = slot; w < a.nwin; w += n_slots) {
         lw_window(a, w, row, s_hist[wv], s_snv[wv], lane);
-        LW_FENCE();
+        wave_fence();
     }
 }
 
@@ -567,11 +548,6 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
     RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
     hipStream_t s = q.c->st;
     const FilterView fv = g->view(0, 0);
-    const bool timing = g->prof_on;
-    Event ev[2];
-    if (timing) for (Event &e : ev) RB_HIP(hipEventCreate(&e.e));
-    double ms = 0;
-    int64_t launches = 0;
     // The call's own buffers (a context's four are one piece's tables in the other calls; here every pass lays out anew): text and counts twice
     // — a pass reads one pair and writes the other —, the tables of a pass, the windows' slots and results, the wavefronts' rows, the final texts
     // and records.  A buffer that has to grow is freed first, and hipFree waits for the device, so no kernel in flight loses what it reads.
@@ -584,10 +560,10 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
     std::vector<int32_t> res, nsolid, wfirst;
     std::vector<LwOut> outs;
     std::vector<uint8_t> tab;
-    const std::vector<int64_t> cut = piece_cuts([&](int64_t i) { return ko[(size_t)i]; }, n, query_piece_max((int64_t)4 << 20));
-    for (size_t cc = 0; cc + 1 < cut.size(); ++cc) {
-        const int64_t ra = cut[cc], rb_ = cut[cc + 1], pn = rb_ - ra, pt = ko[(size_t)rb_] - ko[(size_t)ra];
-        if (pt == 0) continue;
+    // piece by piece (rb_pieces.hpp), 4 M k-mers a piece; with profiling on every piece's passes are timed as one interval: entry "correct_long"
+    for_each_piece(g, s, [&](int64_t i) { return ko[(size_t)i]; }, n, (int64_t)4 << 20, "correct_long", [&](Piece &pc) {
+        const int64_t ra = pc.ra, rb_ = pc.rb, pn = pc.pn, pt = ko[(size_t)rb_] - ko[(size_t)ra];
+        if (pt == 0) return;
         const int64_t tb = offsets[rb_] - offsets[ra], ob = out_offsets[rb_] - out_offsets[ra];
         b_txt[0].reserve((size_t)tb + 16); b_cnt[0].reserve((size_t)pt + 16);
         b_fin.reserve((size_t)ob + 16); b_out.reserve((size_t)pn * sizeof(LwOut) + 16);
@@ -595,8 +571,8 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
         int cur = 0;
         // the tables of a step go up in one copy: tab is laid out on the host, b_tab holds it
         auto upload = [&](const void *a0, size_t n0, const void *a1, size_t n1, const void *a2, size_t n2, size_t &o1, size_t &o2) {
-            o1 = lw_up16(n0); o2 = lw_up16(o1 + n1);
-            tab.assign(lw_up16(o2 + n2) + 16, 0);
+            o1 = up16(n0); o2 = up16(o1 + n1);
+            tab.assign(up16(o2 + n2) + 16, 0);
             if (n0) memcpy(tab.data(), a0, n0);
             if (n1) memcpy(tab.data() + o1, a1, n1);
             if (n2) memcpy(tab.data() + o2, a2, n2);
@@ -615,7 +591,7 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
         }
         RB_HIP(hipMemcpyAsync(b_txt[0].p, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
         upload(live.data(), live.size() * sizeof(LwSeq), nullptr, 0, nullptr, 0, o1, o2);
-        if (timing) RB_HIP(hipEventRecord(ev[0], s));
+        pc.kernels_begin();
         int64_t nl = (int64_t)live.size();
         hipLaunchKernelGGL(k_long_profile, dim3(blocks_for(nl, LW_WAVES)), dim3(LW_TPB), 0, s, fv, (int)g->stranded, k, reinterpret_cast<const LwSeq *>(b_tab.p), nl,
                            b_txt[0].as<uint8_t>(), b_cnt[0].as<uint8_t>());
@@ -666,7 +642,7 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
                 cut_windows(sq.nk, window, to_shift, [&](int64_t a, int64_t e) {
                     const int64_t len = e - a, cap = len + (len / 2) * grow;
                     wins.push_back(LwWin{sq.toff + a, sq.koff + a, slot_bytes, (int32_t)len, (int32_t)cap});
-                    slot_bytes += lw_up16((size_t)(cap + k - 1));
+                    slot_bytes += up16((size_t)(cap + k - 1));
                     W = std::max(W, len); capmax = std::max(capmax, cap);
                 });
                 wfirst[(size_t)li + 1] = (int32_t)wins.size();
@@ -752,13 +728,12 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
             for (size_t li = 0; li < live.size(); ++li) leaving[li] = (int64_t)li;
             finish(leaving, false);
         }
-        if (timing) RB_HIP(hipEventRecord(ev[1], s));
+        pc.kernels_end();
         // only the final copy crosses to the host
         std::vector<uint8_t> fin_host((size_t)ob);
         RB_HIP(hipMemcpyAsync(outs.data(), b_out.p, (size_t)pn * sizeof(LwOut), hipMemcpyDeviceToHost, s));
         if (ob) RB_HIP(hipMemcpyAsync(fin_host.data(), b_fin.p, (size_t)ob, hipMemcpyDeviceToHost, s));
-        RB_HIP(hipStreamSynchronize(s));
-        if (timing) { float t = 0; RB_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); ms += t; ++launches; }
+        pc.finish();                                        // (outs and fin_host are on the host)
         for (int64_t i = 0; i < pn; ++i) {
             rb_long_rec &rc = recs[ra + i];
             if (rc.status == RB_LONG_NO_KMER) continue;
@@ -768,11 +743,7 @@ void long_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
             if (!(o.flags & RB_LONG_OVERFLOW) && o.out_len > 0)
                 memcpy(out_seq + out_offsets[ra + i], fin_host.data() + (out_offsets[ra + i] - out_offsets[ra]), (size_t)o.out_len);
         }
-    }
-    if (launches) {
-        std::lock_guard<std::mutex> lk(g->qm);
-        g->prof_add("correct_long", ms, launches);
-    }
+    });
 }
 
 }  // namespace

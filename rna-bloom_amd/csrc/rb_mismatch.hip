@@ -13,6 +13,7 @@
 
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -206,8 +207,6 @@ __global__ void __launch_bounds__(MM_TPB) k_mismatch(FilterView fv, int stranded
     if (lane == 0) n_fixed[r] = nfix;
 }
 
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
 int rb::mismatch_lds_row() { return MM_LDS_ROW; }
@@ -258,32 +257,24 @@ int rb_graph_correct_mismatches(rb_graph *g, const char *seq, const int64_t *off
         std::vector<int64_t> tab;
         for_each_host_piece(g, s, seq, offsets, ko.data(), n, "mismatches", [&](HostPiece &pc) {
             const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt, tb = offsets[pc.rb] - offsets[ra];
-            // the piece's table: k-mer offsets [pn + 1], text offsets [pn + 1], the sequences whose code row does not fit LDS
-            tab.assign((size_t)(2 * pn + 2), 0);
-            for (int64_t i = 0; i <= pn; ++i) {
-                tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-                tab[(size_t)(pn + 1 + i)] = offsets[ra + i] - offsets[ra];
-            }
+            // the piece's table behind its k-mer offsets: text offsets [pn + 1], the sequences whose code row does not fit LDS
+            tab.assign((size_t)pn + 1, 0);
+            for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = offsets[ra + i] - offsets[ra];
             for (int64_t i = 0; i < pn; ++i)
-                if (tab[(size_t)i + 1] - tab[(size_t)i] > MM_LDS_ROW) tab.push_back(i);
-            const int64_t nlong = (int64_t)tab.size() - (2 * pn + 2);
-            const rb_batch *b = pc.batch();
+                if (ko[(size_t)(ra + i + 1)] - ko[(size_t)(ra + i)] > MM_LDS_ROW) tab.push_back(i);
+            const int64_t nlong = (int64_t)tab.size() - (pn + 1);
             // b3: counts [pt] floats, thresholds [pn], replacements [pn], text [tb], code rows of the long sequences [pt]
             const size_t o_thr = (size_t)pt * 4, o_nf = o_thr + (size_t)pn * 4, o_txt = o_nf + (size_t)pn * 4, o_row = up16(o_txt + (size_t)tb);
-            q.c->b0.reserve(tab.size() * 8);
-            q.c->b1.reserve((size_t)pt * 8);
-            q.c->b2.reserve((size_t)pt * 8);
             q.c->b3.reserve(o_row + (nlong ? (size_t)pt : 0) + 16);
-            const int64_t *dkof = q.c->b0.as<int64_t>(), *dtof = dkof + pn + 1, *dids = dtof + pn + 1;
             uint8_t *base3 = q.c->b3.as<uint8_t>();
             float *dcnt = reinterpret_cast<float *>(base3), *dthr = reinterpret_cast<float *>(base3 + o_thr);
             int32_t *dnf = reinterpret_cast<int32_t *>(base3 + o_nf);
             uint8_t *dtxt = base3 + o_txt, *drow = base3 + o_row;
-            RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
             RB_HIP(hipMemcpyAsync(dthr, cov_threshold + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
             RB_HIP(hipMemcpyAsync(dtxt, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
-            pc.kernels_begin();
-            rb::launch_get_kmers(g, b, dkof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), dcnt, s);
+            const PieceRows rows(g, *q.c, pc, tab.data(), tab.size());
+            const rb_batch *b = pc.batch();
+            const int64_t *dkof = rows.kof, *dtof = dkof + pn + 1, *dids = dtof + pn + 1;
             rb::launch_mismatch(g, min_kmer_cov, pn, dids, nlong, dkof, nullptr, dtof, b->woff, b->valid, dtxt, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(),
                                 dcnt, drow, dthr, dnf, counts ? 1 : 0, s);
             pc.kernels_end();

@@ -13,6 +13,7 @@
 
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -38,8 +39,6 @@ __device__ __forceinline__ int ov_nt_index(uint32_t ch) {
         default: return -1;
     }
 }
-// Math.round(float): floor(x + 1/2), exact in double for every float rounded here
-__device__ __forceinline__ int ov_java_round(float x) { return (int)floor((double)x + 0.5); }
 
 // two reads, and the text overlapped = a + b[o ..] they spell when the last o bytes of a are the first o of b
 struct OvText {
@@ -113,7 +112,7 @@ template <typename T> __device__ bool ov_any_singleton(const FilterView &fv, int
 // counter of base / dinucleotide / trinucleotide c, a signed byte as in the reference (it wraps at 128), and a ballot sees a threshold reached.
 __device__ int ov_is_repeat(const uint8_t *b, int n, uint32_t lane) {
     const float thr = 0.9f;
-    const int t[3] = {ov_java_round((float)n * thr), ov_java_round((float)(n / 2) * thr), ov_java_round((float)(n / 3) * thr)};
+    const int t[3] = {(int)java_round((float)n * thr), (int)java_round((float)(n / 2) * thr), (int)java_round((float)(n / 3) * thr)};
     for (int m = 1; m <= 3; ++m)                         // m letters a unit
         for (int start = 0; start < m; ++start) {
             int8_t cnt = 0;
@@ -278,16 +277,11 @@ int rb_graph_overlap_pairs(rb_graph *g, const char *lseq, const int64_t *loffset
         QueryLease q(g);
         hipStream_t s = q.c->st;
         const FilterView fv = g->view(0, 0);
-        const bool timing = g->prof_on;
-        Event ev[2];
-        if (timing) for (Event &e : ev) RB_HIP(hipEventCreate(&e.e));
-        double ms = 0;
-        int64_t launches = 0;
-        // piece by piece (rb_pieces.hpp), cut by the letters of both reads: b0 the piece's table, b1 / b2 the reads' text, b3 records and text out
-        const std::vector<int64_t> cut = piece_cuts(cap, n, query_piece_max((int64_t)64 << 20));
+        // piece by piece (rb_pieces.hpp), cut by the letters of both reads, 64 M a piece: b0 the piece's table, b1 / b2 the reads' text, b3 records
+        // and text out; with profiling on the kernels of every piece are timed: entry "overlap"
         std::vector<int64_t> tab;
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const int64_t ra = cut[c], rb_ = cut[c + 1], pn = rb_ - ra;
+        for_each_piece(g, s, cap, n, (int64_t)64 << 20, "overlap", [&](Piece &pc) {
+            const int64_t ra = pc.ra, rb_ = pc.rb, pn = pc.pn;
             const int64_t lt = loffsets[rb_] - loffsets[ra], rt = roffsets[rb_] - roffsets[ra];
             // the piece's table: left offsets [pn + 1], right offsets [pn + 1], the pairs that do not fit a row of LDS
             tab.assign((size_t)(2 * pn + 2), 0);
@@ -310,7 +304,7 @@ int rb_graph_overlap_pairs(rb_graph *g, const char *lseq, const int64_t *loffset
             if (lt) RB_HIP(hipMemcpyAsync(q.c->b1.p, lseq + loffsets[ra], (size_t)lt, hipMemcpyHostToDevice, s));
             if (rt) RB_HIP(hipMemcpyAsync(q.c->b2.p, rseq + roffsets[ra], (size_t)rt, hipMemcpyHostToDevice, s));
             if (lt + rt) RB_HIP(hipMemsetAsync(dout, 0, (size_t)(lt + rt), s));     // (what no pair writes comes back as zeros, whatever the cuts)
-            if (timing) RB_HIP(hipEventRecord(ev[0], s));
+            pc.kernels_begin();
             hipLaunchKernelGGL((k_overlap<true>), dim3(blocks_for(pn, OV_WAVES)), dim3(OV_TPB), 0, s, fv, (int)g->stranded, g->k, min_overlap, min_kmer_cov,
                                pn, (const int64_t *)nullptr, (int64_t)0, dlof, drof, q.c->b1.as<uint8_t>(), q.c->b2.as<uint8_t>(), dout, drec);
             RB_HIP(hipGetLastError());
@@ -319,16 +313,10 @@ int rb_graph_overlap_pairs(rb_graph *g, const char *lseq, const int64_t *loffset
                                    min_kmer_cov, pn, dids, nlong, dlof, drof, q.c->b1.as<uint8_t>(), q.c->b2.as<uint8_t>(), dout, drec);
                 RB_HIP(hipGetLastError());
             }
-            if (timing) RB_HIP(hipEventRecord(ev[1], s));
+            pc.kernels_end();
             RB_HIP(hipMemcpyAsync(recs + ra, drec, (size_t)pn * sizeof(rb_overlap_rec), hipMemcpyDeviceToHost, s));
             if (lt + rt) RB_HIP(hipMemcpyAsync(out_seq + out_offsets[ra], dout, (size_t)(lt + rt), hipMemcpyDeviceToHost, s));
-            RB_HIP(hipStreamSynchronize(s));                // the piece's results are on the host: its table and scratch may go
-            if (timing) { float t = 0; RB_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); ms += t; ++launches; }
-        }
-        if (launches) {
-            std::lock_guard<std::mutex> lk(g->qm);          // (queries share the handle: the profile table is written under the context lock)
-            g->prof_add("overlap", ms, launches);
-        }
+        });
     });
 }
 }  // extern "C"

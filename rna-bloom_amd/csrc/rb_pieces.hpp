@@ -1,7 +1,8 @@
 // rb_pieces.hpp — query calls that work piece by piece so that their device scratch stays bounded whatever the caller asks for: how many
-// k-mers a piece may hold (RB_QUERY_PIECE), where the pieces are cut, and — for the calls whose sequences are host text (rb_graph_kmers,
-// rb_graph_paired_kmer_segments, rb_graph_correct_mismatches) — the loop over the pieces: upload of a piece's text as a packed batch, the
-// profile bracket around its kernels, the wait at its end (DESIGN.md §5 "Piece by piece").  Host code only.
+// k-mers a piece may hold (RB_QUERY_PIECE), where the pieces are cut, and the loop over the pieces in two layers: for_each_piece — the cut, the
+// profile bracket around a piece's kernels, the wait at its end, the profile entry — and on top of it, for the calls whose records are host
+// text, for_each_host_piece with the piece's text as a lazily uploaded packed batch and PieceRows, the piece's getKmers rows (DESIGN.md §5
+// "Piece by piece").  Host code only.
 #pragma once
 #include "rb_pipeline.hpp"
 
@@ -61,72 +62,154 @@ inline BatchPtr upload_text_batch(int device, const char *seq, const int64_t *of
     } catch (...) { ascii_batch_abort(up); throw; }
 }
 
-// The piece for_each_host_piece hands to its body: sequences [ra, rb) of the call, pn of them with pt > 0 k-mers together.
-class HostPiece {
+// The piece for_each_piece hands to its body: records [ra, rb) of the call, pn of them.  The body sizes its scratch, uploads what it reads,
+// launches its kernels between kernels_begin() and kernels_end() and enqueues its copies back, all on the query stream of a leased context.
+class Piece {
 public:
-    int64_t ra = 0, rb = 0, pn = 0, pt = 0;
-    // the piece's text as a packed batch, uploaded at the first call and kept until the piece is over.  A body asks for it BEFORE it
-    // enqueues anything on the stream: a body that finds nothing to do for a piece returns without asking, nothing is uploaded, and
-    // finish() has nothing to wait for.
-    const rb_batch *batch() {
-        if (!b) b = upload_text_batch(g->p.device, seq, offsets, ra, pn, s);
-        return b.get();
-    }
+    int64_t ra = 0, rb = 0, pn = 0;
     // around the piece's kernels — after its table and text uploads are enqueued, before its copies back: the interval the profile entry sums
-    void kernels_begin() { if (timing) RB_HIP(hipEventRecord(ev[0], s)); }
+    void kernels_begin() { busy = true; if (timing) RB_HIP(hipEventRecord(ev[0], s)); }
     void kernels_end() { if (timing) { RB_HIP(hipEventRecord(ev[1], s)); timed = true; } }
-    // wait for what a piece that asked for its batch enqueued: its results are on the host, its table and batch may go.  The loop does
-    // it after the body; a body that has to look at a result before the next piece calls it itself.
+    // wait for what the piece enqueued: its results are on the host, its tables and scratch may go.  The loop does it after the body; a body
+    // that has to look at a result before the next piece calls it itself.  A body that found nothing to do — it never came to
+    // kernels_begin() — has nothing to wait for.
     void finish() {
-        if (!b || done) return;
+        if (!busy || done) return;
         done = true;
         RB_HIP(hipStreamSynchronize(s));
         if (timed) { float t = 0; RB_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); ms += t; ++launches; }
     }
-private:
-    template <typename Body>
-    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, int64_t, Body &&);
+protected:
+    template <typename P, typename PC, typename Body>
+    friend void for_each_piece(rb_graph *, hipStream_t, P &&, int64_t, int64_t, const char *, PC &, Body &&);
     rb_graph *g = nullptr;
     hipStream_t s = nullptr;
-    const char *seq = nullptr;
-    const int64_t *offsets = nullptr;
-    BatchPtr b;
     Event ev[2];
-    bool timing = false, timed = false, done = false;
+    bool timing = false, timed = false, busy = false, done = false;
     double ms = 0;                                      // the call's bracketed intervals so far, one launch a piece
     int64_t launches = 0;
 };
 
-// body(piece) for every piece of <= piece_dflt k-mers (RB_QUERY_PIECE overrides it) of n host sequences that has a k-mer at all, in order, on the query
-// stream s of a leased context.  ko: kmer_offsets of the sequences.  The body sizes its scratch, uploads its table, launches its kernels
-// between kernels_begin() and kernels_end() and enqueues its copies back, all on s.  prof_name: with profiling on
-// (rb_graph_profile_enable) the bracketed intervals of the call are summed into this profile entry, one launch a piece; nullptr: not timed.
+// The lower layer of the piece loop: body(pc) for every piece of n records, in order, on the query stream s of a leased context.  A piece takes
+// as many records as cost at most piece_dflt together (RB_QUERY_PIECE overrides it) by the prefix sums prefix(i) = cost of records [0, i), and
+// one record at the least.  prof_name: with profiling on (rb_graph_profile_enable) the bracketed intervals of the call are summed into this
+// profile entry, one launch a piece; nullptr: not timed.  pc is the caller's piece — a Piece, or what a layer above adds to it; what a piece
+// means (text, batches, tables) is that layer's or the body's business.
+template <typename P, typename PC, typename Body>
+void for_each_piece(rb_graph *g, hipStream_t s, P &&prefix, int64_t n, int64_t piece_dflt, const char *prof_name, PC &pc, Body &&body) {
+    Piece &base = pc;
+    base.g = g; base.s = s;
+    base.timing = prof_name && g->prof_on;
+    if (base.timing) for (Event &e : base.ev) RB_HIP(hipEventCreate(&e.e));
+    const std::vector<int64_t> cut = piece_cuts(prefix, n, query_piece_max(piece_dflt));
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        base.ra = cut[c]; base.rb = cut[c + 1]; base.pn = base.rb - base.ra;
+        base.timed = base.busy = base.done = false;
+        body(pc);
+        base.finish();
+    }
+    if (base.launches) {
+        std::lock_guard<std::mutex> lk(g->qm);              // (queries share the handle: the profile table is written under the context lock)
+        g->prof_add(prof_name, base.ms, base.launches);
+    }
+}
+template <typename P, typename Body>
+void for_each_piece(rb_graph *g, hipStream_t s, P &&prefix, int64_t n, int64_t piece_dflt, const char *prof_name, Body &&body) {
+    Piece pc;
+    for_each_piece(g, s, std::forward<P>(prefix), n, piece_dflt, prof_name, pc, std::forward<Body>(body));
+}
+
+// The piece for_each_host_piece hands to its body: records [ra, rb) of the call with `unit` sequences each — sequences [unit ra, unit rb) — that
+// have pt > 0 k-mers together.
+class HostPiece : public Piece {
+public:
+    int64_t pt = 0;
+    int unit = 1;
+    // the piece's text as a packed batch, uploaded at the first call and kept until the piece is over.  A body that finds nothing to do for
+    // a piece returns without asking: nothing is uploaded, and finish() has nothing to wait for.
+    const rb_batch *batch() {
+        if (!b) { busy = true; b = upload_text_batch(g->p.device, seq, offsets, unit * ra, unit * pn, s); }
+        return b.get();
+    }
+private:
+    template <typename Body>
+    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, int64_t, Body &&, int);
+    friend struct PieceRows;
+    const char *seq = nullptr;
+    const int64_t *offsets = nullptr, *ko = nullptr;
+    BatchPtr b;
+    std::vector<int64_t> tab;                           // the piece's table on the host (PieceRows)
+};
+
+// The upper layer: body(piece) for every piece of <= piece_dflt k-mers of n records of host text that has a k-mer at all.  A record is `unit`
+// sequences (1; a read pair: 2) of seq / offsets; ko: kmer_offsets of the unit * n sequences.  The piece keeps its lazily uploaded batch.
+template <typename Body>
+void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
+                         int64_t piece_dflt, Body &&body, int unit) {
+    HostPiece pc;
+    pc.seq = seq; pc.offsets = offsets; pc.ko = ko; pc.unit = unit;
+    for_each_piece(g, s, [&](int64_t i) { return ko[unit * i]; }, n, piece_dflt, prof_name, pc, [&](HostPiece &hp) {
+        hp.pt = ko[unit * hp.rb] - ko[unit * hp.ra];
+        if (hp.pt == 0) return;
+        body(hp);
+        hp.finish();
+        hp.b.reset();
+    });
+}
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
                          int64_t piece_dflt, Body &&body) {
-    HostPiece pc;
-    pc.g = g; pc.s = s; pc.seq = seq; pc.offsets = offsets;
-    pc.timing = prof_name && g->prof_on;
-    if (pc.timing) for (Event &e : pc.ev) RB_HIP(hipEventCreate(&e.e));
-    const std::vector<int64_t> cut = piece_cuts([&](int64_t i) { return ko[i]; }, n, query_piece_max(piece_dflt));
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        pc.ra = cut[c]; pc.rb = cut[c + 1]; pc.pn = pc.rb - pc.ra; pc.pt = ko[pc.rb] - ko[pc.ra];
-        if (pc.pt == 0) continue;
-        pc.timed = pc.done = false;
-        body(pc);
-        pc.finish();
-        pc.b.reset();
-    }
-    if (pc.launches) {
-        std::lock_guard<std::mutex> lk(g->qm);              // (queries share the handle: the profile table is written under the context lock)
-        g->prof_add(prof_name, pc.ms, pc.launches);
-    }
+    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, piece_dflt, std::forward<Body>(body), 1);
 }
 // ... with the usual pieces of 16 M k-mers
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
-                         Body &&body) {
-    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, (int64_t)16 << 20, std::forward<Body>(body));
+                         Body &&body, int unit = 1) {
+    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, (int64_t)16 << 20, std::forward<Body>(body), unit);
+}
+
+// A piece's getKmers rows as its kernel reads them: the k-mer offsets of its unit * pn sequences (kof[0] = 0), both strands' hashes and the
+// count of its pt k-mers, and its batch's 2-bit codes, usable-letter bits and word offsets.
+struct PieceRows {
+    const int64_t *kof;
+    const uint64_t *F, *R;
+    const float *cnt;
+    const uint64_t *codes;
+    const uint32_t *valid, *woff;
+    int64_t pn, pt;
+    // The rows of piece pc in the context's buffers: b0 the table — the k-mer offsets [unit pn + 1], then the caller's n_extra columns, which
+    // the kernel finds at kof + unit pn + 1 —, b1 / b2 the hashes, the head of b3 the counts (the caller has reserved b3: pt floats, then what
+    // it lays out behind them, and has enqueued its own uploads).  The table goes up, the piece's kernels begin (kernels_begin()) and
+    // getKmers is their first.
+    PieceRows(rb_graph *g, rb_query_ctx &c, HostPiece &pc, const int64_t *extra = nullptr, size_t n_extra = 0) {
+        const int64_t ns = pc.unit * pc.pn, s0 = pc.unit * pc.ra;
+        pc.tab.resize((size_t)ns + 1 + n_extra);
+        for (int64_t i = 0; i <= ns; ++i) pc.tab[(size_t)i] = pc.ko[s0 + i] - pc.ko[s0];
+        std::copy(extra, extra + n_extra, pc.tab.begin() + (ns + 1));
+        const rb_batch *b = pc.batch();
+        c.b0.reserve(pc.tab.size() * 8);
+        c.b1.reserve((size_t)pc.pt * 8);
+        c.b2.reserve((size_t)pc.pt * 8);
+        kof = c.b0.as<int64_t>();
+        F = c.b1.as<uint64_t>(); R = c.b2.as<uint64_t>();
+        cnt = c.b3.as<float>();
+        codes = b->codes; valid = b->valid; woff = b->woff;
+        pn = pc.pn; pt = pc.pt;
+        RB_HIP(hipMemcpyAsync(c.b0.p, pc.tab.data(), pc.tab.size() * 8, hipMemcpyHostToDevice, pc.s));
+        pc.kernels_begin();
+        launch_get_kmers(g, b, kof, c.b1.as<uint64_t>(), c.b2.as<uint64_t>(), c.b3.as<float>(), pc.s);
+    }
+    // into a kernel's argument struct that names the rows as this does (k_trim_artifacts fills R itself in a stranded graph: its field is not const)
+    template <class ARGS> void into(ARGS &a) const {
+        a.pn = pn; a.kof = kof; a.F = F; a.R = const_cast<uint64_t *>(R); a.cnt = cnt; a.codes = codes; a.valid = valid; a.woff = woff;
+    }
+};
+
+// the longest k-mer list among the n sequences of ko
+inline int64_t longest_list(const std::vector<int64_t> &ko, int64_t n) {
+    int64_t longest = 0;
+    for (int64_t i = 0; i < n; ++i) longest = std::max(longest, ko[(size_t)i + 1] - ko[(size_t)i]);
+    return longest;
 }
 
 }  // namespace rb

@@ -19,6 +19,7 @@
 #include "rb_lookup.hpp"
 #include "rb_repeat.hpp"
 #include "rb_align.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -43,6 +44,8 @@ constexpr size_t SC_ROW_BUDGET = (size_t)512 << 20;   // device scratch all wave
 struct ScLevel { uint64_t A, B; uint8_t code, base, fmask, pad; uint32_t fcodes; };
 static_assert(sizeof(ScLevel) == 24, "ScLevel is 24 bytes");
 constexpr int SC_LEVELS = SC_MAX_LOOKAHEAD + 1;
+
+using Dir = WaveDir<true>;               // a walk's direction, its rotations by k out of funnel shifts (rb_wave.hpp: k_screen's registers)
 
 struct ScGate { const uint32_t *bits; Mod mod; int num_hash; };       // the gate's dbgbf: BloomFilter assembledKmers
 
@@ -77,33 +80,10 @@ struct ScRows {
     }
 };
 
-#define SC_FENCE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
-
-// Both strands of a k-mer in walking order (as rb_extend.hip's walks): A rolls like a forward hash along the walk, B like a reverse-strand
-// hash.  A right-hand walk has (f, r) = (A, B); a left-hand walk adds bases at the k-mer's front, so its A is the k-mer's reverse-strand
-// hash and its B the forward one: xm / ym turn a base into the code whose seed A / B take.
-struct ScDir {
-    int stranded, left;
-    uint32_t uk, xm, ym;
-    __device__ __forceinline__ uint64_t fwd(uint64_t A, uint64_t B) const { return left ? B : A; }
-    __device__ __forceinline__ uint64_t hash(uint64_t A, uint64_t B) const { return stranded ? fwd(A, B) : smin(A, B); }
-    // the neighbour that drops base `out` and takes base `in` (Successors / PredecessorsNTHashIterator)
-    __device__ __forceinline__ void step(uint64_t A, uint64_t B, uint32_t out, uint32_t in, uint64_t &nA, uint64_t &nB) const {
-        nA = rotl1(A) ^ rotl_var(seed_of(out ^ xm), uk) ^ seed_of(in ^ xm);
-        nB = rotr1(B) ^ rotr1(seed_of(out ^ ym)) ^ rotl_var(seed_of(in ^ ym), uk - 1u);
-    }
-};
-__device__ __forceinline__ ScDir sc_dir(const ScArgs &a, int left) { return ScDir{a.stranded, left, (uint32_t)a.k, left ? 3u : 0u, left ? 0u : 3u}; }
-
-__device__ __forceinline__ uint64_t sc_shfl64(uint64_t v, int src) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // One neighbour of the k-mer (A, B): its hashes and its count code, 0 where it does not count — the gated getSuccessors / getPredecessors
 // (R/graph/Kmer.java:257-299: bf.lookup first, then graph.getCount > 0) or the plain one (:199-255 with minKmerCov 1: getCount >= 1; a
 // present k-mer counts at least 1, so both are "the count code is not 0")
-__device__ __forceinline__ uint32_t sc_neighbor(const ScArgs &a, const ScDir &dr, bool gated, uint64_t A, uint64_t B, uint32_t out, uint32_t in, uint64_t &nA,
+__device__ __forceinline__ uint32_t sc_neighbor(const ScArgs &a, const Dir &dr, bool gated, uint64_t A, uint64_t B, uint32_t out, uint32_t in, uint64_t &nA,
                                                 uint64_t &nB) {
     dr.step(A, B, out, in, nA, nB);
     const uint64_t h = dr.hash(nA, nB);
@@ -112,7 +92,7 @@ __device__ __forceinline__ uint32_t sc_neighbor(const ScArgs &a, const ScDir &dr
 }
 // ... all four by lanes 0 .. 3 (lane l keeps neighbour base l): the mask of those that count, for every lane
 struct ScNb { uint64_t A, B; uint32_t code; };
-__device__ __forceinline__ uint32_t sc_neighbors(const ScArgs &a, const ScDir &dr, bool gated, uint64_t A, uint64_t B, uint32_t out, uint32_t lane, ScNb &nb) {
+__device__ __forceinline__ uint32_t sc_neighbors(const ScArgs &a, const Dir &dr, bool gated, uint64_t A, uint64_t B, uint32_t out, uint32_t lane, ScNb &nb) {
     nb.A = 0; nb.B = 0; nb.code = 0;
     if (lane < 4u) nb.code = sc_neighbor(a, dr, gated, A, B, out, lane, nb.A, nb.B);
     return (uint32_t)__ballot(lane < 4u && nb.code != 0u) & 0xFu;
@@ -123,7 +103,7 @@ __device__ __forceinline__ uint32_t sc_neighbors(const ScArgs &a, const ScDir &d
 // candidate.  The candidate is the k-mer behind chain k-mer `at` of the text tx (ntext bases); st[0 .. SC_LEVELS) is the lane's stack.
 // With psize = path.size() and depth = frontier.size(), psize == depth + 1 at the head of the reference's outer loop and level j of the
 // path is chain k-mer at + 1 + j, whose leaving base is text position at + 1 + j — a base of tx, or one the path itself added.
-__device__ uint32_t sc_lookahead_score(const ScArgs &a, const ScDir &dr, const uint8_t *tx, int at, int ntext, ScLevel *st, uint64_t cA, uint64_t cB,
+__device__ uint32_t sc_lookahead_score(const ScArgs &a, const Dir &dr, const uint8_t *tx, int at, int ntext, ScLevel *st, uint64_t cA, uint64_t cB,
                                        uint32_t ccode, uint32_t cbase) {
     auto base = [&](int pos) -> uint32_t { return pos < ntext ? (uint32_t)tx[pos] : (uint32_t)st[pos - ntext].base; };
     auto nbrs = [&](uint64_t A, uint64_t B, uint32_t out, uint32_t &codes4) -> uint32_t {
@@ -175,7 +155,7 @@ __device__ uint32_t sc_lookahead_score(const ScArgs &a, const ScDir &dr, const u
 // candidates at hand): no neighbour, the only one, or the candidate with the best lookahead score, a tie going to the strictly larger
 // count (:547-559).  The text holds at + k bases.
 struct ScPick { uint64_t A, B; uint32_t base; bool any; };
-__device__ ScPick sc_greedy_step(const ScArgs &a, const ScDir &dr, const uint8_t *tx, int at, uint64_t A, uint64_t B, ScLevel *dfs, uint32_t lane) {
+__device__ ScPick sc_greedy_step(const ScArgs &a, const Dir &dr, const uint8_t *tx, int at, uint64_t A, uint64_t B, ScLevel *dfs, uint32_t lane) {
     ScNb nb;
     const uint32_t mask = sc_neighbors(a, dr, true, A, B, tx[at], lane, nb);
     ScPick p{0, 0, 0, mask != 0u};
@@ -194,7 +174,7 @@ __device__ ScPick sc_greedy_step(const ScArgs &a, const ScDir &dr, const uint8_t
             else if (s == best && cc > best_code) { bi = c; best_code = cc; }
         }
     }
-    p.A = sc_shfl64(nb.A, (int)bi); p.B = sc_shfl64(nb.B, (int)bi); p.base = bi;
+    p.A = wave_shfl64(nb.A, (int)bi); p.B = wave_shfl64(nb.B, (int)bi); p.base = bi;
     return p;
 }
 
@@ -210,14 +190,14 @@ struct ScSeq {
 };
 
 // a walk from k-mer s of the sequence: its text's first k bases in walking order, its hashes
-__device__ void sc_walk_begin(const ScArgs &a, const ScSeq &sq, const ScDir &dr, int s, uint8_t *tx, uint64_t &A, uint64_t &B, uint32_t lane) {
+__device__ void sc_walk_begin(const ScArgs &a, const ScSeq &sq, const Dir &dr, int s, uint8_t *tx, uint64_t &A, uint64_t &B, uint32_t lane) {
     for (int q = (int)lane; q < a.k; q += 64) tx[q] = (uint8_t)sq.base(dr.left ? s + a.k - 1 - q : s + q);
     const uint64_t f = sq.F[s], r = a.stranded ? 0ull : sq.R[s];
     A = dr.left ? r : f; B = dr.left ? f : r;
-    SC_FENCE();
+    wave_fence();
 }
 // Kmer.equals of chain k-mer c of a walk's text and k-mer s of the sequence: the forward hashes first (unequal hashes: unequal bases), then the bases
-__device__ bool sc_equals_seq(const ScArgs &a, const ScSeq &sq, const ScDir &dr, const uint8_t *tx, int c, uint64_t f, int s, uint32_t lane) {
+__device__ bool sc_equals_seq(const ScArgs &a, const ScSeq &sq, const Dir &dr, const uint8_t *tx, int c, uint64_t f, int s, uint32_t lane) {
     if (f != sq.F[s]) return false;
     bool ne = false;
     for (int q = (int)lane; q < a.k; q += 64) ne = ne || (uint32_t)tx[c + q] != sq.base(dr.left ? s + a.k - 1 - q : s + q);
@@ -229,20 +209,11 @@ __device__ bool sc_equals_chain(int k, const uint8_t *tc, int c, const uint8_t *
     for (int q = (int)lane; q < k; q += 64) ne = ne || tc[c + q] != te[rev ? e + k - 1 - q : e + q];
     return __ballot(ne) == 0ull;
 }
-// HashSet.contains: is chain k-mer c of text tc (forward hash f) one of the n k-mers a walk added — entry e is chain k-mer e + 1 of text te with
-// forward hash hrow[e]?  A lane per entry compares the hashes; an equal hash is confirmed on the bases.  *where: the entry (a walk's entries differ).
-__device__ bool sc_contains(int k, const uint64_t *hrow, const uint8_t *te, int n, const uint8_t *tc, int c, uint64_t f, bool rev, uint32_t lane,
-                            int *where = nullptr) {
-    for (int e0 = 0; e0 < n; e0 += 64) {
-        const int e = e0 + (int)lane;
-        unsigned long long m = __ballot(e < n && hrow[e] == f);
-        while (m) {
-            const int hit = e0 + (int)__builtin_ctzll(m);
-            m &= m - 1ull;
-            if (sc_equals_chain(k, tc, c, te, hit + 1, rev, lane)) { if (where) *where = hit; return true; }
-        }
-    }
-    return false;
+// HashSet.contains / indexOf: the entry of the n k-mers a walk added that equals chain k-mer c of text tc (forward hash f), else WAVE_NOWHERE — entry e is
+// chain k-mer e + 1 of text te with forward hash hrow[e] (a walk's entries differ).  rev: the two texts walk in opposite directions.
+__device__ int sc_find(int k, const uint64_t *hrow, const uint8_t *te, int n, const uint8_t *tc, int c, uint64_t f, bool rev, uint32_t lane) {
+    return wave_find(0, n, k, [&](int e) { return hrow[e]; }, f, [&](int e, int q) { return te[e + 1 + (rev ? k - 1 - q : q)]; },
+                     [&](int q) { return tc[c + q]; }, false, lane);
 }
 
 // getMaxCoveragePath(graph, left, right, bound, lookahead, bf) (:1677-1776) for left = k-mer li and right = k-mer ri of the sequence.  form 0:
@@ -255,7 +226,7 @@ struct ScPath {
 };
 __device__ ScPath sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int li, int ri, int bound, uint32_t lane) {
     const int k = a.k;
-    const ScDir dr0 = sc_dir(a, 0), dr1 = sc_dir(a, 1);
+    const Dir dr0 = wave_dir<true>(a.stranded, a.k, 0), dr1 = wave_dir<true>(a.stranded, a.k, 1);
     uint64_t A, B;
     int n0 = 0, n1 = 0;                                          // leftPath.size(), rightPath.size() less the spliced-in k-mers
     sc_walk_begin(a, sq, dr0, li, rw.tx[0], A, B, lane);
@@ -264,9 +235,9 @@ __device__ ScPath sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows
         if (!p.any) break;
         const uint64_t f = dr0.fwd(p.A, p.B);
         if (lane == 0) { rw.tx[0][k + n0] = (uint8_t)p.base; rw.h[0][n0] = f; }      // entry n0, kept only if the k-mer is added
-        SC_FENCE();
+        wave_fence();
         if (sc_equals_seq(a, sq, dr0, rw.tx[0], n0 + 1, f, ri, lane)) return ScPath{1, n0, 0, 0};
-        if (sc_contains(k, rw.h[0], rw.tx[0], n0, rw.tx[0], n0 + 1, f, false, lane)) break;
+        if (sc_find(k, rw.h[0], rw.tx[0], n0, rw.tx[0], n0 + 1, f, false, lane) != WAVE_NOWHERE) break;
         A = p.A; B = p.B; ++n0;
     }
     /* not connected, search from right */
@@ -276,11 +247,11 @@ __device__ ScPath sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows
         if (!p.any) break;
         const uint64_t f = dr1.fwd(p.A, p.B);
         if (lane == 0) { rw.tx[1][k + n1] = (uint8_t)p.base; rw.h[1][n1] = f; }
-        SC_FENCE();
+        wave_fence();
         if (sc_equals_seq(a, sq, dr1, rw.tx[1], n1 + 1, f, li, lane)) return ScPath{2, n0, n1, 0};
-        int idx = 0;
-        if (sc_contains(k, rw.h[0], rw.tx[0], n0, rw.tx[1], n1 + 1, f, true, lane, &idx)) return ScPath{3, n0, n1, idx};     // right path intersects the left path (:1748-1763)
-        if (sc_contains(k, rw.h[1], rw.tx[1], n1, rw.tx[1], n1 + 1, f, false, lane)) break;          // :1769-1771
+        const int idx = sc_find(k, rw.h[0], rw.tx[0], n0, rw.tx[1], n1 + 1, f, true, lane);
+        if (idx != WAVE_NOWHERE) return ScPath{3, n0, n1, idx};     // right path intersects the left path (:1748-1763)
+        if (sc_find(k, rw.h[1], rw.tx[1], n1, rw.tx[1], n1 + 1, f, false, lane) != WAVE_NOWHERE) break;          // :1769-1771
         A = p.A; B = p.B; ++n1;
     }
     return ScPath{0, n0, n1, 0};
@@ -288,7 +259,7 @@ __device__ ScPath sc_max_cov_path(const ScArgs &a, const ScSeq &sq, const ScRows
 
 // greedyExtendRight / Left(graph, source, lookahead, bound, bf) from k-mer s of the sequence into rows `side`: the number of k-mers added
 __device__ int sc_greedy_walk(const ScArgs &a, const ScSeq &sq, const ScRows &rw, ScLevel *dfs, int side, int s, int bound, uint32_t lane) {
-    const ScDir dr = sc_dir(a, side);
+    const Dir dr = wave_dir<true>(a.stranded, a.k, side);
     uint64_t A, B;
     int n = 0;
     sc_walk_begin(a, sq, dr, s, rw.tx[side], A, B, lane);
@@ -296,7 +267,7 @@ __device__ int sc_greedy_walk(const ScArgs &a, const ScSeq &sq, const ScRows &rw
         const ScPick p = sc_greedy_step(a, dr, rw.tx[side], n, A, B, dfs, lane);
         if (!p.any) break;
         if (lane == 0) { rw.tx[side][a.k + n] = (uint8_t)p.base; rw.h[side][n] = dr.fwd(p.A, p.B); }
-        SC_FENCE();
+        wave_fence();
         A = p.A; B = p.B; ++n;
     }
     return n;
@@ -328,20 +299,10 @@ __device__ bool sc_walks_meet(const ScArgs &a, const ScRows &rw, int n0, int n1,
 
 // the first index in [from, to) whose gate bit is `want`, else `to`; the last one in [lo, hi), else lo - 1
 __device__ int sc_next(const ScSeq &sq, int from, int to, bool want, uint32_t lane) {
-    for (int p0 = from; p0 < to; p0 += 64) {
-        const int p = p0 + (int)lane;
-        const unsigned long long m = __ballot(p < to && (sq.gbit[p] != 0) == want);
-        if (m) return p0 + (int)__builtin_ctzll(m);
-    }
-    return to;
+    return wave_first(from, to, [&](int p) { return (sq.gbit[p] != 0) == want; }, lane);
 }
 __device__ int sc_prev(const ScSeq &sq, int lo, int hi, bool want, uint32_t lane) {
-    for (int top = hi; top > lo; top -= 64) {
-        const int p = top - 1 - (int)lane;
-        const unsigned long long m = __ballot(p >= lo && (sq.gbit[p] != 0) == want);
-        if (m) return top - 1 - (int)__builtin_ctzll(m);
-    }
-    return lo - 1;
+    return wave_last(lo, hi, [&](int p) { return (sq.gbit[p] != 0) == want; }, lane);
 }
 
 // isChimera (:7674-7760) into the record's chimera fields; true: chimera
@@ -382,7 +343,7 @@ __device__ bool sc_chimera(const ScArgs &a, const ScSeq &sq, const ScRows &rw, S
 // of those not yet popped.  `frontier.size() >= depth` is tested after every push and after every removal of an empty level, never before
 // the first of them.  A level is pushed only while size < depth <= cap, so the rows hold the stack.
 __device__ int sc_has_depth(const ScArgs &a, const ScSeq &sq, const ScRows &rw, int left, bool gated, int s, int depth, uint32_t lane) {
-    const ScDir dr = sc_dir(a, left);
+    const Dir dr = wave_dir<true>(a.stranded, a.k, left);
     uint8_t *tx = rw.tx[0];
     uint64_t tA, tB;
     sc_walk_begin(a, sq, dr, s, tx, tA, tB, lane);
@@ -390,7 +351,7 @@ __device__ int sc_has_depth(const ScArgs &a, const ScSeq &sq, const ScRows &rw, 
     int visits = 1, size = 1;
     uint32_t tm = sc_neighbors(a, dr, gated, tA, tB, tx[0], lane, nb);
     if (lane == 0) { rw.h[0][0] = tA; rw.h[1][0] = tB; rw.mk[0] = (uint8_t)tm; }
-    SC_FENCE();
+    wave_fence();
     while (size > 0) {
         if (!tm) {                                               // alts.isEmpty(): frontier.removeLast()
             --size;
@@ -402,12 +363,12 @@ __device__ int sc_has_depth(const ScArgs &a, const ScSeq &sq, const ScRows &rw, 
             dr.step(tA, tB, tx[size - 1], b, cA, cB);
             if (visits >= a.max_visits) return -1;
             if (lane == 0) { rw.mk[size - 1] = (uint8_t)tm; tx[a.k + size - 1] = (uint8_t)b; }
-            SC_FENCE();
+            wave_fence();
             ++visits;
             tm = sc_neighbors(a, dr, gated, cA, cB, tx[size], lane, nb);
             tA = cA; tB = cB;
             if (size < a.cap && lane == 0) { rw.h[0][size] = tA; rw.h[1][size] = tB; rw.mk[size] = (uint8_t)tm; }
-            SC_FENCE();
+            wave_fence();
             ++size;
         }
         if (size >= depth) return 1;
@@ -475,19 +436,6 @@ __device__ bool sc_has_variant(const ScArgs &a, const ScSeq &sq, int i) {
     return any;
 }
 
-// a letter outside ACGTU among the sequence's nk + k - 1 (lane l looks at 32 letters at a time)
-__device__ bool sc_bad_letter(const ScArgs &a, int64_t r, int nk, uint32_t lane) {
-    const uint32_t *vw = a.valid + a.woff[r];
-    const int letters = nk + a.k - 1;
-    bool bad = false;
-    for (int w = (int)lane; 32 * w < letters; w += 64) {
-        const int left = letters - 32 * w;
-        const uint32_t want = left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u;
-        bad = bad || (vw[w] & want) != want;
-    }
-    return __ballot(bad) != 0ull;
-}
-
 // the screens of sequence r of the piece, by one wavefront
 __device__ void sc_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, uint32_t lane) {
     const int64_t k0 = a.kof[r];
@@ -499,7 +447,7 @@ __device__ void sc_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *df
         if (lane == 0) a.recs[r] = rec;
         return;
     }
-    if (sc_bad_letter(a, r, nk, lane)) {                         // not judged
+    if (wave_bad_letter(a.valid + a.woff[r], nk + a.k - 1, lane)) {    // not judged
         rec.flags = RB_SCREEN_BAD_LETTER;
         if (lane == 0) a.recs[r] = rec;
         return;
@@ -515,7 +463,7 @@ __device__ void sc_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *df
         }
         if (a.what & RB_SCREEN_BRANCH_FREE) branch = branch || sc_has_variant(a, sq, i);
     }
-    SC_FENCE();
+    wave_fence();
     if ((a.what & RB_SCREEN_BRANCH_FREE) && !__ballot(branch)) rec.flags |= RB_SCREEN_BRANCH_FREE;
     if ((a.what & RB_SCREEN_CHIMERA) && sc_chimera(a, sq, rw, dfs, rec, lane)) rec.flags |= RB_SCREEN_CHIMERA;
     if (a.what & RB_SCREEN_BLUNT_END) {
@@ -534,7 +482,7 @@ __global__ void __launch_bounds__(SC_TPB) k_screen(ScArgs a, uint8_t *scratch, s
     const ScRows rw(scratch + (size_t)slot * row_bytes, a.cap, a.k);
     for (int64_t r = slot; r < a.pn; r += n_slots) {
         sc_one(a, r, rw, s_dfs[wv], lane);
-        SC_FENCE();
+        wave_fence();
     }
 }
 
@@ -547,7 +495,7 @@ template <class S>
 __device__ bool sc_identity_ok(const ScArgs &a, const ScSeq &sq, S s, int slen, int t0, int tlen, int *lds_row, int *dev_row, int &d, uint32_t lane) {
     if (slen == 0) d = tlen;
     else d = ce_distance(s, slen, [&](int x) -> uint32_t { return sq.base(t0 + x); }, tlen, tlen > LEV_LDS ? dev_row : lds_row, lane);
-    SC_FENCE();
+    wave_fence();
     return !(ce_identity(d, slen, tlen) < a.percent_identity);
 }
 
@@ -555,7 +503,7 @@ __device__ bool sc_identity_ok(const ScArgs &a, const ScSeq &sq, S s, int slen, 
 __device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, int *lds_row, int *dev_row, uint32_t lane) {
     const int64_t k0 = a.kof[r];
     const int nk = (int)(a.kof[r + 1] - k0), k = a.k, clip = a.max_depth, max_indel = a.max_indel;
-    if (nk == 0 || sc_bad_letter(a, r, nk, lane)) {
+    if (nk == 0 || wave_bad_letter(a.valid + a.woff[r], nk + a.k - 1, lane)) {
         if (lane == 0) a.reprs[r] = repr_blank(nk == 0 ? RB_SCREEN_NO_KMER : RB_SCREEN_BAD_LETTER);
         return;
     }
@@ -564,7 +512,7 @@ __device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLeve
         const uint64_t f = sq.F[i];
         a.gbit[k0 + i] = (uint8_t)bits_lookup(a.gate.bits, a.gate.mod, a.gate.num_hash, a.kmul, a.stranded ? f : smin(f, sq.R[i]));
     }
-    SC_FENCE();
+    wave_fence();
     rb_repr_rec rec = repr_blank(0);
     rec.why = RB_REPR_WHY_TRUE;
     auto decide = [&](int why, int left, int right, int expected, int found, int d) {
@@ -647,11 +595,9 @@ __global__ void __launch_bounds__(SC_TPB) k_represented(ScArgs a, uint8_t *scrat
     const ScRows rw(mine, a.cap, a.k);
     for (int64_t r = slot; r < a.pn; r += n_slots) {
         sc_repr_one(a, r, rw, s_dfs[wv], s_row[wv], reinterpret_cast<int *>(mine + lev_off), lane);
-        SC_FENCE();
+        wave_fence();
     }
 }
-
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // What the two calls share once their arguments are checked: the pieces (rb_pieces.hpp), each with its getKmers rows, gate bits, records and the
 // wavefronts' rows.  REC is the record, `blank` what a sequence no kernel touches gets, `cap` the entries of a walk row, lev_cols the ints of
@@ -677,47 +623,26 @@ void screen_run(rb_graph *g, const rb_graph *gate, const char *seq, const int64_
     const int64_t max_slots = std::max<int64_t>(16, std::min<int64_t>(SC_MAX_SLOTS, (int64_t)(SC_ROW_BUDGET / row_bytes)));
     // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, gate bits, records and the
     // wavefronts' rows; with profiling on the kernels of every piece are timed: entry `entry`
-    std::vector<int64_t> tab;
     for_each_host_piece(g, s, seq, offsets, ko.data(), n, entry, [&](HostPiece &pc) {
         const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
-        tab.assign((size_t)pn + 1, 0);
-        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-        const rb_batch *b = pc.batch();
         const int64_t slots = std::min<int64_t>(pn, max_slots);
         const unsigned blocks = blocks_for(slots, SC_WAVES);
         const size_t o_g = up16((size_t)pt * 4), o_rec = up16(o_g + (size_t)pt), o_row = up16(o_rec + (size_t)pn * sizeof(REC));
-        q.c->b0.reserve(tab.size() * 8);
-        q.c->b1.reserve((size_t)pt * 8);
-        q.c->b2.reserve((size_t)pt * 8);
         q.c->b3.reserve(o_row + (size_t)blocks * SC_WAVES * row_bytes + 16);
         uint8_t *base3 = q.c->b3.as<uint8_t>();
         a.fv = g->view(0, 0);
         a.gate = ScGate{gate ? gate->dbg.bits : nullptr, gate ? gate->dbg.mod : g->dbg.mod, gate ? gate->dbg.num_hash : 0};
         a.kmul = kmul_of(k);
         a.stranded = (int)g->stranded; a.k = k; a.read_d = g->read_d;
-        a.pn = pn;
-        a.kof = q.c->b0.as<int64_t>();
-        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-        a.cnt = reinterpret_cast<float *>(base3);
         a.gbit = base3 + o_g;
-        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
         REC *recs = reinterpret_cast<REC *>(base3 + o_rec);
-        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
         RB_HIP(hipMemsetAsync(base3 + o_g, 0, o_rec - o_g, s));
-        pc.kernels_begin();
-        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        PieceRows(g, *q.c, pc).into(a);
         launch(a, recs, blocks, s, base3 + o_row, row_bytes, lev_off);
         RB_HIP(hipGetLastError());
         pc.kernels_end();
         RB_HIP(hipMemcpyAsync(out + ra, recs, (size_t)pn * sizeof(REC), hipMemcpyDeviceToHost, s));
     });
-}
-
-// the longest k-mer list among the n sequences
-int64_t longest_list(const std::vector<int64_t> &ko, int64_t n) {
-    int64_t longest = 0;
-    for (int64_t i = 0; i < n; ++i) longest = std::max(longest, ko[(size_t)i + 1] - ko[(size_t)i]);
-    return longest;
 }
 
 void screen_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int what, int lookahead, int max_depth,

@@ -18,6 +18,7 @@
 #include "rb_pieces.hpp"
 #include "rb_lookup.hpp"
 #include "rb_repeat.hpp"
+#include "rb_wave.hpp"
 
 using namespace rb;
 
@@ -48,7 +49,6 @@ struct TrArgs {
     rb_trim_rec *recs;
 };
 
-#define TR_FENCE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront")
 #define TR_FENCE_TABLE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent")
 
 // HashSet<Long>: open addressing over 64-bit keys, linear probing, at most half full.  An empty slot holds 0; the key 0 — a real hash — is not
@@ -371,19 +371,6 @@ __device__ void tr_long(const TrArgs &a, const TrSeq &sq, const TrSet &set, rb_t
     }
 }
 
-// a letter outside ACGTU among the sequence's nk + k - 1 (lane l looks at 32 letters at a time)
-__device__ bool tr_bad_letter(const TrArgs &a, int64_t r, int nk, uint32_t lane) {
-    const uint32_t *vw = a.valid + a.woff[r];
-    const int letters = nk + a.k - 1;
-    bool bad = false;
-    for (int w = (int)lane; 32 * w < letters; w += 64) {
-        const int left = letters - 32 * w;
-        const uint32_t want = left >= 32 ? 0xFFFFFFFFu : (1u << left) - 1u;
-        bad = bad || (vw[w] & want) != want;
-    }
-    return __ballot(bad) != 0ull;
-}
-
 // NTP64RC of every k-mer of a sequence in a stranded graph, whose getKmers row R holds 0: a lane per stretch of windows, the first hashed
 // base by base, the others rolled (R/bloom/hash/NTHash.java:133-166, as k_get_kmers rolls the reverse strand)
 __device__ void tr_reverse_hashes(const TrArgs &a, const uint32_t *cw32, uint64_t *R, int nk, uint32_t lane) {
@@ -399,7 +386,7 @@ __device__ void tr_reverse_hashes(const TrArgs &a, const uint32_t *cw32, uint64_
             R[p] = rv;
         }
     }
-    TR_FENCE();
+    wave_fence();
 }
 
 __device__ __forceinline__ rb_trim_rec tr_blank(int flags, int nk, int mode) {
@@ -414,7 +401,7 @@ __device__ __forceinline__ rb_trim_rec tr_blank(int flags, int nk, int mode) {
 __device__ void tr_one(const TrArgs &a, int64_t r, uint64_t *lds_tab, uint64_t *dev_tab, uint32_t lane) {
     const int64_t k0 = a.kof[r];
     const int nk = (int)(a.kof[r + 1] - k0);
-    if (nk == 0 || tr_bad_letter(a, r, nk, lane)) {              // not judged
+    if (nk == 0 || wave_bad_letter(a.valid + a.woff[r], nk + a.k - 1, lane)) {    // not judged
         if (lane == 0) a.recs[r] = tr_blank(nk == 0 ? RB_SCREEN_NO_KMER : RB_SCREEN_BAD_LETTER, nk, a.mode);
         return;
     }
@@ -441,11 +428,9 @@ __global__ void __launch_bounds__(TR_TPB) k_trim_artifacts(TrArgs a, uint64_t *s
     uint64_t *dev_tab = scratch + (size_t)slot * (size_t)a.tab_cap;
     for (int64_t r = slot; r < a.pn; r += n_slots) {
         tr_one(a, r, s_tab[wv], dev_tab, lane);
-        TR_FENCE();
+        wave_fence();
     }
 }
-
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 void trim_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int mode, int max_edge_clip, float max_cov_gradient, rb_trim_rec *out) {
     const char *who = "rb_graph_trim_rc_artifacts";
@@ -462,8 +447,7 @@ void trim_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
     std::vector<int64_t> ko((size_t)n + 1);
     kmer_offsets(offsets, n, k, ko.data(), who);
     RB_REQUIRE(offsets[n] == offsets[0] || seq, "%s: null sequence text", who);
-    int64_t longest = 0;
-    for (int64_t i = 0; i < n; ++i) longest = std::max(longest, ko[(size_t)i + 1] - ko[(size_t)i]);
+    const int64_t longest = longest_list(ko, n);
     RB_REQUIRE(longest <= TR_MAX_LIST, "%s: a sequence of %lld k-mers (at most %d)", who, (long long)longest, TR_MAX_LIST);
     // what no kernel touches: the sequences of pieces without a k-mer
     for (int64_t i = 0; i < n; ++i) {
@@ -486,29 +470,15 @@ void trim_call(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, 
     a.stranded = (int)g->stranded; a.k = k; a.mode = mode; a.clip = max_edge_clip; a.tab_cap = (int)tab_cap; a.grad = max_cov_gradient;
     // piece by piece (rb_pieces.hpp): b0 the piece's k-mer offsets, b1 / b2 the getKmers hashes, b3 counts, records and the wavefronts'
     // tables; with profiling on the kernels of every piece are timed: entry "trim_artifacts"
-    std::vector<int64_t> tab;
     for_each_host_piece(g, s, seq, offsets, ko.data(), n, "trim_artifacts", [&](HostPiece &pc) {
         const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
-        tab.assign((size_t)pn + 1, 0);
-        for (int64_t i = 0; i <= pn; ++i) tab[(size_t)i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-        const rb_batch *b = pc.batch();
         const int64_t slots = std::min<int64_t>(pn, max_slots);
         const unsigned blocks = blocks_for(slots, TR_WAVES);
         const size_t o_rec = up16((size_t)pt * 4), o_tab = up16(o_rec + (size_t)pn * sizeof(rb_trim_rec));
-        q.c->b0.reserve(tab.size() * 8);
-        q.c->b1.reserve((size_t)pt * 8);
-        q.c->b2.reserve((size_t)pt * 8);
         q.c->b3.reserve(o_tab + (size_t)blocks * TR_WAVES * (size_t)tab_cap * 8 + 16);
         uint8_t *base3 = q.c->b3.as<uint8_t>();
-        a.pn = pn;
-        a.kof = q.c->b0.as<int64_t>();
-        a.F = q.c->b1.as<uint64_t>(); a.R = q.c->b2.as<uint64_t>();
-        a.cnt = reinterpret_cast<float *>(base3);
-        a.codes = b->codes; a.valid = b->valid; a.woff = b->woff;
         a.recs = reinterpret_cast<rb_trim_rec *>(base3 + o_rec);
-        RB_HIP(hipMemcpyAsync(q.c->b0.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-        pc.kernels_begin();
-        rb::launch_get_kmers(g, b, a.kof, q.c->b1.as<uint64_t>(), q.c->b2.as<uint64_t>(), reinterpret_cast<float *>(base3), s);
+        PieceRows(g, *q.c, pc).into(a);
         hipLaunchKernelGGL(k_trim_artifacts, dim3(blocks), dim3(TR_TPB), 0, s, a, reinterpret_cast<uint64_t *>(base3 + o_tab));
         RB_HIP(hipGetLastError());
         pc.kernels_end();
