@@ -532,6 +532,65 @@ typedef struct rb_join_rec {            /* 48 bytes */
 } rb_join_rec;
 int rb_graph_join_pairs(rb_graph *g, const char *lseq, const int64_t *loffsets, const char *rseq, const int64_t *roffsets, int64_t n, int bound,
                         float max_cov_gradient, int max_tip_len, float min_kmer_cov, int64_t *out_offsets, char *out_seq, rb_join_rec *recs);
+/* Connection of read segments through the graph — GraphUtils.connect(ArrayList<String>, graph, lookahead) (R/util/GraphUtils.java:4836-4872) over the
+ * two-string connect (:4874-4896) and the six-argument getMaxCoveragePath (:1591-1675): the first thing the fragment, single-end and long-read workers
+ * do with a read (R/RNABloom.java:1980, 2092, 2106, 4781-4829).  A wavefront per gap and then a wavefront per read on the device; the call is read-only.
+ * Read i owns list entries [read_segs[i], read_segs[i+1]); entry j is seq[seg_offsets[j], seg_offsets[j+1]).  The list is SeqUtils.filterFastq's /
+ * filterFasta's (R/util/SeqUtils.java:1833-1934): entries with an even index within the read are runs of ACGTU (lower case and U read as everywhere in
+ * this library), entries with an odd index are placeholders of which only the LENGTH is read.  m = min_kmer_cov; the reference passes 1.  lookahead is
+ * accepted and not read: the six-argument getMaxCoveragePath never reads it (as max_tip_len of rb_graph_naive_extend).
+ *   By list size (:4838-4843): no entry, the result is "" (EMPTY); one entry, that entry, copied byte for byte whatever its letters (SINGLE).  More:
+ *   last = longest = entry 0, and for i = 1, 3, 5, ...: connected = connect(last, entry i+1, bound = length of entry i + k).  Not empty, it becomes
+ *   last, and longest when STRICTLY longer; empty, entry i+1 becomes last, and longest when strictly longer: of two runs of equal length the earlier
+ *   one is returned (CHAINED).  A connected string ends with the whole of its right segment, so the left k-mer of every gap is the last k-mer of the
+ *   segment before it: the gaps are independent of each other, only this choice is sequential.
+ *   connect(left, right, bound) (:4874-4896): path = getMaxCoveragePath(last k-mer of left, first k-mer of right, bound, m); "" when the path is null,
+ *   is EMPTY (the right k-mer follows the left one directly) or has more than bound k-mers; else left[0, len-k+1) + assemble(path) + right[k-1 ..),
+ *   which is left + the last letter of every path k-mer + right[k-1 ..): a path of fewer than k-1 k-mers lets right overlap left.
+ *   getMaxCoveragePath: a neighbour is Kmer.getMaxCovSuccessor / Predecessor (R/graph/Kmer.java:301-355), the first strictly largest graph.getCount
+ *   >= m among A C G T; equality of k-mers is Kmer.equals, the k bases: forward hashes are compared first and every hit is confirmed on the bases.
+ *   Left walk, up to bound times: no neighbour ends it (NO_NEIGHBOR); the neighbour equal to right returns the left path (how = LEFT_ARRIVED, l_end =
+ *   ARRIVED); one already in the left path ends it (LOOP); else it is added (BOUND after bound of them).  Right walk, up to bound times from right:
+ *   the neighbour equal to left returns the right path (RIGHT_ARRIVED); one in the right path returns null (RIGHT_LOOP, r_end = LOOP); one in the left
+ *   path (r_end = MET, index = the LAST left-path entry equal to it) returns null when SeqUtils.isLowComplexityShort of it holds
+ *   (MEET_LOW_COMPLEXITY), else left path [0, index] + the right path (PATHS_MEET).  Both walks over: null (EXHAUSTED).
+ *   A read the reference cannot be asked about is NOT_JUDGED, with why: a list of 2, 4, ... entries (EVEN_COUNT: the reference throws in get(i+1)); an
+ *   even entry under k letters in a list of more than one (SHORT); a letter outside ACGTU in such an entry (INVALID_LETTER), tested in this order.
+ *   Output: out_offsets (host, n + 1) is a capacity layout from the lengths alone: the sum of the read's even entries' lengths plus, per odd entry, its
+ *   length + 1 (a connected gap adds path_len - k + 1 <= gap length + 1 letters).  out_seq == NULL: a size query — only out_offsets is filled,
+ *   nothing is launched.  out_seq[out_offsets[i] ..] holds the returned string and recs[i].out_len its length; zeros behind it.  A SINGLE read's text
+ *   is the entry's bytes; a CHAINED read's text is upper-case A C G T also where the run is one segment; EMPTY / NOT_JUDGED have out_len 0.
+ *   recs[i]: gaps = the read's odd entries (list size / 2), connected = how many of them connected, first_seg / last_seg the list indices of the
+ *   returned run's first and last segment (-1 for EMPTY / NOT_JUDGED).  gaps (may be NULL), one record per odd entry in list order over all reads:
+ *   connected; how = the line that returned (NOT_RUN for the gaps of a NOT_JUDGED read); l_end / r_end how each walk ended; l_added / r_added the
+ *   k-mers it added; index as above, else -1; path_len the k-mers of the path returned, 0 for null.  connected is 0 for a path that is empty or
+ *   longer than bound: how still says which line returned it.
+ * Every gap is judged against the graph as it stands when the call starts.  The call works in pieces of whole reads cut by letters + bounds
+ * (RB_QUERY_PIECE, 16 M by default); results do not depend on the cuts.  A gap's two path rows — a forward hash per k-mer and the walk's text, 9 bytes
+ * per k-mer of bound and 2 k — live in LDS when bound <= 128 (2592 bytes a wavefront) and else in a row of device scratch that a wavefront owns, laid
+ * out for the piece's largest bound: at most 4096 rows a launch and fewer when they are large — as many as fit 512 MB, but 64 at least.
+ * RB_CONNECT_MAX_BOUND is the largest bound accepted.  It leases a query context (re-entrant on one handle).  With rb_graph_profile_enable on the
+ * kernels' device time is added to the profile entry "connect".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf or counting filter; a min_kmer_cov that is not finite
+ * or is negative; n < 0; with n > 0: a null seg_offsets / read_segs / out_offsets (or recs, unless out_seq is NULL too), decreasing read_segs or
+ * seg_offsets, text missing where offsets say there is some, a gap whose bound exceeds RB_CONNECT_MAX_BOUND.  n == 0 succeeds and touches nothing. */
+enum { RB_CONNECT_EMPTY = 0, RB_CONNECT_SINGLE = 1, RB_CONNECT_CHAINED = 2, RB_CONNECT_NOT_JUDGED = 3 };                        /* rb_connect_rec.outcome */
+enum { RB_CONNECT_WHY_NONE = 0, RB_CONNECT_WHY_EVEN_COUNT = 1, RB_CONNECT_WHY_SHORT = 2, RB_CONNECT_WHY_INVALID_LETTER = 3 };     /* rb_connect_rec.why */
+enum { RB_CONNECT_HOW_NOT_RUN = 0, RB_CONNECT_HOW_LEFT_ARRIVED = 1, RB_CONNECT_HOW_RIGHT_ARRIVED = 2, RB_CONNECT_HOW_PATHS_MEET = 3,
+       RB_CONNECT_HOW_MEET_LOW_COMPLEXITY = 4, RB_CONNECT_HOW_RIGHT_LOOP = 5, RB_CONNECT_HOW_EXHAUSTED = 6 };                     /* rb_connect_gap_rec.how */
+enum { RB_CONNECT_END_NOT_RUN = 0, RB_CONNECT_END_NO_NEIGHBOR = 1, RB_CONNECT_END_LOOP = 2, RB_CONNECT_END_BOUND = 3, RB_CONNECT_END_ARRIVED = 4,
+       RB_CONNECT_END_MET = 5 };                                                                                                 /* rb_connect_gap_rec.l_end, r_end */
+#define RB_CONNECT_MAX_BOUND 65536
+typedef struct rb_connect_rec {         /* 32 bytes */
+    int32_t outcome, why, gaps, connected;
+    int32_t first_seg, last_seg, out_len /* letters */, pad;
+} rb_connect_rec;
+typedef struct rb_connect_gap_rec {     /* 32 bytes */
+    int32_t connected, how, l_end, r_end;
+    int32_t l_added, r_added, index, path_len /* k-mers */;
+} rb_connect_gap_rec;
+int rb_graph_connect_segments(rb_graph *g, const char *seq, const int64_t *seg_offsets, const int64_t *read_segs, int64_t n, int lookahead,
+                              float min_kmer_cov, int64_t *out_offsets, char *out_seq, rb_connect_rec *recs, rb_connect_gap_rec *gaps /* may be NULL */);
 /* The fragment screens of the transcript assembler's worker (TranscriptAssemblyWorker.run, R/RNABloom.java:1816-1927) for n host sequences:
  * GraphUtils.isBranchFree (R/util/GraphUtils.java:7651-7672), isChimera (:7674-7760) and isBluntEndArtifact (:8535-8586), with what they
  * call: the gated getMaxCoveragePath (:1677-1776), the gated greedyExtendRight / Left (:1978-1997, :1940-1959) and the four static

@@ -540,6 +540,38 @@ public class BloomFilterDeBruijnGraph {
     }
 
     /**
+     * GraphUtils.connect(ArrayList, graph, lookahead) (src/rnabloom/util/GraphUtils.java:4836-4872) for a batch of reads in ONE native call: every
+     * masked stretch of every read is bridged by the six-argument getMaxCoveragePath on the device, a wavefront per gap, and the longest connected
+     * run of each read is returned; nothing is written to the graph.  segments.get(i) is read i's list from SeqUtils.filterFastq / filterFasta.
+     * Returns, per read, the string the reference returns, or null where it cannot be asked (an even number of entries, a segment shorter than
+     * k, a letter outside ACGTU: records[8 i] == 3).  records (optional, 8 * reads ints) receives the records of NativeGraph.connectSegments.
+     */
+    public String[] connectSegments(java.util.List<? extends java.util.List<String>> segments, int lookahead, int[] records) {
+        final int n = segments.size();
+        if (records != null && records.length < 8L * n) throw new IllegalArgumentException("connectSegments: records holds " + records.length + " ints, " + 8L * n + " are needed");
+        if (8L * n > Integer.MAX_VALUE) throw new IllegalArgumentException("connectSegments: " + n + " reads' records do not fit one array: smaller batches");
+        final long[] readSegs = new long[n + 1], outOff = new long[n + 1];
+        for (int i = 0; i < n; ++i) readSegs[i + 1] = readSegs[i] + segments.get(i).size();
+        if (readSegs[n] >= Integer.MAX_VALUE) throw new IllegalArgumentException("connectSegments: too many entries in one batch");
+        final long[] segOff = new long[(int) readSegs[n] + 1];
+        int e = 0;
+        for (java.util.List<String> list : segments) for (String s : list) { segOff[e + 1] = segOff[e] + s.length(); ++e; }
+        if (segOff[e] > Integer.MAX_VALUE) throw new IllegalArgumentException("connectSegments: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) segOff[e], 1));
+        for (java.util.List<String> list : segments) for (String s : list) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        final int[] rec = records != null ? records : new int[8 * n];
+        final int cap = NativeGraph.connectSegments(handle, text, segOff, readSegs, n, lookahead, 1f, outOff, null, null, null);
+        final ByteBuffer out = ByteBuffer.allocateDirect(Math.max(cap, 1));
+        NativeGraph.connectSegments(handle, text, segOff, readSegs, n, lookahead, 1f, outOff, out, rec, null);
+        final byte[] b = new byte[cap];
+        out.get(b, 0, cap);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i)
+            res[i] = rec[8 * i] == 3 ? null : new String(b, (int) outOff[i], rec[8 * i + 6], java.nio.charset.StandardCharsets.ISO_8859_1);
+        return res;
+    }
+
+    /**
      * GraphUtils.extendRightSE (direction 0) / extendLeftSE (direction 1) (src/rnabloom/util/GraphUtils.java:6018-6204) for a batch of sequences in ONE
      * native call: the candidates' naive walks, the read-paired k-mer look-ups and the scores run on the device, a wavefront per sequence, and
      * nothing is written to the graph.  seqs are in their natural orientation, minKmerCov holds one floor per sequence.  Returns, per sequence,

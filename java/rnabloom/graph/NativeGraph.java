@@ -155,6 +155,18 @@ public final class NativeGraph {
      *  read it).  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
     public static native int joinPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int bound,
                                        float maxCovGradient, int maxTipLen, float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] recs);
+    /** Connection of the segment lists of n reads through the graph (rb_graph_connect_segments; GraphUtils.connect(ArrayList, graph, lookahead),
+     *  R/util/GraphUtils.java:4836-4872): read i owns list entries [readSegs[i], readSegs[i + 1]), entry j is seq[segOffsets[j], segOffsets[j + 1]);
+     *  entries with an odd index within a read are placeholders read by length only.  outOffsets[n + 1] is filled from the lengths alone; outSeq ==
+     *  null sizes the output only.  Else recs holds 8 ints per read — outcome (0 empty, 1 single, 2 chained, 3 not judged), why (1 an even number of
+     *  entries, 2 a segment shorter than k, 3 a letter outside ACGTU), gaps, gaps connected, the list indices of the returned run's first and last
+     *  segment, the length of the text, 0 — and the returned string is recs[8 i + 6] bytes at outSeq + outOffsets[i].  gapRecs (may be null) holds 8
+     *  ints per odd entry in list order: connected, how (0 not run, 1 the left walk arrived, 2 the right walk arrived, 3 the paths meet, 4 they meet
+     *  in a low-complexity k-mer, 5 the right walk looped, 6 both walks ended), how each walk ended (0 not run, 1 no neighbour, 2 loop, 3 bound, 4
+     *  arrived, 5 met the left path), k-mers added by each, the left-path index of the meeting (-1: none), the k-mers of the path.  lookahead is not
+     *  read.  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
+    public static native int connectSegments(long h, ByteBuffer seq, long[] segOffsets, long[] readSegs, int n, int lookahead, float minKmerCov,
+                                             long[] outOffsets, ByteBuffer outSeq, int[] recs, int[] gapRecs);
     /** The fragment screens of n sequences (rb_graph_screen_fragments; GraphUtils.isBranchFree, isChimera and isBluntEndArtifact,
      *  R/util/GraphUtils.java:7651-7672, :7674-7760, :8535-8586): what = 1 branch-free | 2 chimera | 4 blunt-end artifact; gateHandleOr0 is the
      *  handle whose dbgbf is the BloomFilter assembledKmers (0 only for what == 1); maxDepth is maxEdgeClipLength; maxVisits the budget of one

@@ -474,6 +474,39 @@ jint FN(joinPairs)(JNIEnv *e, jclass c, jlong h, jobject lseq, jlongArray loffse
     if (rc) throw_rc(e, rc);
     return cap;
 }
+/* rb_graph_connect_segments: a read's record (rb_connect_rec, 32 bytes) is 8 ints to Java: outcome, why, gaps, connected, first_seg, last_seg, out_len, 0; a
+ * gap's (rb_connect_gap_rec, 32 bytes; gapRecs may be null) 8 more: connected, how, l_end, r_end, l_added, r_added, index, path_len.  outSeq == null (then recs may
+ * be null too) sizes the output: outOffsets is filled and outOffsets[n] returned */
+jint FN(connectSegments)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray segOffsets, jlongArray readSegs, jint n, jint lookahead, jfloat minKmerCov,
+                         jlongArray outOffsets, jobject outSeq, jintArray recs, jintArray gapRecs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!segOffsets || !readSegs || !outOffsets || (*e)->GetArrayLength(e, readSegs) <= n || (*e)->GetArrayLength(e, outOffsets) <= n ||
+                            (outSeq && (!recs || (*e)->GetArrayLength(e, recs) / 8 < n))))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "connectSegments: an array is too short for n reads");
+        return 0;
+    }
+    jlong *so = la(e, segOffsets), *rs = la(e, readSegs), *oo = la(e, outOffsets);
+    /* the lists' entries and gaps as readSegs counts them: segOffsets has one more element than entries, gapRecs 8 ints per odd entry */
+    int short_arrays = 0;
+    if (n > 0 && rs) {
+        jlong gaps = 0;
+        for (jint i = 0; i < n; ++i) gaps += rs[i + 1] > rs[i] ? (rs[i + 1] - rs[i]) / 2 : 0;
+        short_arrays = rs[n] < 0 || (jlong)(*e)->GetArrayLength(e, segOffsets) <= rs[n] || (outSeq && gapRecs && (jlong)(*e)->GetArrayLength(e, gapRecs) / 8 < gaps);
+    }
+    if (short_arrays) {
+        lr(e, segOffsets, so, JNI_ABORT); lr(e, readSegs, rs, JNI_ABORT); lr(e, outOffsets, oo, JNI_ABORT);
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "connectSegments: segOffsets or gapRecs is too short for the lists of readSegs");
+        return 0;
+    }
+    jint *rc8 = ia(e, recs), *gc8 = ia(e, gapRecs);
+    int rc = rb_graph_connect_segments(G(h), (const char *)direct(e, seq), (const int64_t *)so, (const int64_t *)rs, n, lookahead, minKmerCov, (int64_t *)oo,
+                                       outSeq ? (char *)direct(e, outSeq) : 0, (rb_connect_rec *)rc8, outSeq ? (rb_connect_gap_rec *)gc8 : 0);
+    if (rc == 0 && oo && n >= 0 && oo[n] > 0x7fffffffLL) rc = RB_ERR_INVALID;      /* the capacity layout does not fit the int this returns: smaller batches */
+    const jint cap = rc == 0 && oo && n >= 0 ? (jint)oo[n] : 0;
+    lr(e, segOffsets, so, JNI_ABORT); lr(e, readSegs, rs, JNI_ABORT); lr(e, outOffsets, oo, 0); ir(e, recs, rc8, 0); ir(e, gapRecs, gc8, 0);
+    if (rc) throw_rc(e, rc);
+    return cap;
+}
 /* rb_graph_screen_fragments: a record (rb_screen_rec, 32 bytes) is 8 ints to Java: flags, chim_why, break_i, break_j, right_len, left_len, blunt_why, boundary */
 void FN(screenFragments)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlongArray offsets, jint n, jint what, jint lookahead, jint maxDepth,
                          jlong maxVisits, jintArray recs) {

@@ -137,6 +137,7 @@ SYMBOLS = [
     ("rb_graph_extend_se", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_join_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp]),
+    ("rb_graph_connect_segments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
     ("rb_graph_represented", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp]),
     ("rb_graph_trim_rc_artifacts", _i32, [_vp, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp]),

@@ -632,6 +632,47 @@ class BloomFilterDeBruijnGraph:
         return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes() if rc["outcome"] == self.JOIN_JOINED else None, int(rc["outcome"]), int(rc["why"]))
                 for i, rc in enumerate(recs)]
 
+    CONNECT_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("gaps", "<i4"), ("connected", "<i4"), ("first_seg", "<i4"), ("last_seg", "<i4"),
+                              ("out_len", "<i4"), ("pad", "<i4")])
+    CONNECT_GAP_DTYPE = np.dtype([("connected", "<i4"), ("how", "<i4"), ("l_end", "<i4"), ("r_end", "<i4"), ("l_added", "<i4"), ("r_added", "<i4"),
+                                  ("index", "<i4"), ("path_len", "<i4")])
+    CONNECT_OUTCOMES = ("empty", "single", "chained", "not_judged")
+    CONNECT_WHYS = ("none", "even_count", "short", "invalid_letter")
+    CONNECT_HOWS = ("not_run", "left_arrived", "right_arrived", "paths_meet", "meet_low_complexity", "right_loop", "exhausted")
+    CONNECT_ENDS = ("not_run", "no_neighbor", "loop", "bound", "arrived", "met")
+    CONNECT_EMPTY, CONNECT_SINGLE, CONNECT_CHAINED, CONNECT_NOT_JUDGED = range(4)
+    CONNECT_MAX_BOUND = 65536
+
+    def connectSegmentsFlat(self, seq, segOffsets, readSegs, lookahead=0, minKmerCov=1.0, gaps=True):
+        """rb_graph_connect_segments on flat host text (GraphUtils.connect over a segment list, R/util/GraphUtils.java:4836-4872): read i owns
+        list entries readSegs[i]:readSegs[i + 1], entry j is seq[segOffsets[j]:segOffsets[j + 1]] (uint8); the entries with an odd index
+        within a read are placeholders read by length only.  Returns (out, out_offsets, recs, gap_recs): one CONNECT_DTYPE record per read,
+        the returned string at out[out_offsets[i]:out_offsets[i] + recs[i]["out_len"]], one CONNECT_GAP_DTYPE record per odd entry in list
+        order (None with gaps=False).  lookahead is not read.  Read-only."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        so, rs = np.ascontiguousarray(segOffsets, dtype=np.int64), np.ascontiguousarray(readSegs, dtype=np.int64)
+        n = rs.size - 1
+        oo = np.zeros(n + 1, np.int64)
+        args = (self.h, _ptr(seq), _ptr(so), _ptr(rs), n, lookahead, minKmerCov, _ptr(oo))
+        check(lib.rb_graph_connect_segments(*args, None, None, None))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        recs = np.zeros(n, self.CONNECT_DTYPE)
+        grecs = np.zeros(max(1, int((np.diff(rs) // 2).sum())), self.CONNECT_GAP_DTYPE) if gaps else None
+        check(lib.rb_graph_connect_segments(*args, _ptr(out), _ptr(recs), _ptr(grecs) if gaps else None))
+        return out, oo, recs, (grecs[:int((np.diff(rs) // 2).sum())] if gaps else None)
+
+    def connectSegments(self, segmentLists, lookahead=0, minKmerCov=1.0):
+        """GraphUtils.connect of each read's segment list (filterFastq's / filterFasta's, rnabloom.io): per read (bytes, outcome, why) — the
+        string the reference returns (b"" for an empty list and for a read that is CONNECT_NOT_JUDGED: an even number of entries, a segment
+        shorter than k, a letter outside ACGTU), the CONNECT_* outcome and the index into CONNECT_WHYS."""
+        enc = lambda s: s.encode() if isinstance(s, str) else bytes(s)
+        flat = [enc(s) for segs in segmentLists for s in segs]
+        seq, so = _pack(flat)
+        rs = np.zeros(len(segmentLists) + 1, np.int64)
+        np.cumsum([len(segs) for segs in segmentLists], out=rs[1:])
+        out, oo, recs, _ = self.connectSegmentsFlat(seq, so, rs, lookahead, minKmerCov, gaps=False)
+        return [(out[oo[i]:oo[i] + rc["out_len"]].tobytes(), int(rc["outcome"]), int(rc["why"])) for i, rc in enumerate(recs)]
+
     EXT_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("n_candidates", "<i4"), ("out_len", "<i4"), ("pairs", "<i4"),
                           ("last_partnered", "<i4"), ("winner", "<i4"), ("score", "<f4")])
     EXT_OUTCOMES = ("none", "single", "first", "second")

@@ -201,6 +201,43 @@ def overlapAndConnect(graph, lefts, rights, bound, minOverlap, maxCovGradient, m
     return res
 
 
+def connect(graph, segment_lists, lookahead=0):
+    """GraphUtils.connect(segments, graph, lookahead) (R/util/GraphUtils.java:4836-4872) for many reads in ONE graph.connectSegments call: the
+    segment lists are filterFastq's / filterFasta's (rnabloom.io).  Returns per read the string the reference returns as bytes, or None for a
+    read it cannot be asked about (an even number of entries, a segment shorter than k in a list of several, a letter outside ACGTU).  The
+    reference's minKmerCov is 1; lookahead is not read."""
+    return [None if outcome == graph.CONNECT_NOT_JUDGED else text for text, outcome, _ in graph.connectSegments(segment_lists, lookahead, 1.0)]
+
+
+def connectComposed(graph, segment_lists):
+    """The same from getMaxCoveragePaths (two lane-per-walk launches for all gaps of one bound, the letters stitched here): the route a caller had
+    before graph.connectSegments, kept as its in-library cross-check and as the other side of tools/connect_bench.py.  Every list has an odd
+    number of entries, segments of at least k letters of ACGT in upper case."""
+    k = graph.k
+    by_bound = {}
+    for r, segs in enumerate(segment_lists):
+        for i in range(1, len(segs), 2):
+            by_bound.setdefault(len(segs[i]) + k, []).append((r, i))
+    paths = {}
+    for bound, where in by_bound.items():
+        got = getMaxCoveragePaths(graph, [bytes(segment_lists[r][i - 1][-k:]) for r, i in where], [bytes(segment_lists[r][i + 1][:k]) for r, i in where], bound)
+        for key, p in zip(where, got):
+            paths[key] = p if p and len(p) <= bound else None
+    out = []
+    for r, segs in enumerate(segment_lists):
+        if len(segs) < 2:
+            out.append(bytes(segs[0]) if segs else b"")
+            continue
+        last = longest = bytes(segs[0])
+        for i in range(1, len(segs), 2):
+            p = paths[(r, i)]
+            last = last + bytes(km[-1] for km in p) + bytes(segs[i + 1][k - 1:]) if p else bytes(segs[i + 1])
+            if len(last) > len(longest):
+                longest = last
+        out.append(longest)
+    return out
+
+
 def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
     """GraphUtils.extendSE(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6454-6565) for many sequences: first to the left,
     then to the right, each sequence is extended across branches by extendLeftSE / extendRightSE until the step returns nothing at the

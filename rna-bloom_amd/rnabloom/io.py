@@ -67,6 +67,61 @@ def batchFromFasta(text, device=0, final=True):
     return ReadBatch(h, device), used.value, bool(ended.value)
 
 
+# ---- the segment lists GraphUtils.connect takes (BloomFilterDeBruijnGraph.connectSegments, graphutils.connect) ----
+import re
+
+_PHRED33 = bytes(range(33, 127))                   # R/util/SeqUtils.java:1426
+
+
+def _nucleotide_pattern(k):
+    """SeqUtils.getNucleotideCharsPattern (R/util/SeqUtils.java:1436-1438)"""
+    return re.compile(b"[ACGTU]{%d,}" % k, re.IGNORECASE)
+
+
+def _phred33_pattern(minBaseQual, k):
+    """SeqUtils.getPhred33Pattern (R/util/SeqUtils.java:1432-1434): runs of at least k quality letters of minBaseQual or more"""
+    return re.compile(b"[" + re.escape(_PHRED33[minBaseQual:]) + b"]{%d,}" % k)
+
+
+def _runs_and_gaps(seq, pattern, keep):
+    """the loop both functions run (R/util/SeqUtils.java:1842-1862): every match of pattern in upper case through keep(), and in front of
+    every match but the first what lies between it and the match before: one 'N' for one letter, else that many 'N' (GAP_CHAR)"""
+    end = 0
+    for m in pattern.finditer(seq):
+        if end > 0:
+            keep(b"N" * (m.start() - end))
+        end = m.end()
+        keep(seq[m.start():end].upper())
+
+
+def filterFasta(seq, k):
+    """SeqUtils.filterFasta(seq, getNucleotideCharsPattern(k)) (R/util/SeqUtils.java:1833-1865): the runs of at least k letters of ACGTU (either
+    case, returned in upper case; U stays U) at the even indices, placeholders of N — as long as what was left out between two runs — at the odd
+    ones.  What lies before the first run and behind the last one is dropped.  bytes in, a list of bytes out."""
+    seq = seq.encode() if isinstance(seq, str) else bytes(seq)
+    out = []
+    _runs_and_gaps(seq, _nucleotide_pattern(k), out.append)
+    return out
+
+
+def filterFastq(seq, qual, k, minBaseQual):
+    """SeqUtils.filterFastq(seq, qual, getNucleotideCharsPattern(k), getPhred33Pattern(minBaseQual, k)) (R/util/SeqUtils.java:1871-1934): the
+    letters under the Phred-33 runs of at least k qualities >= minBaseQual are kept, what lies between two such runs becomes N, and the result
+    is filtered as filterFasta filters.  An empty seq or qual gives an empty list.  seq and qual have the same length."""
+    seq = seq.encode() if isinstance(seq, str) else bytes(seq)
+    qual = qual.encode() if isinstance(qual, str) else bytes(qual)
+    if not seq or not qual:
+        return []
+    kept = []
+    end = 0
+    for m in _phred33_pattern(minBaseQual, k).finditer(qual):                   # (the same loop, with the matches found in qual and cut out of seq)
+        if end > 0:
+            kept.append(b"N" * (m.start() - end))
+        end = m.end()
+        kept.append(seq[m.start():end].upper())
+    return filterFasta(b"".join(kept), k)
+
+
 def writeNbits(path, seq, offsets, append=False):
     """NucleotideBitsWriter: 4-byte big-endian length + 2-bit bases (first base in the top bits, value - 128) per sequence"""
     seq = np.ascontiguousarray(seq, np.uint8); off = np.ascontiguousarray(offsets, np.int64)
