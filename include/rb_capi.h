@@ -476,6 +476,61 @@ typedef struct rb_extend_pe_rec {       /* 40 bytes */
 } rb_extend_pe_rec;
 int rb_graph_extend_pe(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int direction, const float *min_kmer_cov,
                        char *out_bases /* n * (frag_d + 2) */, float *out_count /* n * (frag_d + 2), may be NULL */, rb_extend_pe_rec *recs);
+/* The extension loop of fragments — GraphUtils.extendSE (R/util/GraphUtils.java:6454-6565; which = RB_EXTL_SE) and extendPE (:6567-6678; RB_EXTL_PE),
+ * the step of TranscriptAssemblyWorker.run that grows a fragment into a transcript (R/RNABloom.java:1846-1851) — for n host sequences in ONE call: a
+ * wavefront per sequence keeps it on the device from its first round to its last.  The call is read-only.  Sequence i is seq[offsets[i],
+ * offsets[i+1]), kmers = getKmers of it; D is the read-paired k-mer distance for SE and the fragment-paired one for PE; m = min_kmer_cov.
+ *   The left side runs first, over the reversed list, with extendLeftSE / extendLeftPE; the right side after it with extendRightSE / PE.  An outer
+ *   iteration (:6467-6512): thr = the minimum getCount of the list's last min(size, D) k-mers (an added k-mer carries the count its step returned).
+ *   Inner loop: thr = max(m, thr * 0.1f) in float32, then a step with that floor — rb_graph_extend_se's / _pe's step exactly — until the step returns
+ *   k-mers or thr == m.  Nothing returned: the side ends (END_NOTHING).  Else used = every returned k-mer is already a k-mer of the list
+ *   (Kmer.equals: hashes are compared first, every hit is confirmed on the bases).  The reference's second loop (:6497-6504) re-tests members of the
+ *   list against the set made of the list; it can never clear the flag and is not restated.  used and size < D: the side ends (END_USED_SHORT).  used
+ *   and hasDuplicatedKmerPair(list, e.getLast(), D, size - 1 - D + |e|) (:6416-6452: lastIndexOf, indexOf and the scan between them, which together
+ *   ask whether some list[i] == e.getLast(), i >= D, has list[i - D] == list[size - 1 - D + |e|]): the side ends (END_USED_PAIR).  Else the k-mers are
+ *   appended to the list and count as its k-mers from then on.
+ *   Letters: the device judges sequences of upper-case A C G T only — the reference compares k-mers as bytes and added letters are upper-case A C G
+ *   T, so `acgt`, U and N would need the bytes kept beside the codes.  A sequence with fewer than k letters is NOT_JUDGED / WHY_NO_KMER, any other
+ *   with another byte NOT_JUDGED / WHY_LETTER: it comes back as it went in (out_len its length, every other field 0) and the caller's host loop is
+ *   its route.  With clean letters RB_EXT_WHY_REPEAT_THROWS and WHY_INVALID_SEED cannot occur in a step.
+ *   Room: the reference's loop has no bound; `room` is the most letters (= k-mers) a call may add on EACH side of a sequence.  Only whole rounds are
+ *   applied: a round whose k-mers do not fit in what is left of its side's room is dropped (before the used test), the side ends with END_ROOM and the
+ *   status is RB_EXTL_ROOM; after a left END_ROOM the right side is not run (END_NOT_RUN).  Nothing is truncated or guessed: the list's k-mers are
+ *   the set, thr is recomputed from the list at the top of every outer iteration, so the state after any whole round is a state of the reference's
+ *   loop.  Resume with the returned text: phase[i] = 0 (or phase == NULL) runs both sides — after a left END_ROOM; phase[i] = 1 runs the right side
+ *   only (left_end = END_NOT_RUN) — after a right END_ROOM.  Chained calls return what one call with ample room returns; left_ext / right_ext add up
+ *   over the calls.  A step returns at most D k-mers and room >= D + 2, so every call makes progress.
+ *   Output: out_offsets (host, n + 1) is the capacity layout len_i + 2 * room, filled from the lengths alone; out_seq == NULL is a size query: nothing
+ *   else is touched, nothing is launched.  Else out_seq[out_offsets[i] ..] holds out_len letters — the original ones as they were, added ones
+ *   upper-case A C G T — and zeros behind them.  recs[i]: left_ext / right_ext the k-mers (= letters) added on each side, left_end / right_end how each
+ *   side ended, left_rounds / right_rounds the rounds applied, steps the steps taken, floor_drops the steps that returned nothing above the lowest
+ *   floor, used_passed the rounds that were `used` and went on, left_floor / right_floor the floor of the LAST step taken on that side (a dropped
+ *   round's included; 0 where no step was taken).
+ * The call works in pieces cut by capacity k-mers, len_i + 2 * room - k + 1 (RB_QUERY_PIECE, 16 M by default); results do not depend on the cuts.
+ * Device scratch of a piece: 20 bytes per capacity k-mer (both hashes, the count) and 2 per capacity letter (the code, the text out) — a sequence's
+ * row for as long as the piece lasts —, 20 bytes per k-mer of the text that went in, 64 + 1 per sequence, and for each of at most 4096 wavefronts
+ * about 100 + 5 D bytes of the step's own, plus for D > 256 (the walks' rows do not fit LDS) about 25 D.  It leases a query context (re-entrant on
+ * one handle).  With rb_graph_profile_enable on the kernels' device time is added to the profile entry "extend_loop".  RB_ERR_STATE: a row was found
+ * outgrown (an internal error; nothing is cut silently).
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf, counting filter or read-pair filter (or a graph made
+ * without one), for PE also the fragment-pair filter; a distance below 2; `which` other than 0 / 1; a min_kmer_cov that is not finite or is negative;
+ * room < D + 2 or room > 2^24; n < 0; with n > 0: a null offsets / out_offsets (or recs, unless out_seq is NULL too), a null seq where there is text,
+ * decreasing offsets, a phase byte above 1.  n == 0 succeeds and touches nothing. */
+enum { RB_EXTL_SE = 0, RB_EXTL_PE = 1 };                                                                                         /* which */
+enum { RB_EXTL_DONE = 0, RB_EXTL_ROOM = 1, RB_EXTL_NOT_JUDGED = 2 };                                                             /* rb_extend_loop_rec.status */
+enum { RB_EXTL_WHY_NONE = 0, RB_EXTL_WHY_NO_KMER = 1, RB_EXTL_WHY_LETTER = 2 };                                                  /* rb_extend_loop_rec.why (NOT_JUDGED) */
+enum { RB_EXTL_END_NOT_RUN = 0, RB_EXTL_END_NOTHING = 1, RB_EXTL_END_USED_SHORT = 2, RB_EXTL_END_USED_PAIR = 3, RB_EXTL_END_ROOM = 4 };   /* left_end, right_end */
+typedef struct rb_extend_loop_rec {     /* 64 bytes */
+    int32_t status, why;
+    int32_t left_ext, right_ext, out_len /* letters */;
+    int32_t left_end, right_end;
+    int32_t left_rounds, right_rounds;
+    int32_t steps, floor_drops, used_passed;
+    float left_floor, right_floor;
+    int32_t pad[2];
+} rb_extend_loop_rec;
+int rb_graph_extend_loop(rb_graph *g, int which, const char *seq, const int64_t *offsets, int64_t n, const uint8_t *phase /* may be NULL */,
+                         float min_kmer_cov, int room, int64_t *out_offsets, char *out_seq, rb_extend_loop_rec *recs);
 /* Joining of read pairs through the graph — GraphUtils.join (R/util/GraphUtils.java:892-1147), the second half of overlapAndConnect (:5065-5090) that
  * the FragmentAssembler runs on every pair GraphUtils.overlap returned null for (R/RNABloom.java:2148).  A wavefront per pair on the device; the call
  * is read-only.  Pair i is lseq[loffsets[i], loffsets[i+1]) and rseq[roffsets[i], roffsets[i+1]); each read's k-mer list is getKmers(String)'s

@@ -155,6 +155,19 @@ public final class NativeGraph {
      *  read it).  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
     public static native int joinPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int bound,
                                        float maxCovGradient, int maxTipLen, float minKmerCov, long[] outOffsets, ByteBuffer outSeq, int[] recs);
+    /** The extension loop of n fragments on the device (rb_graph_extend_loop; GraphUtils.extendSE, which = 0, and extendPE, which = 1,
+     *  R/util/GraphUtils.java:6454-6678): every sequence — upper-case A C G T, at least k letters — is extended to the left and then to the right,
+     *  round after round, until the step returns nothing at the lowest floor or only k-mers the sequence already holds.  room (at least the loop's
+     *  distance + 2) is the most letters a call adds on each side; outOffsets[n + 1] is filled with the capacity layout length + 2 room; outSeq ==
+     *  null sizes the output only.  Else recs holds 16 ints per sequence — status (0 done, 1 out of room: call again with the returned text and
+     *  phase 0 after a left end 4, phase 1 after a right end 4; 2 not judged: keep the host loop for it), why (1 fewer than k letters, 2 a letter
+     *  other than upper-case A C G T), k-mers added left and right, the length of the text, how the left and the right side ended (0 not run, 1
+     *  nothing found, 2 only known k-mers and the list shorter than the distance, 3 a duplicated k-mer pair, 4 out of room), rounds left and right,
+     *  steps, floor drops, rounds of known k-mers that went on, the bits of both sides' last floors (Float.intBitsToFloat), 0, 0 — and the text is
+     *  recs[16 i + 4] bytes at outSeq + outOffsets[i].  phase (may be null: all 0): 0 both sides, 1 the right side only.  Read-only.  Returns
+     *  outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
+    public static native int extendLoop(long h, int which, ByteBuffer seq, long[] offsets, int n, byte[] phase, float minKmerCov, int room,
+                                        long[] outOffsets, ByteBuffer outSeq, int[] recs);
     /** Connection of the segment lists of n reads through the graph (rb_graph_connect_segments; GraphUtils.connect(ArrayList, graph, lookahead),
      *  R/util/GraphUtils.java:4836-4872): read i owns list entries [readSegs[i], readSegs[i + 1]), entry j is seq[segOffsets[j], segOffsets[j + 1]);
      *  entries with an odd index within a read are placeholders read by length only.  outOffsets[n + 1] is filled from the lengths alone; outSeq ==

@@ -1,7 +1,8 @@
 // rb_extend_step.hpp — the paired-k-mer branch step on the device, once: GraphUtils.extendRightSE / extendLeftSE (R/util/GraphUtils.java:6018-6204) and,
 // as a compile-time variant, extendRightPE / extendLeftPE (:6206-6414) of ONE sequence by ONE wavefront (ex_one), with the naive walks, the pair
 // counts and the repeat scan it is made of.  rb_extend.hip runs it over host sequences (rb_graph_extend_se / rb_graph_extend_pe: k_extend); rb_join.hip
-// calls it where a walk of GraphUtils.join stands at a fork, with the path's tail where it lies in device memory (k_join).  Everything is in an
+// calls it where a walk of GraphUtils.join stands at a fork, with the path's tail where it lies in device memory (k_join); rb_extend_loop.hip
+// calls it round after round on a sequence that grows in a row of device memory (k_extloop), letters included (ExRowText).  Everything is in an
 // unnamed namespace: a unit that includes this gets its own copy, inlined into its kernels.
 #pragma once
 #include <math.h>
@@ -225,6 +226,30 @@ __device__ void ex_emit(const ExArgs &a, int64_t r, const ExChain &ch, const ExC
     }
 }
 
+// Where the step reads a sequence's letters — the last k-mer's, and for PE those of the trailing k-mers — by their place p in the text the
+// tail's k-mers are windows of.  Two sources: the piece's packed batch (k_extend, k_join: 2-bit codes 32 a word and a usable-letter bit
+// each), and a walk's row in device memory that holds a code a byte and nothing but A C G T (k_extloop, whose sequences grow where they lie).
+struct ExBatchText {
+    const uint64_t *codes;
+    const uint32_t *valid, *woff;                // woff: the sequence's own entry (looked up at every use: a pointer held across the walks costs k_extend registers)
+    __device__ __forceinline__ const uint64_t *cw() const { return codes + *woff; }
+    __device__ __forceinline__ bool usable(uint32_t p) const { return ((valid + *woff)[p >> 5] >> (p & 31u)) & 1u; }
+    __device__ __forceinline__ uint32_t seed_code(uint32_t p) const { return (uint32_t)(cw()[p >> 5] >> (2u * (p & 31u))) & 3u; }
+    __device__ __forceinline__ uint32_t code(uint32_t p) const { return base_at(reinterpret_cast<const uint32_t *>(cw()), p); }
+    __device__ __forceinline__ bool window_is_repeat(uint32_t p, int k, int t1, int t2, int t3) const {
+        return rb::window_is_repeat(reinterpret_cast<const uint32_t *>(cw()), p, k, t1, t2, t3);
+    }
+};
+struct ExRowText {
+    const uint8_t *t;
+    __device__ __forceinline__ bool usable(uint32_t) const { return true; }
+    __device__ __forceinline__ uint32_t seed_code(uint32_t p) const { return t[p]; }
+    __device__ __forceinline__ uint32_t code(uint32_t p) const { return t[p]; }
+    __device__ __forceinline__ bool window_is_repeat(uint32_t p, int k, int t1, int t2, int t3) const {
+        return window_is_repeat_of([&](int j) { return (uint32_t)t[p + (uint32_t)j]; }, k, t1, t2, t3);
+    }
+};
+
 // The repeat scan of extendRightPE / extendLeftPE (:6226-6233, :6333-6340): the number of trailing k-mers of the list, from the last one
 // backwards, that graph.isRepeatKmer accepts (SeqUtils.isRepeat(byte[]) :458-497 of the k-mer in its natural orientation, also for the
 // left-hand direction), each lowering the bound by one.  Every bound <= 0 acts alike — a walk adds one k-mer and ++extensionLength > bound
@@ -233,9 +258,8 @@ __device__ void ex_emit(const ExArgs &a, int64_t r, const ExChain &ch, const ExC
 // (window_is_repeat on the batch's packed codes), a ballot, the run of leading ones.  A k-mer holding a letter outside ACGTU: the
 // reference's first loop returns true if a base count reaches t1 before that letter and else indexes an array with -1 and throws; -1 is
 // returned for the throw.  A bad letter further back than the scan reaches is not seen.
-__device__ int ex_trailing_repeats(const ExArgsPE &a, int64_t r, int nt, int most, uint32_t lane) {
-    const uint32_t *cw32 = reinterpret_cast<const uint32_t *>(a.codes + a.woff[r]);
-    const uint32_t *vw = a.valid + a.woff[r];
+template <class TEXT>
+__device__ int ex_trailing_repeats(const ExArgsPE &a, const TEXT &tx, int nt, int most, uint32_t lane) {
     const int k = a.k, S = min(nt, most);
     int count = 0;
     for (int base = 0; base < S; base += 64) {
@@ -244,12 +268,12 @@ __device__ int ex_trailing_repeats(const ExArgsPE &a, int64_t r, int nt, int mos
         if (t < S) {
             const uint32_t p = (uint32_t)(a.direction ? t : nt - 1 - t);           // the k-mer's place in the text
             int fb = 0;                                           // letters before the first one outside ACGTU
-            while (fb < k && ((vw[(p + (uint32_t)fb) >> 5] >> ((p + (uint32_t)fb) & 31u)) & 1u)) ++fb;
-            if (fb == k) verdict = window_is_repeat(cw32, p, k, a.t1, a.t2, a.t3) ? 1 : 0;
+            while (fb < k && tx.usable(p + (uint32_t)fb)) ++fb;
+            if (fb == k) verdict = tx.window_is_repeat(p, k, a.t1, a.t2, a.t3) ? 1 : 0;
             else {
                 int c4[4] = {0, 0, 0, 0};
                 for (int j = 0; j < fb; ++j) {
-                    const uint32_t c = base_at(cw32, p + (uint32_t)j);
+                    const uint32_t c = tx.code(p + (uint32_t)j);
                     c4[0] += c == 0u; c4[1] += c == 1u; c4[2] += c == 2u; c4[3] += c == 3u;
                 }
                 verdict = max(max(c4[0], c4[1]), max(c4[2], c4[3])) >= a.t1 ? 1 : 2;
@@ -272,8 +296,9 @@ __device__ int ex_trailing_repeats(const ExArgsPE &a, int64_t r, int nt, int mos
 //   Rows (the layout above, D >= d).  A walk adds at most max(bound, 0) + 1 k-mers.  First level: candidate + walk <= max(M, 0) + 2 <= d
 // entries for every d >= 2 and every M <= d - 2, negative M included (2 <= d).  Second level: bound M - gap <= d - 3, so next candidate +
 // walk <= max(d - 3, 0) + 2 = max(d - 1, 2) <= d + 2 entries.  The SE step's bounds are d - 2 and d - gap: d and d + 1 entries.
-template <bool PE>
-__device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t lane) {
+//   tx: the sequence's letters (ExBatchText, ExRowText); ex_one below is the step over the piece's batch.
+template <bool PE, class TEXT>
+__device__ void ex_one_on(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t lane, const TEXT &tx) {
     const int k = a.k, d = a.d, D = a.D;
     const int64_t k0 = a.kof[r];
     const int nt = (int)(a.kof[r + 1] - k0);
@@ -294,16 +319,14 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
 
     // the last k-mer's bases in walking order, four a byte (lane l packs bases 4 l .. 4 l + 3); one outside ACGTU ends the sequence
     {
-        const uint64_t *cw = a.codes + a.woff[r];
-        const uint32_t *vw = a.valid + a.woff[r];
         uint32_t byte = 0;
         bool bad = false;
         for (int j = 0; j < 4; ++j) {
             const int q = 4 * (int)lane + j;
             if (q < k) {
                 const uint32_t p = (uint32_t)(a.direction ? k - 1 - q : nt - 1 + q);
-                bad = bad || !((vw[p >> 5] >> (p & 31u)) & 1u);
-                byte |= ((uint32_t)(cw[p >> 5] >> (2u * (p & 31u))) & 3u) << (2 * j);
+                bad = bad || !tx.usable(p);
+                byte |= tx.seed_code(p) << (2 * j);
             }
         }
         if (4 * (int)lane < k) seed[lane] = (uint8_t)byte;
@@ -316,7 +339,7 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
     // PE: the repeat scan, used below only where there are two or more candidates.  It runs here, for every sequence, because nothing of the
     // walks is held in registers yet (behind the candidates' probes it costs the kernel a dozen registers); one round of a lane per k-mer as a rule
     int rep = 0;
-    if constexpr (PE) rep = ex_trailing_repeats(a, r, nt, d - 2, lane);
+    if constexpr (PE) rep = ex_trailing_repeats(a, tx, nt, d - 2, lane);
     const float min_cov = a.floors[r];
 
     // candidates: neighbours of the last k-mer with count >= 1, whatever the floor (Kmer.getSuccessors(k, numHash, graph), R/graph/Kmer.java:228-230)
@@ -465,6 +488,10 @@ __device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t l
     if (b_level == 1) ex_emit(a, r, ExChain{seed, l1b + c * S1, l1b + c * S1, k, EX_NO_GAP}, ExCodes{l1c + c * D, l1c + c * D, EX_NO_GAP, b_len}, b_len, lane);
     else ex_emit(a, r, ExChain{seed, l1b + c * S1, l2b + w * S2, k, len1[c]}, ExCodes{l1c + c * D, l2c + w * C2, len1[c], b_len}, b_len, lane);
     if (lane == 0) ex_put<PE>(a, r, b_level == 1 ? RB_EXT_FIRST : RB_EXT_SECOND, RB_EXT_WHY_FOUND, n_cand, b_len, b_pairs, b_fpairs, b_last, b_win, best, M);
+}
+template <bool PE>
+__device__ void ex_one(const ExArgsT<PE> &a, int64_t r, uint8_t *row, uint32_t lane) {
+    ex_one_on<PE>(a, r, row, lane, ExBatchText{a.codes, a.valid, a.woff + r});
 }
 
 }  // namespace

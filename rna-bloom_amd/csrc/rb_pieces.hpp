@@ -133,7 +133,7 @@ public:
     }
 private:
     template <typename Body>
-    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, int64_t, Body &&, int);
+    friend void for_each_host_piece(rb_graph *, hipStream_t, const char *, const int64_t *, const int64_t *, int64_t, const char *, int64_t, Body &&, int, const int64_t *);
     friend struct PieceRows;
     const char *seq = nullptr;
     const int64_t *offsets = nullptr, *ko = nullptr;
@@ -143,12 +143,13 @@ private:
 
 // The upper layer: body(piece) for every piece of <= piece_dflt k-mers of n records of host text that has a k-mer at all.  A record is `unit`
 // sequences (1; a read pair: 2) of seq / offsets; ko: kmer_offsets of the unit * n sequences.  The piece keeps its lazily uploaded batch.
+// cost (n + 1 prefix sums, or nullptr): what the pieces are cut by where a record's scratch does not follow its k-mers (a sequence that grows).
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
-                         int64_t piece_dflt, Body &&body, int unit) {
+                         int64_t piece_dflt, Body &&body, int unit, const int64_t *cost) {
     HostPiece pc;
     pc.seq = seq; pc.offsets = offsets; pc.ko = ko; pc.unit = unit;
-    for_each_piece(g, s, [&](int64_t i) { return ko[unit * i]; }, n, piece_dflt, prof_name, pc, [&](HostPiece &hp) {
+    for_each_piece(g, s, [&](int64_t i) { return cost ? cost[i] : ko[unit * i]; }, n, piece_dflt, prof_name, pc, [&](HostPiece &hp) {
         hp.pt = ko[unit * hp.rb] - ko[unit * hp.ra];
         if (hp.pt == 0) return;
         body(hp);
@@ -159,13 +160,13 @@ void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int6
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
                          int64_t piece_dflt, Body &&body) {
-    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, piece_dflt, std::forward<Body>(body), 1);
+    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, piece_dflt, std::forward<Body>(body), 1, nullptr);
 }
 // ... with the usual pieces of 16 M k-mers
 template <typename Body>
 void for_each_host_piece(rb_graph *g, hipStream_t s, const char *seq, const int64_t *offsets, const int64_t *ko, int64_t n, const char *prof_name,
                          Body &&body, int unit = 1) {
-    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, (int64_t)16 << 20, std::forward<Body>(body), unit);
+    for_each_host_piece(g, s, seq, offsets, ko, n, prof_name, (int64_t)16 << 20, std::forward<Body>(body), unit, nullptr);
 }
 
 // A piece's getKmers rows as its kernel reads them: the k-mer offsets of its unit * pn sequences (kof[0] = 0), both strands' hashes and the

@@ -17,14 +17,15 @@ __device__ __forceinline__ uint32_t base_at(const uint32_t *cw32, uint32_t b) { 
 __device__ __forceinline__ void vote(uint32_t &cand, uint32_t &cnt, uint32_t d) {
     if (cnt == 0u) { cand = d; cnt = 1u; } else if (cand == d) ++cnt; else --cnt;
 }
-__device__ bool window_is_repeat(const uint32_t *cw32, uint32_t b0, int k, int t1, int t2, int t3) {
+// base(j): the 2-bit code of the window's letter j — a batch's packed codes (window_is_repeat below) or a walk's row of a code a byte
+template <class BASE> __device__ __forceinline__ bool window_is_repeat_of(BASE base, int k, int t1, int t2, int t3) {
     uint32_t cnt_ac = 0, cnt_gt = 0;                                 // base counts, 16 bits each
     uint32_t d0 = 0, d1 = 0, dn0 = 0, dn1 = 0;                       // dinucleotide candidates / votes, phases 0 1
     uint32_t e0 = 0, e1 = 0, e2 = 0, en0 = 0, en1 = 0, en2 = 0;      // trinucleotide candidates / votes, phases 0 1 2
     uint32_t p1 = 0, p2 = 0;                                         // the previous two bases
     uint32_t ph3 = 0;                                                // (j - 2) mod 3
     for (int j = 0; j < k; ++j) {
-        const uint32_t c = base_at(cw32, b0 + (uint32_t)j);
+        const uint32_t c = base(j);
         if (c & 2u) cnt_gt += 1u << (16u * (c & 1u)); else cnt_ac += 1u << (16u * (c & 1u));
         if (j >= 1) {
             const uint32_t d = (p1 << 2) | c;
@@ -42,7 +43,7 @@ __device__ bool window_is_repeat(const uint32_t *cw32, uint32_t b0, int k, int t
     uint32_t n20 = 0, n21 = 0, n30 = 0, n31 = 0, n32 = 0;
     p1 = p2 = 0; ph3 = 0;
     for (int j = 0; j < k; ++j) {
-        const uint32_t c = base_at(cw32, b0 + (uint32_t)j);
+        const uint32_t c = base(j);
         if (j >= 1) {
             const uint32_t d = (p1 << 2) | c;
             if ((uint32_t)(j - 1) & 1u) n21 += d == d1 ? 1u : 0u; else n20 += d == d0 ? 1u : 0u;
@@ -57,6 +58,9 @@ __device__ bool window_is_repeat(const uint32_t *cw32, uint32_t b0, int k, int t
     // a phase with no element never returns (the reference's loop does not run); with elements, its majority's count decides
     return (k > 1 && (int)n20 >= t2) || (k > 2 && (int)n21 >= t2) ||
            (k > 2 && (int)n30 >= t3) || (k > 3 && (int)n31 >= t3) || (k > 4 && (int)n32 >= t3);
+}
+__device__ bool window_is_repeat(const uint32_t *cw32, uint32_t b0, int k, int t1, int t2, int t3) {
+    return window_is_repeat_of([&](int j) { return base_at(cw32, b0 + (uint32_t)j); }, k, t1, t2, t3);
 }
 
 }  // namespace rb

@@ -36,6 +36,15 @@ TRIM_FOUND, TRIM_TRIMMED, TRIM_NOT_JUDGED = 1, 2, 32
 # rb_graph_correct_long: rb_long_rec.status, rb_long_rec.flags
 LONG_NULL, LONG_UNCHANGED, LONG_CHANGED, LONG_NO_KMER = range(4)
 LONG_OVERFLOW, LONG_TRIMMED_TO_NOTHING = 1, 2
+# rb_graph_extend_loop: which; rb_extend_loop_rec.status, why, left_end / right_end; the record's fields (64 bytes; a numpy dtype is made of them)
+EXTL_SE, EXTL_PE = 0, 1
+EXTL_DONE, EXTL_ROOM, EXTL_NOT_JUDGED = range(3)
+EXTL_WHY_NONE, EXTL_WHY_NO_KMER, EXTL_WHY_LETTER = range(3)
+EXTL_END_NOT_RUN, EXTL_END_NOTHING, EXTL_END_USED_SHORT, EXTL_END_USED_PAIR, EXTL_END_ROOM = range(5)
+EXTL_REC_FIELDS = [("status", "<i4"), ("why", "<i4"), ("left_ext", "<i4"), ("right_ext", "<i4"), ("out_len", "<i4"), ("left_end", "<i4"),
+                   ("right_end", "<i4"), ("left_rounds", "<i4"), ("right_rounds", "<i4"), ("steps", "<i4"), ("floor_drops", "<i4"),
+                   ("used_passed", "<i4"), ("left_floor", "<f4"), ("right_floor", "<f4"), ("pad", "<i4", (2,))]
+EXTL_MAX_ROOM = 1 << 24
 
 
 class GraphParams(C.Structure):
@@ -136,6 +145,7 @@ SYMBOLS = [
     ("rb_graph_overlap_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_extend_se", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    ("rb_graph_extend_loop", _i32, [_vp, _i32, _vp, _vp, _i64, _vp, C.c_float, _i32, _vp, _vp, _vp]),
     ("rb_graph_join_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_connect_segments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),

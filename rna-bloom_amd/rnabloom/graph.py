@@ -732,6 +732,40 @@ class BloomFilterDeBruijnGraph:
         bases, recs, _ = self.extendStepPEFlat(seq, off, direction, minKmerCov)
         return [bases[i, :rc["out_len"]].tobytes() if rc["outcome"] != self.EXT_NONE else None for i, rc in enumerate(recs)], recs
 
+    EXTL_DTYPE = np.dtype(N.EXTL_REC_FIELDS)
+    EXTL_SE, EXTL_PE = N.EXTL_SE, N.EXTL_PE
+    EXTL_DONE, EXTL_ROOM, EXTL_NOT_JUDGED = N.EXTL_DONE, N.EXTL_ROOM, N.EXTL_NOT_JUDGED
+    EXTL_STATUSES = ("done", "room", "not_judged")
+    EXTL_WHYS = ("none", "no_kmer", "letter")
+    EXTL_ENDS = ("not_run", "nothing", "used_short", "used_pair", "room")
+
+    def extendLoopFlat(self, seq, offsets, which, minKmerCov, room, phase=None):
+        """rb_graph_extend_loop on flat host text (GraphUtils.extendSE, which = EXTL_SE, and extendPE, EXTL_PE, R/util/GraphUtils.java:6454-6678):
+        sequence i is seq[offsets[i]:offsets[i + 1]] (uint8); room is the most letters the call adds on each side of a sequence; phase (uint8
+        per sequence, or None) 0 runs both sides, 1 the right side only.  Returns (out, out_offsets, recs): one EXTL_DTYPE record per sequence,
+        its text at out[out_offsets[i]:out_offsets[i] + recs[i]["out_len"]].  Read-only."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        ph = None if phase is None else np.ascontiguousarray(phase, dtype=np.uint8)
+        oo = np.zeros(n + 1, np.int64)
+        args = (self.h, which, _ptr(seq), _ptr(off), n, _ptr(ph), minKmerCov, room, _ptr(oo))
+        check(lib.rb_graph_extend_loop(*args, None, None))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        recs = np.zeros(n, self.EXTL_DTYPE)
+        check(lib.rb_graph_extend_loop(*args, _ptr(out), _ptr(recs)))
+        return out, oo, recs
+
+    def extendLoop(self, seqs, which, minKmerCov, room, phase=None):
+        """GraphUtils.extendSE / extendPE of each sequence's getKmers list on the device, in one call: (texts, recs).  A sequence whose record
+        says EXTL_ROOM wants a further call with the returned text (phase 1 where its right side ran out of room), one that says
+        EXTL_NOT_JUDGED (fewer than k letters, a letter other than upper-case A C G T) comes back as it went in: graphutils.extendSEOnDevice /
+        extendPEOnDevice do both."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        out, oo, recs = self.extendLoopFlat(seq, off, which, minKmerCov, room, phase)
+        return [out[oo[i]:oo[i] + rc["out_len"]].tobytes() for i, rc in enumerate(recs)], recs
+
     SCREEN_DTYPE = np.dtype([("flags", "<i4"), ("chim_why", "<i4"), ("break_i", "<i4"), ("break_j", "<i4"), ("right_len", "<i4"), ("left_len", "<i4"),
                              ("blunt_why", "<i4"), ("boundary", "<i4")])
     SCREEN_BRANCH_FREE, SCREEN_CHIMERA, SCREEN_BLUNT_END = N.SCREEN_BRANCH_FREE, N.SCREEN_CHIMERA, N.SCREEN_BLUNT_END

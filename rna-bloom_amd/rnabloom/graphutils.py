@@ -245,15 +245,56 @@ def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
     ONE graph.extendStepSE call per round for all sequences still growing, each with its own floor max(minKmerCov, min count of its last d
     k-mers * 0.1), lowered by a further * 0.1 while the step returns nothing; the counts come from graph.getKmers of the sequences' ends.
     Returns (extended sequences, [leftExtLen, leftExtLen + origLen] per sequence, in k-mers).  The reference's loop has no bound;
-    max_rounds raises instead of looping forever."""
+    max_rounds raises instead of looping forever.  extendSEOnDevice is the same in one device call for all rounds."""
     return _extend_loop(graph, seqs, minKmerCov, max_rounds, graph.getReadPairedKmerDistance(), graph.extendStepSE, "extendSE")
 
 
 def extendPE(graph, seqs, minKmerCov, max_rounds=100000):
     """GraphUtils.extendPE (R/util/GraphUtils.java:6567-6678), the loop the transcript stage runs whenever fragment-paired k-mers exist
     (R/RNABloom.java:1846-1851): extendSE's loop with d = the FRAGMENT-paired k-mer distance and extendLeftPE / extendRightPE as the step
-    (graph.extendStepPE, one call per round).  A step the reference's isRepeat would throw in counts as one that returns nothing."""
+    (graph.extendStepPE, one call per round).  A step the reference's isRepeat would throw in counts as one that returns nothing.
+    extendPEOnDevice is the same in one device call for all rounds."""
     return _extend_loop(graph, seqs, minKmerCov, max_rounds, graph.getFragPairedKmerDistance(), graph.extendStepPE, "extendPE")
+
+
+def extendSEOnDevice(graph, seqs, minKmerCov, room=4096):
+    """extendSE with the whole loop on the device (graph.extendLoop, rb_graph_extend_loop): what extendSE returns — the extended sequences and
+    [leftExtLen, leftExtLen + origLen] per sequence — from ONE call for all rounds of all sequences.  room is the most letters a call adds on
+    each side of a sequence; the few sequences that want more get further calls, with the room doubled each time.  A sequence the device does
+    not judge (a letter other than upper-case A C G T) goes through extendSE's host loop, in one call for all of them."""
+    return _extend_on_device(graph, seqs, minKmerCov, room, graph.EXTL_SE, extendSE)
+
+
+def extendPEOnDevice(graph, seqs, minKmerCov, room=4096):
+    """extendPE with the whole loop on the device: as extendSEOnDevice, with the fragment-paired distance and step."""
+    return _extend_on_device(graph, seqs, minKmerCov, room, graph.EXTL_PE, extendPE)
+
+
+def _extend_on_device(graph, seqs, minKmerCov, room, which, host_loop):
+    k = graph.k
+    texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    n0 = [max(len(t) - k + 1, 0) for t in texts]
+    left = [0] * len(texts)
+    todo, phase, host = list(range(len(texts))), None, []
+    while todo:
+        got, recs = graph.extendLoop([texts[i] for i in todo], which, minKmerCov, room, phase)
+        nxt, phase = [], []
+        for i, t, rc in zip(todo, got, recs):
+            status = int(rc["status"])
+            if status == graph.EXTL_NOT_JUDGED:
+                host.append(i)
+                continue
+            texts[i] = t
+            left[i] += int(rc["left_ext"])
+            if status == graph.EXTL_ROOM:                       # resume where the whole rounds ended: the right side only once the left side has ended
+                nxt.append(i)
+                phase.append(0 if int(rc["left_end"]) == N.EXTL_END_ROOM else 1)
+        todo, room = nxt, min(2 * room, N.EXTL_MAX_ROOM)
+    if host:
+        got, ranges = host_loop(graph, [texts[i] for i in host], minKmerCov)
+        for i, t, r in zip(host, got, ranges):
+            texts[i], left[i] = t, r[0]
+    return texts, [[l, l + n] for l, n in zip(left, n0)]
 
 
 def _extend_loop(graph, seqs, minKmerCov, max_rounds, d, step, who):
