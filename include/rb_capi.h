@@ -358,6 +358,76 @@ typedef struct rb_corr_gap {            /* 20 bytes */
 } rb_corr_gap;
 int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, const rb_corr_params *p,
                             int64_t *out_offsets, char *out_seq, int32_t *out_len, uint32_t *flags, rb_corr_gap *gaps, int64_t *gap_offsets);
+/* Error correction of read pairs, every round inside the call — GraphUtils.correctErrorsPE (R/util/GraphUtils.java:4051-4182), which the
+ * FragmentAssembler runs on every pair between connect and overlapAndConnect (R/RNABloom.java:2086-2235), and, with rseq == NULL,
+ * GraphUtils.correctErrorsSE (:3998-4049), the single-end worker's (R/RNABloom.java:1980-2001).  Read-only on the graph.  Texts, hash rows and
+ * counts stay on the device between rounds; the input goes up once and the final texts come back once.
+ *   Pair i is left = lseq[loffsets[i], loffsets[i+1]) and right = rseq[roffsets[i], roffsets[i+1]).  The count profile of a mate is getKmers' of its
+ *   current text, as in rb_graph_correct_errors: every window, count 0 where a letter is outside ACGTU.
+ *   A round of the pair form (the loop :4066-4179): nFP = (int) Math.round(max(nL, nR) * cov_fpr) from the CURRENT lists (:4071); per mate the
+ *   sorted counts are walked down from startIndex = n - 1, lowered by nFP only if startIndex > nFP (:4084-4087): the threshold is covs[startIndex],
+ *   then covs[i] for i = startIndex - 1 .. 0 until threshold * max_cov_gradient >= covs[i] (found; float32, one operation) (:4088-4097, :4118-4126).
+ *   The pair's threshold (:4129-4143): both found -> the smaller; one found -> that one if it is <= the other mate's (which is its covs[0]); else -1.
+ *   If threshold >= min_cov_threshold (:4145), correctErrorHelper runs on both mates with it — exactly what rb_graph_correct_errors computes, its
+ *   flag RB_CORR_CORRECTED being the reference's "non-null" — and a non-null result replaces the mate (:4155-4172).  Both null ends the loop (:4174).
+ *   A round whose threshold is below min_cov_threshold changes nothing, and the reference repeats it unchanged until the rounds run out: the call
+ *   stops the pair there (RB_PAIRC_END_LOW) with the same result.
+ *   Single form (rseq, roffsets, rout_offsets, rout all NULL): correctErrorsSE runs once if iterations > 0.  The search is rb_cov_stats.se_threshold's:
+ *   startIndex = n - 1 - nFP with nFP = (int) Math.round(n * cov_fpr), strict `>`, not found when startIndex < 0 (:4019-4035); min_cov_threshold
+ *   is not read.  The right-hand fields of the record stay 0.
+ *   recs[i]: status — RB_PAIRC_CORRECTED exactly when ReadPair.corrected is true (:4181; single form: the helper returned non-null),
+ *   RB_PAIRC_UNCHANGED, or RB_PAIRC_NOT_JUDGED; end — why the rounds ended: RB_PAIRC_END_ALL the round count ran out (iterations == 0 included),
+ *   END_NO_CHANGE both results null (:4174), END_LOW the threshold was below min_cov_threshold (single form: not found, the reference returns null),
+ *   END_NO_KMER, END_LOST_KMERS (below); rounds_run: the rounds in which the helper ran; flags: RB_PAIRC_LEFT / RIGHT leftCorrected /
+ *   rightCorrected, and the overflow bits; left_len, right_len: the lengths of the final texts; thr_first / thr_last: the bits of the pair's
+ *   threshold of round 0 and of the last round entered, -1.0f where there was none (:4129; single form: not found; no round entered);
+ *   found_first: round 0, bit 0 the left threshold was found, bit 1 the right; left_changed / right_changed: the rounds in which the helper
+ *   returned non-null for that mate; gaps_replaced / gaps_trimmed / gaps_kept (rb_corr_gap.outcome) and mismatches (replacements of the mismatch
+ *   pass), summed over rounds and mates.
+ *   Not judged, never guessed: a pair one of whose mates has no k-mer at entry is RB_PAIRC_NOT_JUDGED / END_NO_KMER (the reference throws at :4088);
+ *   in the single form an empty list is RB_PAIRC_UNCHANGED / END_NO_KMER (the reference returns null, :4007).  A mate that leaves a round with no
+ *   k-mer is NOT_JUDGED / END_LOST_KMERS (the next round would throw).  The texts of a not-judged pair come back as they went in.
+ *   iterations == 0: nothing runs; every record is RB_PAIRC_UNCHANGED / END_ALL.
+ *   Output: lout_offsets / rout_offsets (n + 1 each) are INPUTS, the caller's capacity layouts, as in rb_graph_correct_long.  A final text is written
+ *   at its offset if it fits; else the mate's overflow bit is set and nothing is written for it.  left_len / right_len are the lengths needed either
+ *   way; the computation is deterministic, so a second call with room gives the text.  Nothing is ever truncated.
+ * The call works in pieces (RB_QUERY_PIECE input k-mers of both mates, by default as rb_graph_correct_errors); a pair is never split and results
+ * do not depend on the cuts.  Device scratch of a piece: 21 bytes per input k-mer + 1.2 per letter for the first profile; then per round, for the
+ * mates still live, 21 bytes per k-mer + 1 per letter of the round's input and rb_graph_correct_errors' scratch for them (40 bytes per capacity
+ * k-mer, 60 per gap, the walks' 256 MB), the capacity being taken from the mates' actual lengths every round; 64 bytes a pair; the finished
+ * texts of a round; a gather table of 56 bytes per mate of the round.  Between rounds the host sees 4 bytes a live mate and pair (lengths, live
+ * flags) and the gap records, as the corrector does; from them it builds the compaction's gather table (source and destination offsets, 7 int64
+ * a mate) and uploads it: the rows are moved on the device, their destinations are computed on the host.  A round costs three stream
+ * synchronisations (live flags; the finished texts, where there are any; lengths) besides the corrector's own two, and the call's buffers grow
+ * by free and allocate, each a device-wide wait.  None of it is tuned.
+ * It leases a query context (re-entrant on one handle).  Profile entry "correct_pairs": the interval from a piece's first to its last kernel,
+ * the host's work between the rounds included.  RB_ERR_STATE: a sequence outgrew its slot (an internal error).
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle / loffsets / p / lout_offsets, null recs / lout (n > 0), roffsets without rout_offsets
+ * or rout, rseq / rout_offsets / rout without roffsets, text missing where there is text; a shard handle; a destroyed dbgbf or counting filter;
+ * k < 2; a float parameter that is not finite; max_cov_gradient < 0; cov_fpr outside [0, 1]; lookahead outside 1..16; max_indel_size outside
+ * 0..4096; iterations < 0; decreasing offsets (input or capacity).  n == 0 succeeds and touches nothing. */
+typedef struct rb_pairc_params {
+    int32_t iterations, lookahead, max_indel_size;      /* errorCorrectionIterations >= 0; lookahead / max_indel_size as rb_corr_params */
+    float max_cov_gradient, cov_fpr, min_cov_threshold, percent_identity, min_kmer_cov;
+} rb_pairc_params;
+enum { RB_PAIRC_UNCHANGED = 0, RB_PAIRC_CORRECTED = 1, RB_PAIRC_NOT_JUDGED = 2 };                   /* status */
+enum { RB_PAIRC_END_ALL = 0, RB_PAIRC_END_NO_CHANGE = 1, RB_PAIRC_END_LOW = 2,
+       RB_PAIRC_END_NO_KMER = 3, RB_PAIRC_END_LOST_KMERS = 4 };                                     /* end */
+#define RB_PAIRC_LEFT 1u        /* flags: leftCorrected */
+#define RB_PAIRC_RIGHT 2u       /* rightCorrected */
+#define RB_PAIRC_LEFT_OVERFLOW 4u
+#define RB_PAIRC_RIGHT_OVERFLOW 8u
+typedef struct rb_pairc_rec {   /* 64 bytes */
+    int32_t status, end, rounds_run, flags, left_len, right_len;
+    uint32_t thr_first, thr_last;          /* float bits: the pair's threshold of round 0 and of the last round entered (-1.0f: none) */
+    int32_t found_first;                   /* round 0: bit 0 left threshold found, bit 1 right */
+    int32_t left_changed, right_changed;   /* rounds in which correctErrorHelper returned non-null for that mate */
+    int32_t gaps_replaced, gaps_trimmed, gaps_kept, mismatches;   /* summed over rounds and mates */
+    int32_t reserved;                      /* 0 */
+} rb_pairc_rec;
+int rb_graph_correct_pairs(rb_graph *g, const char *lseq, const int64_t *loffsets, const char *rseq, const int64_t *roffsets, int64_t n,
+                           const rb_pairc_params *p, const int64_t *lout_offsets, char *lout, const int64_t *rout_offsets, char *rout,
+                           rb_pairc_rec *recs);
 /* Overlap of read pairs — GraphUtils.overlap (R/util/GraphUtils.java:4898-5063), the first half of overlapAndConnect (:5065-5090) that the
  * FragmentAssembler runs on every corrected pair (R/RNABloom.java:2148), over SeqUtils.overlapMaximally (R/util/SeqUtils.java:1335-1379).  A wavefront
  * per pair on the device; the call is read-only.  Pair i is left = lseq[loffsets[i], loffsets[i+1]) and right = rseq[roffsets[i], roffsets[i+1]); each

@@ -742,6 +742,90 @@ public class BloomFilterDeBruijnGraph {
         return result;
     }
 
+    public static final int PAIRC_UNCHANGED = 0, PAIRC_CORRECTED = 1, PAIRC_NOT_JUDGED = 2;
+    public static final int PAIRC_LEFT_OVERFLOW = 4, PAIRC_RIGHT_OVERFLOW = 8;
+
+    /**
+     * GraphUtils.correctErrorsPE (src/rnabloom/util/GraphUtils.java:4051-4182) for a batch of read pairs in ONE native call with every round on the
+     * device (and a second one for the few mates whose text outgrew length + 16).  lefts[i] / rights[i] are replaced by the strings the reference's
+     * ReadPair spells; the result is its `corrected` per pair.  A pair that is not judged (a mate without a k-mer: the reference throws) keeps its
+     * texts, is reported false and has status PAIRC_NOT_JUDGED in its record.  records (16 * lefts.length ints) receives the records of
+     * NativeGraph.correctPairs.  The k-mer lists are getKmers(String)'s: the worker's stretch selection comes before the call.
+     */
+    public boolean[] correctErrorsPE(String[] lefts, String[] rights, int lookahead, int maxIndelSize, float maxCovGradient, float covFPR,
+                                     int errorCorrectionIterations, float minCovThreshold, float percentIdentity, float minKmerCov, int[] records) {
+        if (lefts.length != rights.length) throw new IllegalArgumentException("correctErrorsPE: " + lefts.length + " left and " + rights.length + " right mates");
+        return correctPairs(lefts, rights, new int[]{errorCorrectionIterations, lookahead, maxIndelSize},
+                            new float[]{maxCovGradient, covFPR, minCovThreshold, percentIdentity, minKmerCov}, records, "correctErrorsPE");
+    }
+
+    /**
+     * GraphUtils.correctErrorsSE (src/rnabloom/util/GraphUtils.java:3998-4049) for a batch of reads in ONE native call.  Returns the strings the
+     * returned k-mers spell, null where the reference returns null.  records (16 * seqs.length ints) receives the records.
+     */
+    public String[] correctErrorsSE(String[] seqs, int lookahead, int maxIndelSize, float maxCovGradient, float covFPR, float percentIdentity,
+                                    float minKmerCov, int[] records) {
+        final String[] texts = seqs.clone();
+        final boolean[] corrected = correctPairs(texts, null, new int[]{1, lookahead, maxIndelSize},
+                                                 new float[]{maxCovGradient, covFPR, 0f, percentIdentity, minKmerCov}, records, "correctErrorsSE");
+        for (int i = 0; i < texts.length; ++i) if (!corrected[i]) texts[i] = null;
+        return texts;
+    }
+
+    private static ByteBuffer packText(String[] seqs, int[] todo, long[] off, String who) {
+        final int m = todo.length;
+        for (int j = 0; j < m; ++j) off[j + 1] = off[j] + seqs[todo[j]].length();
+        if (off[m] > Integer.MAX_VALUE) throw new IllegalArgumentException(who + ": more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[m], 1));
+        for (int j = 0; j < m; ++j) { final String s = seqs[todo[j]]; for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i)); }
+        return text;
+    }
+
+    private static String unpackText(ByteBuffer out, long at, int len) {
+        final byte[] b = new byte[len];
+        for (int i = 0; i < len; ++i) b[i] = out.get((int) at + i);
+        return new String(b, java.nio.charset.StandardCharsets.ISO_8859_1);
+    }
+
+    private boolean[] correctPairs(String[] lefts, String[] rights, int[] params, float[] fparams, int[] records, String who) {
+        final int n = lefts.length;
+        final boolean pe = rights != null;
+        if (records == null || records.length < 16L * n) throw new IllegalArgumentException(who + ": records must hold " + 16L * n + " ints");
+        final boolean[] corrected = new boolean[n];
+        final int[] lroom = new int[n], rroom = new int[n];
+        for (int i = 0; i < n; ++i) { lroom[i] = lefts[i].length() + 16; if (pe) rroom[i] = rights[i].length() + 16; }
+        int[] todo = new int[n];
+        for (int i = 0; i < n; ++i) todo[i] = i;
+        for (int round = 0; round < 2 && todo.length > 0; ++round) {
+            final int m = todo.length;
+            final long[] lo = new long[m + 1], loo = new long[m + 1], ro = pe ? new long[m + 1] : null, roo = pe ? new long[m + 1] : null;
+            for (int j = 0; j < m; ++j) { loo[j + 1] = loo[j] + lroom[todo[j]]; if (pe) roo[j + 1] = roo[j] + rroom[todo[j]]; }
+            if (loo[m] > Integer.MAX_VALUE || (pe && roo[m] > Integer.MAX_VALUE)) throw new IllegalArgumentException(who + ": more than 2 GB of text in one batch");
+            final ByteBuffer ltext = packText(lefts, todo, lo, who), rtext = pe ? packText(rights, todo, ro, who) : null;
+            final ByteBuffer lout = ByteBuffer.allocateDirect(Math.max((int) loo[m], 1)), rout = pe ? ByteBuffer.allocateDirect(Math.max((int) roo[m], 1)) : null;
+            final int[] recs = new int[16 * m];
+            NativeGraph.correctPairs(handle, ltext, lo, rtext, ro, m, params, fparams, loo, lout, roo, rout, recs);
+            int again = 0;
+            for (int j = 0; j < m; ++j) {
+                final int i = todo[j];
+                System.arraycopy(recs, 16 * j, records, 16 * i, 16);
+                if ((recs[16 * j + 3] & (PAIRC_LEFT_OVERFLOW | PAIRC_RIGHT_OVERFLOW)) != 0) {
+                    lroom[i] = Math.max(lroom[i], recs[16 * j + 4]);
+                    if (pe) rroom[i] = Math.max(rroom[i], recs[16 * j + 5]);
+                    todo[again++] = i;
+                    continue;
+                }
+                corrected[i] = recs[16 * j] == PAIRC_CORRECTED;
+                if (!corrected[i]) continue;
+                lefts[i] = unpackText(lout, loo[j], recs[16 * j + 4]);
+                if (pe) rights[i] = unpackText(rout, roo[j], recs[16 * j + 5]);
+            }
+            todo = java.util.Arrays.copyOf(todo, again);
+        }
+        if (todo.length > 0) throw new IllegalStateException(who + ": " + todo.length + " pairs overflowed the room their own records asked for");
+        return corrected;
+    }
+
     public ArrayList<Kmer> getKmers(String seq) { return getKmers(seq, 0, seq.length()); }
 
     public ArrayList<Kmer> getKmers(String seq, int start, int end) {

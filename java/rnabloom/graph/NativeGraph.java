@@ -212,6 +212,16 @@ public final class NativeGraph {
      *  written, 2: trimmed to nothing).  Read-only. */
     public static native void correctLong(long h, ByteBuffer seq, long[] offsets, int n, int[] params, float maxCovGradient, float percentIdentity,
                                           long[] outOffsets, ByteBuffer out, int[] recs);
+    /** GraphUtils.correctErrorsPE (rb_graph_correct_pairs, R/util/GraphUtils.java:4051-4182) of n read pairs, every round inside the call; with
+     *  rseq, roffsets, routOffsets and rout all null, GraphUtils.correctErrorsSE (:3998-4049) of n reads.  params: errorCorrectionIterations,
+     *  lookahead, maxIndelSize; fparams: maxCovGradient, covFPR, minCovThreshold, percentIdentity, minKmerCov.  loutOffsets / routOffsets (n + 1)
+     *  are the caller's capacity layouts: a final text is written at its offset if it fits.  recs holds 16 ints per pair — status (0 unchanged,
+     *  1 corrected, 2 not judged), end (0 the rounds ran out, 1 nothing changed, 2 threshold too low, 3 a mate without a k-mer, 4 a mate lost
+     *  its k-mers), the rounds the helper ran in, flags (1 left corrected, 2 right corrected, 4 / 8: the left / right text did not fit and was
+     *  not written), the final lengths (the room needed, where it did not fit), the float bits of the first and last threshold, the found bits
+     *  of round 0, the rounds that changed the left / right mate, gaps replaced / trimmed / kept, mismatches, 0 (include/rb_capi.h).  Read-only. */
+    public static native void correctPairs(long h, ByteBuffer lseq, long[] loffsets, ByteBuffer rseq, long[] roffsets, int n, int[] params,
+                                           float[] fparams, long[] loutOffsets, ByteBuffer lout, long[] routOffsets, ByteBuffer rout, int[] recs);
     /** getKmers of nReads sequences: koffsets[nReads + 1] is filled; pass f == null to size the outputs first. */
     public static native void getKmers(long h, ByteBuffer seq, long[] offsets, int nReads, long[] koffsets, long[] f, long[] r, float[] count);
     public static native void neighbors(long h, long[] f, long[] r, byte[] charOut, int n, int direction, long[] f4, long[] r4, float[] count4);

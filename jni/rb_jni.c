@@ -593,6 +593,30 @@ void FN(correctLong)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offse
     lr(e, offsets, po, JNI_ABORT); lr(e, outOffsets, poo, JNI_ABORT); ir(e, recs, rc16, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_correct_pairs: params holds iterations, lookahead, max_indel_size; fparams max_cov_gradient, cov_fpr, min_cov_threshold, percent_identity,
+ * min_kmer_cov; a record (rb_pairc_rec, 64 bytes) is 16 ints to Java.  rseq, roffsets, routOffsets and rout all null: the single form */
+void FN(correctPairs)(JNIEnv *e, jclass c, jlong h, jobject lseq, jlongArray loffsets, jobject rseq, jlongArray roffsets, jint n, jintArray params,
+                      jfloatArray fparams, jlongArray loutOffsets, jobject lout, jlongArray routOffsets, jobject rout, jintArray recs) {
+    (void)c;
+    if (n < 0 || !params || (*e)->GetArrayLength(e, params) < 3 || !fparams || (*e)->GetArrayLength(e, fparams) < 5 ||
+        (n > 0 && (!loffsets || !loutOffsets || !recs || (*e)->GetArrayLength(e, loffsets) <= n || (*e)->GetArrayLength(e, loutOffsets) <= n ||
+                   (roffsets && (*e)->GetArrayLength(e, roffsets) <= n) || (routOffsets && (*e)->GetArrayLength(e, routOffsets) <= n) ||
+                   (*e)->GetArrayLength(e, recs) / 16 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "correctPairs: an array is too short for n pairs");
+        return;
+    }
+    jint *pp = ia(e, params);
+    jfloat *fp = fa(e, fparams);
+    rb_pairc_params p = {pp[0], pp[1], pp[2], fp[0], fp[1], fp[2], fp[3], fp[4]};
+    ir(e, params, pp, JNI_ABORT); fr(e, fparams, fp, JNI_ABORT);
+    jlong *plo = la(e, loffsets), *pro = la(e, roffsets), *ploo = la(e, loutOffsets), *proo = la(e, routOffsets);
+    jint *rc16 = ia(e, recs);
+    int rc = rb_graph_correct_pairs(G(h), (const char *)direct(e, lseq), (const int64_t *)plo, (const char *)direct(e, rseq), (const int64_t *)pro, n, &p,
+                                    (const int64_t *)ploo, (char *)direct(e, lout), (const int64_t *)proo, (char *)direct(e, rout), (rb_pairc_rec *)rc16);
+    lr(e, loffsets, plo, JNI_ABORT); lr(e, roffsets, pro, JNI_ABORT); lr(e, loutOffsets, ploo, JNI_ABORT); lr(e, routOffsets, proo, JNI_ABORT);
+    ir(e, recs, rc16, 0);
+    if (rc) throw_rc(e, rc);
+}
 void FN(neighbors)(JNIEnv *e, jclass c, jlong h, jlongArray f, jlongArray r, jbyteArray ch, jint n, jint direction, jlongArray f4, jlongArray r4, jfloatArray c4) {
     jlong *pf = la(e, f), *pr = la(e, r), *of = la(e, f4), *orr = la(e, r4);
     jbyte *pc = ba(e, ch);

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rb_pieces.hpp"
+#include "rb_correct.hpp"
 #include "rb_lookup.hpp"
 #include "rb_align.hpp"
 #include "rb_wave.hpp"
@@ -31,7 +32,6 @@ namespace {
 
 constexpr int CE_TPB = 256;
 constexpr int CE_WAVES = CE_TPB / 64;         // sequences / gaps per workgroup: a wavefront each
-constexpr int CE_MAX_INDEL = 4096;               // the largest max_indel_size taken (the reference's default is 1)
 constexpr size_t WALK_CHUNK_BYTES = (size_t)256 << 20;      // device scratch of the walks that run together
 
 static_assert(sizeof(rb_corr_gap) == 20, "rb_corr_gap is 20 bytes");
@@ -413,12 +413,6 @@ __global__ void __launch_bounds__(CE_TPB) k_text_kmers(FilterView fv, int strand
     }
 }
 
-// a bump allocator over one device buffer
-struct Arena {
-    uint8_t *base = nullptr;
-    size_t at = 0;
-    template <typename T> T *take(size_t n) { T *p = reinterpret_cast<T *>(base + at); at = up16(at + n * sizeof(T)); return p; }
-};
 // the arrays of a piece in the context's arena; lay() is run once on an empty arena for the size and once on the buffer
 struct PieceArrays {
     float *cnt, *thr, *cnt2;            // getKmers counts of the input [pt], thresholds [pn], counts of the stitched text [cpt]
@@ -433,39 +427,244 @@ struct PieceArrays {
         over = a.take<uint32_t>(4);
     }
 };
-struct PhaseTimer {                       // device time per phase of the call, summed over pieces and chunks (profiling on)
-    static constexpr int N = 6;
-    const char *names[N] = {"correct_errors.profile", "correct_errors.scan", "correct_errors.walks", "correct_errors.resolve", "correct_errors.stitch",
-                            "correct_errors.mismatch"};
-    bool on = false;
-    hipStream_t s = nullptr;
-    struct Span { int phase; Event e0, e1; };
-    std::vector<Span> spans;
-    double ms[N] = {0, 0, 0, 0, 0, 0};
-    int64_t launches[N] = {0, 0, 0, 0, 0, 0};
-    void begin(int phase) {
-        if (!on) return;
-        spans.emplace_back();
-        spans.back().phase = phase;
-        RB_HIP(hipEventCreate(&spans.back().e0.e));
-        RB_HIP(hipEventCreate(&spans.back().e1.e));
-        RB_HIP(hipEventRecord(spans.back().e0, s));
-    }
-    void end() { if (on) RB_HIP(hipEventRecord(spans.back().e1, s)); }
-    void collect() {                      // the stream is idle
-        for (Span &sp : spans) { float t = 0; RB_HIP(hipEventElapsedTime(&t, sp.e0, sp.e1)); ms[sp.phase] += t; ++launches[sp.phase]; }
-        spans.clear();
-    }
-};
-
-// the most letters sequence of `len` letters can have after gap repair: see rb_capi.h
-inline int64_t corr_capacity(int64_t len, int64_t k, int64_t max_indel) {
-    const int64_t nk = len >= k ? len - k + 1 : 0;
-    if (nk <= 0) return len;
-    return len + ((nk - 1) / 2) * max_indel + ((nk - 1) / (k + 1)) * 2;
-}
 
 }  // namespace
+
+void rb::launch_text_kmers(rb_graph *g, int64_t pn, const int64_t *tof, const int64_t *kof, const uint32_t *woff, const uint8_t *txt, const int32_t *len,
+                           uint32_t *valid, uint64_t *F, uint64_t *R, float *cnt, hipStream_t s) {
+    hipLaunchKernelGGL(k_text_kmers, dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, g->view(0, 0), (int)g->stranded, g->k, pn, tof, kof, woff, txt, len,
+                       valid, F, R, cnt);
+    RB_HIP(hipGetLastError());
+}
+
+void rb::CorrBody::prepare(int64_t pn_, const int64_t *kof, const int64_t *tof, const int64_t *ctof) {
+    const int k = g->k;
+    const int lds_row = rb::mismatch_lds_row();
+    pn = pn_;
+    pt = kof[pn] - kof[0]; tb = tof[pn] - tof[0]; ctb = ctof[pn] - ctof[0];
+    // the piece's table: k-mer offsets, text offsets, capacity text offsets, capacity k-mer offsets [pn + 1 each], the sequences whose
+    // capacity has more k-mers than a code row in LDS; then the capacity word offsets of the usable-letter bits
+    tab.assign((size_t)(4 * pn + 4), 0);
+    cwoff.assign((size_t)pn + 1, 0);
+    std::vector<int64_t> longs;
+    {
+        int64_t *t_kof = tab.data(), *t_tof = t_kof + pn + 1, *t_ctof = t_tof + pn + 1, *t_ckof = t_ctof + pn + 1;
+        for (int64_t i = 0; i <= pn; ++i) {
+            t_kof[i] = kof[i] - kof[0];
+            t_tof[i] = tof[i] - tof[0];
+            t_ctof[i] = ctof[i] - ctof[0];
+        }
+        for (int64_t i = 0; i < pn; ++i) {
+            const int64_t cl = t_ctof[i + 1] - t_ctof[i], cnk = cl >= k ? cl - k + 1 : 0;
+            t_ckof[i + 1] = t_ckof[i] + cnk;
+            cwoff[(size_t)i + 1] = cwoff[(size_t)i] + (uint32_t)((cl + 31) / 32);
+            if (cnk > lds_row) longs.push_back(i);
+        }
+        cpt = t_ckof[pn];
+    }
+    RB_REQUIRE(cpt < ((int64_t)1 << 40) && (int64_t)cwoff[(size_t)pn] * 32 < ((int64_t)1 << 36), "%s: piece too large", who);
+    tab.insert(tab.end(), longs.begin(), longs.end());            // (the pointers above are gone: this may move the table)
+    nlong = (int64_t)tab.size() - (4 * pn + 4);
+    const size_t tab_bytes = up16(tab.size() * 8);
+    c->b0.reserve(tab_bytes + (size_t)(pn + 1) * 4 + 16);
+    c->b1.reserve((size_t)cpt * 8 + 16);
+    c->b2.reserve((size_t)cpt * 8 + 16);
+    PieceArrays pa;
+    Arena ar;
+    const int64_t in_pt = own_input ? pt : 0, in_tb = own_input ? tb : 0;
+    pa.lay(ar, in_pt, pn, in_tb, ctb, cpt, nlong != 0, (size_t)cwoff[(size_t)pn] + 1);
+    c->b3.reserve(ar.at + 64);
+    ar.base = c->b3.as<uint8_t>(); ar.at = 0;
+    pa.lay(ar, in_pt, pn, in_tb, ctb, cpt, nlong != 0, (size_t)cwoff[(size_t)pn] + 1);
+    dcnt2 = pa.cnt2; dng = pa.ngap; dclen = pa.clen; dcnk = pa.cnk; dnf = pa.nf;
+    dctxt = pa.ctxt; drow = pa.row; dflags = pa.flags; dvalid = pa.valid; dover = pa.over;
+    uint8_t *b0 = c->b0.as<uint8_t>();
+    dkof = reinterpret_cast<const int64_t *>(b0); dtof = dkof + pn + 1; dctof = dtof + pn + 1; dckof = dctof + pn + 1; dids = dckof + pn + 1;
+    dcwoff = reinterpret_cast<const uint32_t *>(b0 + tab_bytes);
+    dF = c->b1.as<uint64_t>(); dR = c->b2.as<uint64_t>();
+    own_txt = own_input ? pa.txt : nullptr; own_cnt = own_input ? pa.cnt : nullptr; own_thr = own_input ? pa.thr : nullptr;
+    if (own_input) { dtxt = own_txt; dcnt = own_cnt; dthr = own_thr; dFin = dF; dRin = dR; }
+    RB_HIP(hipMemcpyAsync(b0, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+    RB_HIP(hipMemcpyAsync(b0 + tab_bytes, cwoff.data(), cwoff.size() * 4, hipMemcpyHostToDevice, s));
+    RB_HIP(hipMemsetAsync(dctxt, 0, (size_t)ctb, s));
+    RB_HIP(hipMemsetAsync(dover, 0, 16, s));
+}
+
+void rb::CorrBody::run() {
+    const int k = g->k, max_indel = p.max_indel_size, lookahead = p.lookahead;
+    const float min_cov = p.min_kmer_cov, pid = p.percent_identity;
+    const FilterView fv = g->view(0, 0);
+    CorrPhaseTimer &ph = *this->ph;
+    DevBuf &gbuf = *this->gbuf, &wbuf = *this->wbuf;
+    const uint8_t *dtxt = this->dtxt;
+    const float *dcnt = this->dcnt;
+    // 1. the number of gaps per sequence
+    ph.begin(1);
+    hipLaunchKernelGGL((k_gap_scan<false>), dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dkof, dcnt, dthr, (const int64_t *)nullptr, dng,
+                       (rb_corr_gap *)nullptr);
+    RB_HIP(hipGetLastError());
+    ph.end();
+    ngap.resize((size_t)pn);
+    RB_HIP(hipMemcpyAsync(ngap.data(), dng, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+    RB_HIP(hipStreamSynchronize(s));
+    gof.assign((size_t)pn + 1, 0);
+    for (int64_t i = 0; i < pn; ++i) gof[(size_t)i + 1] = gof[(size_t)i] + ngap[(size_t)i];
+    G = gof[(size_t)pn];
+    RB_REQUIRE(G < ((int64_t)1 << 31), "%s: piece too large", who);
+    // gap-level arrays: gof [pn + 1], records [G], rof [G + 1], lof [G], the lists [G], then the pool and the Levenshtein rows
+    int64_t *dlof; int32_t *dlist;
+    auto lay_gaps = [&](Arena &x) {
+        dgof = x.take<int64_t>((size_t)pn + 1); drecs = x.take<rb_corr_gap>((size_t)G); drof = x.take<int64_t>((size_t)G + 1);
+        dlof = x.take<int64_t>((size_t)G); dlist = x.take<int32_t>((size_t)G);
+    };
+    Arena ga;
+    lay_gaps(ga);
+    const size_t g_fixed = ga.at;
+    gbuf.reserve(g_fixed + 64);
+    ga.base = gbuf.as<uint8_t>(); ga.at = 0;
+    lay_gaps(ga);
+    RB_HIP(hipMemcpyAsync(dgof, gof.data(), gof.size() * 8, hipMemcpyHostToDevice, s));
+    uint8_t *dpool = nullptr;
+    int *dlev = nullptr;
+    if (G > 0) {
+        ph.begin(1);
+        hipLaunchKernelGGL((k_gap_scan<true>), dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dkof, dcnt, dthr, dgof, (int32_t *)nullptr, drecs);
+        RB_HIP(hipGetLastError());
+        ph.end();
+        recs.resize((size_t)G);
+        RB_HIP(hipMemcpyAsync(recs.data(), drecs, (size_t)G * sizeof(rb_corr_gap), hipMemcpyDeviceToHost, s));
+        RB_HIP(hipStreamSynchronize(s));
+        // the lists: [no walk: SNV bubbles | tips shorter than lookahead | left tips | right tips | path gaps]
+        rof.assign((size_t)G + 1, 0); lof.assign((size_t)G, -1);
+        std::vector<int32_t> l_snv, l_short, l_left, l_right, l_path;
+        int64_t lev_ints = 0;
+        for (int64_t i = 0; i < G; ++i) {
+            const rb_corr_gap &r = recs[(size_t)i];
+            int64_t room;
+            if (r.kind == RB_GAP_SNV) { l_snv.push_back((int32_t)i); room = k + 2; }
+            else if (r.kind == RB_GAP_PATH) { l_path.push_back((int32_t)i); room = (int64_t)r.run + max_indel; }
+            else { (r.run < lookahead ? l_short : r.kind == RB_GAP_LEFT_EDGE ? l_left : l_right).push_back((int32_t)i); room = r.run; }
+            rof[(size_t)i + 1] = rof[(size_t)i] + room;
+            if (r.kind != RB_GAP_SNV && r.run >= lookahead && (int64_t)r.run + k - 1 > LEV_LDS) { lof[(size_t)i] = lev_ints; lev_ints += (int64_t)r.run + k; }
+        }
+        lists.clear();
+        const size_t o_snv = 0, o_short = l_snv.size(), o_left = o_short + l_short.size(), o_right = o_left + l_left.size(),
+                     o_path = o_right + l_right.size();
+        for (auto *l : {&l_snv, &l_short, &l_left, &l_right, &l_path}) lists.insert(lists.end(), l->begin(), l->end());
+        // (growing gbuf would lose what is in it: the pool and the rows get a buffer laid out behind the fixed part, which is uploaded again)
+        const size_t o_pool = g_fixed, o_lev = up16(o_pool + (size_t)rof[(size_t)G] + 16), g_all = o_lev + (size_t)lev_ints * 4 + 64;
+        gbuf.reserve(g_all);                 // (may move the buffer: everything in it is uploaded again below)
+        ga.base = gbuf.as<uint8_t>(); ga.at = 0;
+        lay_gaps(ga);
+        dpool = gbuf.as<uint8_t>() + o_pool;
+        dlev = reinterpret_cast<int *>(gbuf.as<uint8_t>() + o_lev);
+        RB_HIP(hipMemcpyAsync(dgof, gof.data(), gof.size() * 8, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemcpyAsync(drecs, recs.data(), (size_t)G * sizeof(rb_corr_gap), hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemcpyAsync(drof, rof.data(), rof.size() * 8, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemcpyAsync(dlof, lof.data(), lof.size() * 8, hipMemcpyHostToDevice, s));
+        RB_HIP(hipMemcpyAsync(dlist, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
+        const CorrView cv{dkof, dtof, dtxt, dFin, dRin, dcnt, drecs, drof, dpool, dlof, dlev};
+        // 2. gaps that need no walk
+        ph.begin(3);
+        if (!l_snv.empty())
+            hipLaunchKernelGGL(k_resolve_snv, dim3(blocks_for((int64_t)l_snv.size(), CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv,
+                               dlist + o_snv, (int64_t)l_snv.size(), min_cov);
+        if (!l_short.empty())
+            hipLaunchKernelGGL(k_resolve_edge, dim3(blocks_for((int64_t)l_short.size(), CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv,
+                               dlist + o_short, (int64_t)l_short.size(), lookahead, pid, min_cov, 0, (const uint8_t *)nullptr, (const float *)nullptr,
+                               (const int32_t *)nullptr);
+        RB_HIP(hipGetLastError());
+        ph.end();
+        // 3. the walks, as many at a time as WALK_CHUNK_BYTES holds with the uniform row of the longest of them, and their gaps
+        auto chunks = [&](const std::vector<int32_t> &l, int64_t extra, auto per_walk, auto run) {
+            size_t a = 0;
+            while (a < l.size()) {
+                size_t e = a;
+                int64_t B = 1;
+                while (e < l.size()) {
+                    const int64_t nb2 = std::max<int64_t>(B, (int64_t)recs[(size_t)l[e]].run + extra);
+                    if (e > a && (e - a + 1) * per_walk(nb2) > WALK_CHUNK_BYTES) break;
+                    B = nb2; ++e;
+                }
+                run(a, e - a, (int)B);
+                a = e;
+            }
+        };
+        const size_t ks = (size_t)k;
+        for (int side = 0; side < 2; ++side) {
+            const std::vector<int32_t> &l = side ? l_right : l_left;
+            const size_t o_l = side ? o_right : o_left;
+            chunks(l, 0, [&](int64_t B) { return ks + rb::greedy_seq_stride(k, (int)B) + (size_t)B * 5 + 64; },
+                   [&](size_t a, size_t cn, int B) {
+                       Arena wa;
+                       auto lay = [&](Arena &x, uint8_t *&seeds, uint8_t *&sq, uint8_t *&ob, float *&oc, int32_t *&ol, uint8_t *&orr, int32_t *&bd) {
+                           seeds = x.take<uint8_t>(cn * ks); sq = x.take<uint8_t>(cn * rb::greedy_seq_stride(k, B)); ob = x.take<uint8_t>(cn * (size_t)B);
+                           oc = x.take<float>(cn * (size_t)B); ol = x.take<int32_t>(cn); orr = x.take<uint8_t>(cn); bd = x.take<int32_t>(cn);
+                       };
+                       uint8_t *seeds, *sq, *ob, *orr; float *oc; int32_t *ol, *bd;
+                       lay(wa, seeds, sq, ob, oc, ol, orr, bd);
+                       wbuf.reserve(wa.at + 64);
+                       wa.base = wbuf.as<uint8_t>(); wa.at = 0;
+                       lay(wa, seeds, sq, ob, oc, ol, orr, bd);
+                       const int32_t *lst = dlist + o_l + a;
+                       ph.begin(2);
+                       hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, side ? 1 : 0, max_indel, lst, (int64_t)cn, drecs, dtof,
+                                          dtxt, (const uint8_t *)nullptr, seeds, (uint8_t *)nullptr, bd);
+                       RB_HIP(hipGetLastError());
+                       rb::launch_greedy_extend(g, side ? 0 : 1, seeds, cn, lookahead, B, bd, sq, ob, oc, ol, orr, s);
+                       ph.end();
+                       ph.begin(3);
+                       hipLaunchKernelGGL(k_resolve_edge, dim3(blocks_for((int64_t)cn, CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv, lst,
+                                          (int64_t)cn, lookahead, pid, min_cov, B, ob, oc, ol);
+                       RB_HIP(hipGetLastError());
+                       ph.end();
+                   });
+        }
+        chunks(l_path, max_indel, [&](int64_t B) { return 2 * (ks + (ks + (size_t)B) + (size_t)B * 21 + 64); },
+               [&](size_t a, size_t cn, int B) {
+                   Arena wa;
+                   struct W { uint8_t *seeds, *sq, *ob, *orr; uint64_t *of, *orv; float *oc; int32_t *ol, *bd; } L, Rw;
+                   auto lay = [&](Arena &x, W &w) {
+                       w.seeds = x.take<uint8_t>(cn * ks); w.sq = x.take<uint8_t>(cn * (ks + (size_t)B)); w.ob = x.take<uint8_t>(cn * (size_t)B);
+                       w.of = x.take<uint64_t>(cn * (size_t)B); w.orv = x.take<uint64_t>(cn * (size_t)B); w.oc = x.take<float>(cn * (size_t)B);
+                       w.ol = x.take<int32_t>(cn); w.orr = x.take<uint8_t>(cn); w.bd = x.take<int32_t>(cn);
+                   };
+                   lay(wa, L); lay(wa, Rw);
+                   wbuf.reserve(wa.at + 64);
+                   wa.base = wbuf.as<uint8_t>(); wa.at = 0;
+                   lay(wa, L); lay(wa, Rw);
+                   const int32_t *lst = dlist + o_path + a;
+                   ph.begin(2);
+                   // the first walk's seeds are the second's targets and the other way round
+                   hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, 2, max_indel, lst, (int64_t)cn, drecs, dtof, dtxt,
+                                      (const uint8_t *)nullptr, L.seeds, Rw.seeds, L.bd);
+                   RB_HIP(hipGetLastError());
+                   rb::launch_walk_max_cov(g, 0, L.seeds, Rw.seeds, cn, B, L.bd, min_cov, L.sq, L.ob, L.of, L.orv, L.oc, L.ol, L.orr, s);
+                   hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, 3, max_indel, lst, (int64_t)cn, drecs, dtof, dtxt,
+                                      (const uint8_t *)L.orr, (uint8_t *)nullptr, (uint8_t *)nullptr, Rw.bd);
+                   RB_HIP(hipGetLastError());
+                   rb::launch_walk_max_cov(g, 1, Rw.seeds, L.seeds, cn, B, Rw.bd, min_cov, Rw.sq, Rw.ob, Rw.of, Rw.orv, Rw.oc, Rw.ol, Rw.orr, s);
+                   ph.end();
+                   ph.begin(3);
+                   hipLaunchKernelGGL(k_resolve_path, dim3(blocks_for((int64_t)cn, CE_WAVES)), dim3(CE_TPB), 0, s, k, cv, lst, (int64_t)cn, max_indel, pid, B,
+                                      L.sq, L.of, L.ol, L.orr, Rw.sq, Rw.of, Rw.ol, Rw.orr);
+                   RB_HIP(hipGetLastError());
+                   ph.end();
+               });
+    }
+    // 4. the new text, its getKmers rows, the mismatch pass
+    ph.begin(4);
+    hipLaunchKernelGGL(k_stitch, dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dtof, dctof, dtxt, dgof, drecs, drof, dpool, dctxt, dclen, dcnk,
+                       dflags, dover);
+    RB_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_text_kmers, dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, pn, dctof, dckof, dcwoff, dctxt, dclen,
+                       dvalid, dF, dR, dcnt2);
+    RB_HIP(hipGetLastError());
+    ph.end();
+    ph.begin(5);
+    rb::launch_mismatch(g, min_cov, pn, dids, nlong, dckof, dcnk, dctof, dcwoff, dvalid, dctxt, dF, dR, dcnt2, drow, dthr, dnf, write_counts, s);
+    ph.end();
+}
 
 extern "C" {
 int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const float *cov_threshold, const rb_corr_params *p,
@@ -480,8 +679,7 @@ int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets
         RB_REQUIRE(p->lookahead >= 1 && p->lookahead <= 16, "rb_graph_correct_errors: lookahead out of range [1, 16]");
         RB_REQUIRE(p->max_indel_size >= 0 && p->max_indel_size <= CE_MAX_INDEL, "rb_graph_correct_errors: max_indel_size out of range [0, %d]", CE_MAX_INDEL);
         RB_REQUIRE(!gaps || gap_offsets, "rb_graph_correct_errors: gaps needs gap_offsets");
-        const int k = g->k, max_indel = p->max_indel_size, lookahead = p->lookahead;
-        const float min_cov = p->min_kmer_cov, pid = p->percent_identity;
+        const int k = g->k, max_indel = p->max_indel_size;
         std::vector<int64_t> ko((size_t)n + 1);
         kmer_offsets(offsets, n, k, ko.data(), "rb_graph_correct_errors");
         for (int64_t i = 0; i < n; ++i)
@@ -509,9 +707,8 @@ int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets
         const int64_t ctext = out_offsets[n];
         HostPin pin_seq(seq + offsets[0], (size_t)text), pin_out(out_seq, (size_t)ctext), pin_thr(cov_threshold, (size_t)n * 4);
         QueryLease q(g);
-        const FilterView fv = g->view(0, 0);
         hipStream_t s = q.c->st;
-        PhaseTimer ph;
+        CorrPhaseTimer ph;
         ph.on = g->prof_on; ph.s = s;
         // the piece's gap-level arrays; the walks that run together.  Both belong to the call, not to the leased context: a context's four buffers are
         // taken (table, two hash rows, the arena).  A chunk that needs more than wbuf holds makes reserve() free it, and hipFree waits for the device — which
@@ -519,246 +716,37 @@ int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets
         // size reuse the block in stream order, which is safe for the same stream.  The cost (an allocation a call, a device-wide wait per regrowth) is
         // accepted here: chunks are sized in descending need only by accident, and a call has few of them.
         DevBuf gbuf, wbuf;
-        std::vector<int64_t> tab, gof, rof, lof;
-        std::vector<uint32_t> cwoff;
-        std::vector<int32_t> ngap, nf, lists;
-        std::vector<rb_corr_gap> recs;
-        const int lds_row = rb::mismatch_lds_row();
+        CorrBody body;
+        body.g = g; body.c = q.c.get(); body.s = s; body.ph = &ph; body.gbuf = &gbuf; body.wbuf = &wbuf; body.p = *p;
+        std::vector<int32_t> nf;
         int64_t gbase = 0;                                  // gap records of the pieces before this one
         int64_t piece_end = 0;
         // a piece's scratch goes by its CAPACITY k-mers (the stitched text's rows: 40 bytes each), up to 1 + max_indel / 2 per input k-mer: the pieces
         // are cut smaller by that factor, so a piece holds about 16 M capacity k-mers (RB_QUERY_PIECE still counts input k-mers)
         const int64_t piece_dflt = std::max<int64_t>(1, ((int64_t)16 << 20) / (1 + (max_indel + 1) / 2));
         for_each_host_piece(g, s, seq, offsets, ko.data(), n, "correct_errors", piece_dflt, [&](HostPiece &pc) {
-            const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt, tb = offsets[pc.rb] - offsets[ra], ctb = out_offsets[pc.rb] - out_offsets[ra];
+            const int64_t ra = pc.ra, pn = pc.pn;
             if (gap_offsets) for (int64_t i = piece_end; i <= ra; ++i) gap_offsets[i] = gbase;
-            // the piece's table: k-mer offsets, text offsets, capacity text offsets, capacity k-mer offsets [pn + 1 each], the sequences whose
-            // capacity has more k-mers than a code row in LDS; then the capacity word offsets of the usable-letter bits
-            tab.assign((size_t)(4 * pn + 4), 0);
-            cwoff.assign((size_t)pn + 1, 0);
-            int64_t cpt = 0;
-            std::vector<int64_t> longs;
-            {
-                int64_t *t_kof = tab.data(), *t_tof = t_kof + pn + 1, *t_ctof = t_tof + pn + 1, *t_ckof = t_ctof + pn + 1;
-                for (int64_t i = 0; i <= pn; ++i) {
-                    t_kof[i] = ko[(size_t)(ra + i)] - ko[(size_t)ra];
-                    t_tof[i] = offsets[ra + i] - offsets[ra];
-                    t_ctof[i] = out_offsets[ra + i] - out_offsets[ra];
-                }
-                for (int64_t i = 0; i < pn; ++i) {
-                    const int64_t cl = t_ctof[i + 1] - t_ctof[i], cnk = cl >= k ? cl - k + 1 : 0;
-                    t_ckof[i + 1] = t_ckof[i] + cnk;
-                    cwoff[(size_t)i + 1] = cwoff[(size_t)i] + (uint32_t)((cl + 31) / 32);
-                    if (cnk > lds_row) longs.push_back(i);
-                }
-                cpt = t_ckof[pn];
-            }
-            RB_REQUIRE(cpt < ((int64_t)1 << 40) && (int64_t)cwoff[(size_t)pn] * 32 < ((int64_t)1 << 36), "rb_graph_correct_errors: piece too large");
-            tab.insert(tab.end(), longs.begin(), longs.end());            // (the pointers above are gone: this may move the table)
-            const int64_t nlong = (int64_t)tab.size() - (4 * pn + 4);
-            const size_t tab_bytes = up16(tab.size() * 8);
             const rb_batch *b = pc.batch();
-            q.c->b0.reserve(tab_bytes + (size_t)(pn + 1) * 4 + 16);
-            q.c->b1.reserve((size_t)cpt * 8 + 16);
-            q.c->b2.reserve((size_t)cpt * 8 + 16);
-            PieceArrays pa;
-            Arena ar;
-            pa.lay(ar, pt, pn, tb, ctb, cpt, nlong != 0, (size_t)cwoff[(size_t)pn] + 1);
-            q.c->b3.reserve(ar.at + 64);
-            ar.base = q.c->b3.as<uint8_t>(); ar.at = 0;
-            pa.lay(ar, pt, pn, tb, ctb, cpt, nlong != 0, (size_t)cwoff[(size_t)pn] + 1);
-            float *dcnt = pa.cnt, *dthr = pa.thr, *dcnt2 = pa.cnt2; int32_t *dng = pa.ngap, *dclen = pa.clen, *dcnk = pa.cnk, *dnf = pa.nf;
-            uint8_t *dtxt = pa.txt, *dctxt = pa.ctxt, *drow = pa.row; uint32_t *dflags = pa.flags, *dvalid = pa.valid, *dover = pa.over;
-            uint8_t *b0 = q.c->b0.as<uint8_t>();
-            const int64_t *dkof = reinterpret_cast<const int64_t *>(b0), *dtof = dkof + pn + 1, *dctof = dtof + pn + 1, *dckof = dctof + pn + 1,
-                          *dids = dckof + pn + 1;
-            const uint32_t *dcwoff = reinterpret_cast<const uint32_t *>(b0 + tab_bytes);
-            uint64_t *dF = q.c->b1.as<uint64_t>(), *dR = q.c->b2.as<uint64_t>();
-            RB_HIP(hipMemcpyAsync(b0, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemcpyAsync(b0 + tab_bytes, cwoff.data(), cwoff.size() * 4, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemcpyAsync(dthr, cov_threshold + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemcpyAsync(dtxt, seq + offsets[ra], (size_t)tb, hipMemcpyHostToDevice, s));
-            RB_HIP(hipMemsetAsync(dctxt, 0, (size_t)ctb, s));
-            RB_HIP(hipMemsetAsync(dover, 0, 16, s));
+            body.prepare(pn, ko.data() + ra, offsets + ra, out_offsets + ra);
+            RB_HIP(hipMemcpyAsync(body.own_thr, cov_threshold + ra, (size_t)pn * 4, hipMemcpyHostToDevice, s));
+            RB_HIP(hipMemcpyAsync(body.own_txt, seq + offsets[ra], (size_t)body.tb, hipMemcpyHostToDevice, s));
             pc.kernels_begin();
-            // 1. the count profile, the number of gaps per sequence
+            // the count profile
             ph.begin(0);
-            rb::launch_get_kmers(g, b, dkof, dF, dR, dcnt, s);
+            rb::launch_get_kmers(g, b, body.dkof, body.dF, body.dR, body.own_cnt, s);
             ph.end();
-            ph.begin(1);
-            hipLaunchKernelGGL((k_gap_scan<false>), dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dkof, dcnt, dthr, (const int64_t *)nullptr, dng,
-                               (rb_corr_gap *)nullptr);
-            RB_HIP(hipGetLastError());
-            ph.end();
-            ngap.resize((size_t)pn);
-            RB_HIP(hipMemcpyAsync(ngap.data(), dng, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipStreamSynchronize(s));
-            gof.assign((size_t)pn + 1, 0);
-            for (int64_t i = 0; i < pn; ++i) gof[(size_t)i + 1] = gof[(size_t)i] + ngap[(size_t)i];
-            const int64_t G = gof[(size_t)pn];
-            RB_REQUIRE(G < ((int64_t)1 << 31), "rb_graph_correct_errors: piece too large");
-            // gap-level arrays: gof [pn + 1], records [G], rof [G + 1], lof [G], the lists [G], then the pool and the Levenshtein rows
-            int64_t *dgof, *drof, *dlof; rb_corr_gap *drecs; int32_t *dlist;
-            auto lay_gaps = [&](Arena &x) {
-                dgof = x.take<int64_t>((size_t)pn + 1); drecs = x.take<rb_corr_gap>((size_t)G); drof = x.take<int64_t>((size_t)G + 1);
-                dlof = x.take<int64_t>((size_t)G); dlist = x.take<int32_t>((size_t)G);
-            };
-            Arena ga;
-            lay_gaps(ga);
-            const size_t g_fixed = ga.at;
-            gbuf.reserve(g_fixed + 64);
-            ga.base = gbuf.as<uint8_t>(); ga.at = 0;
-            lay_gaps(ga);
-            RB_HIP(hipMemcpyAsync(dgof, gof.data(), gof.size() * 8, hipMemcpyHostToDevice, s));
-            uint8_t *dpool = nullptr;
-            int *dlev = nullptr;
-            if (G > 0) {
-                ph.begin(1);
-                hipLaunchKernelGGL((k_gap_scan<true>), dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dkof, dcnt, dthr, dgof, (int32_t *)nullptr, drecs);
-                RB_HIP(hipGetLastError());
-                ph.end();
-                recs.resize((size_t)G);
-                RB_HIP(hipMemcpyAsync(recs.data(), drecs, (size_t)G * sizeof(rb_corr_gap), hipMemcpyDeviceToHost, s));
-                RB_HIP(hipStreamSynchronize(s));
-                // the lists: [no walk: SNV bubbles | tips shorter than lookahead | left tips | right tips | path gaps]
-                rof.assign((size_t)G + 1, 0); lof.assign((size_t)G, -1);
-                std::vector<int32_t> l_snv, l_short, l_left, l_right, l_path;
-                int64_t lev_ints = 0;
-                for (int64_t i = 0; i < G; ++i) {
-                    const rb_corr_gap &r = recs[(size_t)i];
-                    int64_t room;
-                    if (r.kind == RB_GAP_SNV) { l_snv.push_back((int32_t)i); room = k + 2; }
-                    else if (r.kind == RB_GAP_PATH) { l_path.push_back((int32_t)i); room = (int64_t)r.run + max_indel; }
-                    else { (r.run < lookahead ? l_short : r.kind == RB_GAP_LEFT_EDGE ? l_left : l_right).push_back((int32_t)i); room = r.run; }
-                    rof[(size_t)i + 1] = rof[(size_t)i] + room;
-                    if (r.kind != RB_GAP_SNV && r.run >= lookahead && (int64_t)r.run + k - 1 > LEV_LDS) { lof[(size_t)i] = lev_ints; lev_ints += (int64_t)r.run + k; }
-                }
-                lists.clear();
-                const size_t o_snv = 0, o_short = l_snv.size(), o_left = o_short + l_short.size(), o_right = o_left + l_left.size(),
-                             o_path = o_right + l_right.size();
-                for (auto *l : {&l_snv, &l_short, &l_left, &l_right, &l_path}) lists.insert(lists.end(), l->begin(), l->end());
-                // (growing gbuf would lose what is in it: the pool and the rows get a buffer laid out behind the fixed part, which is uploaded again)
-                const size_t o_pool = g_fixed, o_lev = up16(o_pool + (size_t)rof[(size_t)G] + 16), g_all = o_lev + (size_t)lev_ints * 4 + 64;
-                gbuf.reserve(g_all);                 // (may move the buffer: everything in it is uploaded again below)
-                ga.base = gbuf.as<uint8_t>(); ga.at = 0;
-                lay_gaps(ga);
-                dpool = gbuf.as<uint8_t>() + o_pool;
-                dlev = reinterpret_cast<int *>(gbuf.as<uint8_t>() + o_lev);
-                RB_HIP(hipMemcpyAsync(dgof, gof.data(), gof.size() * 8, hipMemcpyHostToDevice, s));
-                RB_HIP(hipMemcpyAsync(drecs, recs.data(), (size_t)G * sizeof(rb_corr_gap), hipMemcpyHostToDevice, s));
-                RB_HIP(hipMemcpyAsync(drof, rof.data(), rof.size() * 8, hipMemcpyHostToDevice, s));
-                RB_HIP(hipMemcpyAsync(dlof, lof.data(), lof.size() * 8, hipMemcpyHostToDevice, s));
-                RB_HIP(hipMemcpyAsync(dlist, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, s));
-                const CorrView cv{dkof, dtof, dtxt, dF, dR, dcnt, drecs, drof, dpool, dlof, dlev};
-                // 2. gaps that need no walk
-                ph.begin(3);
-                if (!l_snv.empty())
-                    hipLaunchKernelGGL(k_resolve_snv, dim3(blocks_for((int64_t)l_snv.size(), CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv,
-                                       dlist + o_snv, (int64_t)l_snv.size(), min_cov);
-                if (!l_short.empty())
-                    hipLaunchKernelGGL(k_resolve_edge, dim3(blocks_for((int64_t)l_short.size(), CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv,
-                                       dlist + o_short, (int64_t)l_short.size(), lookahead, pid, min_cov, 0, (const uint8_t *)nullptr, (const float *)nullptr,
-                                       (const int32_t *)nullptr);
-                RB_HIP(hipGetLastError());
-                ph.end();
-                // 3. the walks, as many at a time as WALK_CHUNK_BYTES holds with the uniform row of the longest of them, and their gaps
-                auto chunks = [&](const std::vector<int32_t> &l, int64_t extra, auto per_walk, auto run) {
-                    size_t a = 0;
-                    while (a < l.size()) {
-                        size_t e = a;
-                        int64_t B = 1;
-                        while (e < l.size()) {
-                            const int64_t nb2 = std::max<int64_t>(B, (int64_t)recs[(size_t)l[e]].run + extra);
-                            if (e > a && (e - a + 1) * per_walk(nb2) > WALK_CHUNK_BYTES) break;
-                            B = nb2; ++e;
-                        }
-                        run(a, e - a, (int)B);
-                        a = e;
-                    }
-                };
-                const size_t ks = (size_t)k;
-                for (int side = 0; side < 2; ++side) {
-                    const std::vector<int32_t> &l = side ? l_right : l_left;
-                    const size_t o_l = side ? o_right : o_left;
-                    chunks(l, 0, [&](int64_t B) { return ks + rb::greedy_seq_stride(k, (int)B) + (size_t)B * 5 + 64; },
-                           [&](size_t a, size_t cn, int B) {
-                               Arena wa;
-                               auto lay = [&](Arena &x, uint8_t *&seeds, uint8_t *&sq, uint8_t *&ob, float *&oc, int32_t *&ol, uint8_t *&orr, int32_t *&bd) {
-                                   seeds = x.take<uint8_t>(cn * ks); sq = x.take<uint8_t>(cn * rb::greedy_seq_stride(k, B)); ob = x.take<uint8_t>(cn * (size_t)B);
-                                   oc = x.take<float>(cn * (size_t)B); ol = x.take<int32_t>(cn); orr = x.take<uint8_t>(cn); bd = x.take<int32_t>(cn);
-                               };
-                               uint8_t *seeds, *sq, *ob, *orr; float *oc; int32_t *ol, *bd;
-                               lay(wa, seeds, sq, ob, oc, ol, orr, bd);
-                               wbuf.reserve(wa.at + 64);
-                               wa.base = wbuf.as<uint8_t>(); wa.at = 0;
-                               lay(wa, seeds, sq, ob, oc, ol, orr, bd);
-                               const int32_t *lst = dlist + o_l + a;
-                               ph.begin(2);
-                               hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, side ? 1 : 0, max_indel, lst, (int64_t)cn, drecs, dtof,
-                                                  dtxt, (const uint8_t *)nullptr, seeds, (uint8_t *)nullptr, bd);
-                               RB_HIP(hipGetLastError());
-                               rb::launch_greedy_extend(g, side ? 0 : 1, seeds, cn, lookahead, B, bd, sq, ob, oc, ol, orr, s);
-                               ph.end();
-                               ph.begin(3);
-                               hipLaunchKernelGGL(k_resolve_edge, dim3(blocks_for((int64_t)cn, CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, cv, lst,
-                                                  (int64_t)cn, lookahead, pid, min_cov, B, ob, oc, ol);
-                               RB_HIP(hipGetLastError());
-                               ph.end();
-                           });
-                }
-                chunks(l_path, max_indel, [&](int64_t B) { return 2 * (ks + (ks + (size_t)B) + (size_t)B * 21 + 64); },
-                       [&](size_t a, size_t cn, int B) {
-                           Arena wa;
-                           struct W { uint8_t *seeds, *sq, *ob, *orr; uint64_t *of, *orv; float *oc; int32_t *ol, *bd; } L, Rw;
-                           auto lay = [&](Arena &x, W &w) {
-                               w.seeds = x.take<uint8_t>(cn * ks); w.sq = x.take<uint8_t>(cn * (ks + (size_t)B)); w.ob = x.take<uint8_t>(cn * (size_t)B);
-                               w.of = x.take<uint64_t>(cn * (size_t)B); w.orv = x.take<uint64_t>(cn * (size_t)B); w.oc = x.take<float>(cn * (size_t)B);
-                               w.ol = x.take<int32_t>(cn); w.orr = x.take<uint8_t>(cn); w.bd = x.take<int32_t>(cn);
-                           };
-                           lay(wa, L); lay(wa, Rw);
-                           wbuf.reserve(wa.at + 64);
-                           wa.base = wbuf.as<uint8_t>(); wa.at = 0;
-                           lay(wa, L); lay(wa, Rw);
-                           const int32_t *lst = dlist + o_path + a;
-                           ph.begin(2);
-                           // the first walk's seeds are the second's targets and the other way round
-                           hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, 2, max_indel, lst, (int64_t)cn, drecs, dtof, dtxt,
-                                              (const uint8_t *)nullptr, L.seeds, Rw.seeds, L.bd);
-                           RB_HIP(hipGetLastError());
-                           rb::launch_walk_max_cov(g, 0, L.seeds, Rw.seeds, cn, B, L.bd, min_cov, L.sq, L.ob, L.of, L.orv, L.oc, L.ol, L.orr, s);
-                           hipLaunchKernelGGL(k_walk_setup, dim3(blocks_for((int64_t)cn)), dim3(TPB), 0, s, k, 3, max_indel, lst, (int64_t)cn, drecs, dtof, dtxt,
-                                              (const uint8_t *)L.orr, (uint8_t *)nullptr, (uint8_t *)nullptr, Rw.bd);
-                           RB_HIP(hipGetLastError());
-                           rb::launch_walk_max_cov(g, 1, Rw.seeds, L.seeds, cn, B, Rw.bd, min_cov, Rw.sq, Rw.ob, Rw.of, Rw.orv, Rw.oc, Rw.ol, Rw.orr, s);
-                           ph.end();
-                           ph.begin(3);
-                           hipLaunchKernelGGL(k_resolve_path, dim3(blocks_for((int64_t)cn, CE_WAVES)), dim3(CE_TPB), 0, s, k, cv, lst, (int64_t)cn, max_indel, pid, B,
-                                              L.sq, L.of, L.ol, L.orr, Rw.sq, Rw.of, Rw.ol, Rw.orr);
-                           RB_HIP(hipGetLastError());
-                           ph.end();
-                       });
-            }
-            // 4. the new text, its getKmers rows, the mismatch pass
-            ph.begin(4);
-            hipLaunchKernelGGL(k_stitch, dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, k, pn, dtof, dctof, dtxt, dgof, drecs, drof, dpool, dctxt, dclen, dcnk,
-                               dflags, dover);
-            RB_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_text_kmers, dim3(blocks_for(pn, CE_WAVES)), dim3(CE_TPB), 0, s, fv, (int)g->stranded, k, pn, dctof, dckof, dcwoff, dctxt, dclen,
-                               dvalid, dF, dR, dcnt2);
-            RB_HIP(hipGetLastError());
-            ph.end();
-            ph.begin(5);
-            rb::launch_mismatch(g, min_cov, pn, dids, nlong, dckof, dcnk, dctof, dcwoff, dvalid, dctxt, dF, dR, dcnt2, drow, dthr, dnf, 0, s);
-            ph.end();
+            body.run();
             pc.kernels_end();
+            const int64_t G = body.G;
             nf.resize((size_t)pn);
             uint32_t over = 0;
-            RB_HIP(hipMemcpyAsync(out_seq + out_offsets[ra], dctxt, (size_t)ctb, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipMemcpyAsync(out_len + ra, dclen, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipMemcpyAsync(flags + ra, dflags, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipMemcpyAsync(nf.data(), dnf, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
-            RB_HIP(hipMemcpyAsync(&over, dover, 4, hipMemcpyDeviceToHost, s));
-            if (gaps && G > 0) RB_HIP(hipMemcpyAsync(gaps + gbase, drecs, (size_t)G * sizeof(rb_corr_gap), hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(out_seq + out_offsets[ra], body.dctxt, (size_t)body.ctb, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(out_len + ra, body.dclen, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(flags + ra, body.dflags, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(nf.data(), body.dnf, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+            RB_HIP(hipMemcpyAsync(&over, body.dover, 4, hipMemcpyDeviceToHost, s));
+            if (gaps && G > 0) RB_HIP(hipMemcpyAsync(gaps + gbase, body.drecs, (size_t)G * sizeof(rb_corr_gap), hipMemcpyDeviceToHost, s));
             pc.finish();
             ph.collect();
             if (over) {
@@ -772,14 +760,14 @@ int rb_graph_correct_errors(rb_graph *g, const char *seq, const int64_t *offsets
                 flags[ra + i] = f;
             }
             if (gaps) for (int64_t i = 0; i < G; ++i) gaps[gbase + i].seq += (int32_t)ra;
-            if (gap_offsets) for (int64_t i = 0; i <= pn; ++i) gap_offsets[ra + i] = gbase + gof[(size_t)i];
+            if (gap_offsets) for (int64_t i = 0; i <= pn; ++i) gap_offsets[ra + i] = gbase + body.gof[(size_t)i];
             gbase += G;
             piece_end = pc.rb + 1;
         });
         if (gap_offsets) for (int64_t i = piece_end; i <= n; ++i) gap_offsets[i] = gbase;
         if (ph.on) {
             std::lock_guard<std::mutex> lk(g->qm);
-            for (int i = 0; i < PhaseTimer::N; ++i) if (ph.launches[i]) g->prof_add(ph.names[i], ph.ms[i], ph.launches[i]);
+            for (int i = 0; i < CorrPhaseTimer::N; ++i) if (ph.launches[i]) g->prof_add(ph.names[i], ph.ms[i], ph.launches[i]);
         }
     });
 }

@@ -10,6 +10,7 @@
 
 #include "rb_pieces.hpp"
 #include "rb_repeat.hpp"
+#include "rb_covwalk.hpp"
 #include "rb_wave.hpp"
 
 using namespace rb;
@@ -19,7 +20,6 @@ using namespace rb;
 
 namespace {
 
-constexpr int COV_BINS = 129;            // a bin per count code (count_code_of, rb_device.hpp): every count getCount can return
 constexpr int COV_TPB = 256;
 constexpr int64_t COV_LONG = 4096;       // segments of at least this many windows get a workgroup of their own
 
@@ -27,32 +27,6 @@ __device__ __forceinline__ bool window_usable(const uint32_t *vw, uint32_t b0, i
     for (uint32_t b = b0; b < b0 + (uint32_t)k; ++b)
         if (!((vw[b >> 5] >> (b & 31u)) & 1u)) return false;
     return true;
-}
-
-// the bin holding sorted position r (cum[b] = elements in bins < b, cum[COV_BINS] = n)
-__device__ __forceinline__ int bin_of_rank(const uint32_t *cum, int64_t r) {
-    int lo = 0, hi = COV_BINS - 1;                     // largest b with cum[b] <= r
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if ((int64_t)cum[mid] <= r) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-// The downward walk of the reference from sorted position s: pairs (covs[i], covs[i+1]) for i = s-1 .. 0, stop at the first with
-// covs[i+1] * g > covs[i] (strict) or >= (PE); the threshold is then covs[i+1], else covs[0].  Over bins: the pairs inside one bin are
-// all (v, v) and give the same answer, so a bin is tested once inside (when the walk sees two of its elements) and once against the
-// next lower non-empty bin — the step-by-step loop's answer, multiplicities included.
-__device__ float cov_walk(const uint32_t *cum, int64_t s, float g, bool strict, bool &found) {
-    int b = bin_of_rank(cum, s);
-    float v = count_code_value((uint32_t)b);
-    int64_t seen = s - (int64_t)cum[b] + 1;            // elements of bin b at or below the walk's start
-    for (;;) {
-        const float t = v * g;
-        if (seen >= 2 && (strict ? t > v : t >= v)) { found = true; return v; }
-        int pb = b - 1;
-        while (pb >= 0 && cum[pb + 1] == cum[pb]) --pb;
-        if (pb < 0) { found = false; return v; }
-        const float pv = count_code_value((uint32_t)pb);
-        if (strict ? t > pv : t >= pv) { found = true; return v; }
-        b = pb; v = pv; seen = (int64_t)cum[b + 1] - cum[b];
-    }
 }
 
 struct CovSrc {                                        // the reads a segment's windows come from (n_complex)

@@ -45,6 +45,13 @@ EXTL_REC_FIELDS = [("status", "<i4"), ("why", "<i4"), ("left_ext", "<i4"), ("rig
                    ("right_end", "<i4"), ("left_rounds", "<i4"), ("right_rounds", "<i4"), ("steps", "<i4"), ("floor_drops", "<i4"),
                    ("used_passed", "<i4"), ("left_floor", "<f4"), ("right_floor", "<f4"), ("pad", "<i4", (2,))]
 EXTL_MAX_ROOM = 1 << 24
+# rb_graph_correct_pairs: rb_pairc_rec.status, end, flags; the record's fields (64 bytes; a numpy dtype is made of them)
+PAIRC_UNCHANGED, PAIRC_CORRECTED, PAIRC_NOT_JUDGED = range(3)
+PAIRC_END_ALL, PAIRC_END_NO_CHANGE, PAIRC_END_LOW, PAIRC_END_NO_KMER, PAIRC_END_LOST_KMERS = range(5)
+PAIRC_LEFT, PAIRC_RIGHT, PAIRC_LEFT_OVERFLOW, PAIRC_RIGHT_OVERFLOW = 1, 2, 4, 8
+PAIRC_REC_FIELDS = [("status", "<i4"), ("end", "<i4"), ("rounds_run", "<i4"), ("flags", "<i4"), ("left_len", "<i4"), ("right_len", "<i4"),
+                    ("thr_first", "<u4"), ("thr_last", "<u4"), ("found_first", "<i4"), ("left_changed", "<i4"), ("right_changed", "<i4"),
+                    ("gaps_replaced", "<i4"), ("gaps_trimmed", "<i4"), ("gaps_kept", "<i4"), ("mismatches", "<i4"), ("reserved", "<i4")]
 
 
 class GraphParams(C.Structure):
@@ -90,6 +97,18 @@ class CorrParams(C.Structure):
 
 
 assert C.sizeof(CorrParams) == 16
+
+
+class PairCorrParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("lookahead", C.c_int32), ("max_indel_size", C.c_int32), ("max_cov_gradient", C.c_float),
+                ("cov_fpr", C.c_float), ("min_cov_threshold", C.c_float), ("percent_identity", C.c_float), ("min_kmer_cov", C.c_float)]
+
+
+class PairCorrRec(C.Structure):
+    _fields_ = [(name, C.c_uint32 if t == "<u4" else C.c_int32) for name, t in PAIRC_REC_FIELDS]
+
+
+assert C.sizeof(PairCorrParams) == 32 and C.sizeof(PairCorrRec) == 64
 
 
 class LongParams(C.Structure):
@@ -142,6 +161,7 @@ SYMBOLS = [
     ("rb_graph_paired_kmer_segments", _i32, [_vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_correct_mismatches", _i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     ("rb_graph_correct_errors", _i32, [_vp, _vp, _vp, _i64, _vp, C.POINTER(CorrParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("rb_graph_correct_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(PairCorrParams), _vp, _vp, _vp, _vp, _vp]),
     ("rb_graph_overlap_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_extend_se", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),

@@ -564,6 +564,103 @@ class BloomFilterDeBruijnGraph:
         out, oo, ol, fl, _, _ = self.correctErrorsFlat(seq, off, thresholds, lookahead, maxIndelSize, percentIdentity, minKmerCov)
         return [(out[oo[i]:oo[i] + ol[i]].tobytes(), bool(fl[i] & self.CORR_CORRECTED)) for i in range(len(seqs))]
 
+    PAIRC_DTYPE = np.dtype(N.PAIRC_REC_FIELDS)
+    PAIRC_STATUS = ("unchanged", "corrected", "not_judged")
+    PAIRC_ENDS = ("all", "no_change", "low", "no_kmer", "lost_kmers")
+
+    def correctPairsFlat(self, lseq, loffsets, rseq, roffsets, loutOffsets, routOffsets, lookahead=5, maxIndelSize=1, maxCovGradient=0.5,
+                         covFPR=0.01, errorCorrectionIterations=2, minCovThreshold=2.0, percentIdentity=0.9, minKmerCov=1.0):
+        """rb_graph_correct_pairs on flat host text: GraphUtils.correctErrorsPE (R/util/GraphUtils.java:4051-4182) of pair i = (lseq[loffsets[i]:
+        loffsets[i + 1]], rseq[roffsets[i]:roffsets[i + 1]]) with every round on the device; with rseq, roffsets and routOffsets None,
+        GraphUtils.correctErrorsSE (:3998-4049) of the reads in lseq.  loutOffsets / routOffsets are the caller's capacity layouts (n + 1).
+        Returns (lout, rout, recs): the uint8 text buffers laid out by them (rout None in the single form) and one PAIRC_DTYPE record per pair;
+        the left text of pair i is lout[loutOffsets[i]:loutOffsets[i] + recs[i]["left_len"]] unless recs[i]["flags"] has PAIRC_LEFT_OVERFLOW,
+        in which case nothing was written for it and left_len is the room it needs; the right text likewise."""
+        def flat(x):
+            return np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, dtype=np.uint8)
+        lseq = flat(lseq)
+        lo = np.ascontiguousarray(loffsets, dtype=np.int64)
+        loo = np.ascontiguousarray(loutOffsets, dtype=np.int64)
+        n = lo.size - 1
+        pe = roffsets is not None
+        if loo.size != n + 1:
+            raise ValueError("correctPairsFlat: loutOffsets needs %d entries" % (n + 1))
+        rseq_, ro, roo, rout = None, None, None, None
+        if pe:
+            rseq_ = flat(rseq)
+            ro = np.ascontiguousarray(roffsets, dtype=np.int64)
+            roo = np.ascontiguousarray(routOffsets, dtype=np.int64)
+            if ro.size != n + 1 or roo.size != n + 1:
+                raise ValueError("correctPairsFlat: roffsets and routOffsets need %d entries" % (n + 1))
+            rout = np.zeros(max(1, int(roo[-1]) if n else 0), np.uint8)
+        elif rseq is not None or routOffsets is not None:
+            raise ValueError("correctPairsFlat: the single form takes neither rseq nor routOffsets")
+        p = N.PairCorrParams(errorCorrectionIterations, lookahead, maxIndelSize, maxCovGradient, covFPR, minCovThreshold, percentIdentity, minKmerCov)
+        lout = np.zeros(max(1, int(loo[-1]) if n else 0), np.uint8)
+        recs = np.zeros(n, self.PAIRC_DTYPE)
+        check(lib.rb_graph_correct_pairs(self.h, _ptr(lseq), _ptr(lo), _ptr(rseq_), _ptr(ro), n, C.byref(p), _ptr(loo), _ptr(lout), _ptr(roo), _ptr(rout),
+                                         _ptr(recs)))
+        return lout, rout, recs
+
+    def _correct_pairs(self, lefts, rights, slack, params):
+        """correctPairsFlat over lists of bytes with room for length + slack per mate, and once more for the mates that overflowed with the room
+        their records ask for -> (left texts, right texts or None, recs)."""
+        n, pe = len(lefts), rights is not None
+        recs = np.zeros(n, self.PAIRC_DTYPE)
+        lt, rt = [None] * n, [None] * n
+        todo = np.arange(n)
+        lroom = np.fromiter((len(s) + slack for s in lefts), np.int64, n)
+        rroom = np.fromiter((len(s) + slack for s in rights), np.int64, n) if pe else None
+        for _ in range(2):
+            if not todo.size:
+                break
+            ids = todo.tolist()
+            lseq, lo = _pack([lefts[i] for i in ids])
+            loo = np.zeros(todo.size + 1, np.int64)
+            np.cumsum(lroom[todo], out=loo[1:])
+            rseq = ro = roo = None
+            if pe:
+                rseq, ro = _pack([rights[i] for i in ids])
+                roo = np.zeros(todo.size + 1, np.int64)
+                np.cumsum(rroom[todo], out=roo[1:])
+            lout, rout, rc = self.correctPairsFlat(lseq, lo, rseq, ro, loo, roo, **params)
+            recs[todo] = rc
+            over = (rc["flags"] & (N.PAIRC_LEFT_OVERFLOW | N.PAIRC_RIGHT_OVERFLOW)) != 0
+            lroom[todo] = np.maximum(lroom[todo], rc["left_len"])
+            if pe:
+                rroom[todo] = np.maximum(rroom[todo], rc["right_len"])
+            for texts, out, oo, lens in ((lt, lout, loo, rc["left_len"]), (rt, rout, roo, rc["right_len"])) if pe else ((lt, lout, loo, rc["left_len"]),):
+                buf = out.tobytes()
+                for i, a, ln, ov in zip(ids, oo[:-1].tolist(), lens.tolist(), over.tolist()):
+                    if not ov:
+                        texts[i] = buf[a:a + ln]
+            todo = todo[over]
+        if todo.size:
+            raise RuntimeError("correctPairs: %d pairs overflowed the room their own records asked for" % todo.size)
+        return lt, (rt if pe else None), recs
+
+    def correctPairs(self, lefts, rights, slack=16, records=False, **params):
+        """GraphUtils.correctErrorsPE of every pair in one call (and a second for the few mates that outgrow length + slack): per pair
+        (left, right, corrected) — the strings the reference's ReadPair spells, as bytes, and its `corrected` — or None where the pair is not
+        judged (a mate without a k-mer: the reference throws).  params: correctPairsFlat's, named as the reference names them.
+        records=True: (results, recs) with the PAIRC_DTYPE records."""
+        lefts = [s.encode() if isinstance(s, str) else bytes(s) for s in lefts]
+        rights = [s.encode() if isinstance(s, str) else bytes(s) for s in rights]
+        if len(lefts) != len(rights):
+            raise ValueError("correctPairs: %d left and %d right mates" % (len(lefts), len(rights)))
+        lt, rt, recs = self._correct_pairs(lefts, rights, slack, params)
+        res = [None if st == N.PAIRC_NOT_JUDGED else (l, r, st == N.PAIRC_CORRECTED) for l, r, st in zip(lt, rt, recs["status"].tolist())]
+        return (res, recs) if records else res
+
+    def correctReads(self, seqs, slack=16, records=False, **params):
+        """GraphUtils.correctErrorsSE of every read in one call: per read the string the returned k-mers spell, as bytes, or None where the
+        reference returns null (no k-mer, no threshold, or the helper changed nothing).  params: correctPairsFlat's; minCovThreshold is not
+        read and errorCorrectionIterations only as zero or not.  records=True: (results, recs)."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        lt, _, recs = self._correct_pairs(seqs, None, slack, params)
+        res = [t if st == N.PAIRC_CORRECTED else None for t, st in zip(lt, recs["status"].tolist())]
+        return (res, recs) if records else res
+
     OVL_DTYPE = np.dtype([("outcome", "<i4"), ("why", "<i4"), ("flags", "<u4"), ("overlap", "<i4"), ("out_len", "<i4"), ("span_first", "<i4"),
                           ("span_n", "<i4"), ("pad", "<i4")])
     OVL_OUTCOMES = ("none", "left", "right", "merged", "spanned", "rescue")

@@ -238,6 +238,74 @@ def connectComposed(graph, segment_lists):
     return out
 
 
+def _pair_params(lookahead, maxIndelSize, maxCovGradient, covFPR, errorCorrectionIterations, minCovThreshold, percentIdentity, minKmerCov):
+    return dict(lookahead=lookahead, maxIndelSize=maxIndelSize, maxCovGradient=maxCovGradient, covFPR=covFPR,
+                errorCorrectionIterations=errorCorrectionIterations, minCovThreshold=minCovThreshold, percentIdentity=percentIdentity,
+                minKmerCov=minKmerCov)
+
+
+def correctErrorsPE(graph, lefts, rights, lookahead, maxIndelSize, maxCovGradient, covFPR, errorCorrectionIterations, minCovThreshold,
+                    percentIdentity, minKmerCov):
+    """GraphUtils.correctErrorsPE (R/util/GraphUtils.java:4051-4182) for many pairs in ONE graph.correctPairs call, all rounds on the device
+    (rb_graph_correct_pairs).  Returns per pair (left, right, corrected) — the strings the reference's ReadPair spells, as bytes — or None for a
+    pair one of whose mates has no k-mer (the reference throws).  The k-mer lists are getKmers(String)'s of the texts: the worker's stretch
+    selection getKmers(left, minKmerCov) comes before the call."""
+    return graph.correctPairs(lefts, rights, **_pair_params(lookahead, maxIndelSize, maxCovGradient, covFPR, errorCorrectionIterations,
+                                                            minCovThreshold, percentIdentity, minKmerCov))
+
+
+def correctErrorsSE(graph, seqs, lookahead, maxIndelSize, maxCovGradient, covFPR, percentIdentity, minKmerCov):
+    """GraphUtils.correctErrorsSE (R/util/GraphUtils.java:3998-4049) for many reads in ONE graph.correctReads call.  Returns per read the
+    string the returned k-mers spell, as bytes, or None where the reference returns null."""
+    return graph.correctReads(seqs, **_pair_params(lookahead, maxIndelSize, maxCovGradient, covFPR, 1, 0.0, percentIdentity, minKmerCov))
+
+
+def correctErrorsPEComposed(graph, lefts, rights, lookahead, maxIndelSize, maxCovGradient, covFPR, errorCorrectionIterations, minCovThreshold,
+                            percentIdentity, minKmerCov):
+    """The same from the calls a caller had before graph.correctPairs, with the loop (:4066-4179) on the host: per round a ReadBatch of each
+    side's current texts, graph.coverageStats with mates (the two searches and the combining rule), graph.correctErrors on the mates of the
+    pairs whose threshold passes, the texts read back.  Kept as the in-library cross-check of correctErrorsPE and as the other side of
+    tools/correct_pairs_bench.py."""
+    from .graph import ReadBatch, _pack
+    k = graph.k
+    cur = [[s.encode() if isinstance(s, str) else bytes(s) for s in side] for side in (lefts, rights)]
+    n = len(cur[0])
+    judged = [len(cur[0][i]) >= k and len(cur[1][i]) >= k for i in range(n)]
+    corrected = [False] * n
+    live = [i for i in range(n) if judged[i]]
+    for _ in range(errorCorrectionIterations):
+        if not live:
+            break
+        packed = [_pack([cur[side][i] for i in live]) for side in (0, 1)]
+        lb, rb = (ReadBatch.from_ascii(seq, None, off, 0, graph.device) for seq, off in packed)
+        try:
+            _, _, thr = graph.coverageStats(lb, mates=rb, maxCovGradient=maxCovGradient, covFPR=covFPR, minKmerCov=minKmerCov)
+        finally:
+            lb.close()
+            rb.close()
+        run = [j for j in range(len(live)) if thr[j] >= minCovThreshold]
+        if not run:
+            break                                    # nothing can change any more: every later round repeats this one
+        res = graph.correctErrors([cur[side][live[j]] for side in (0, 1) for j in run], [float(thr[j]) for _ in (0, 1) for j in run],
+                                  lookahead, maxIndelSize, percentIdentity, minKmerCov)
+        nxt = []
+        for x, j in enumerate(run):
+            i = live[j]
+            changed = False
+            for side in (0, 1):
+                text, ok = res[side * len(run) + x]
+                if ok:
+                    cur[side][i] = text
+                    corrected[i] = changed = True
+            if changed:
+                if len(cur[0][i]) < k or len(cur[1][i]) < k:
+                    judged[i] = False                # the next round would throw
+                else:
+                    nxt.append(i)
+        live = nxt
+    return [(cur[0][i], cur[1][i], corrected[i]) if judged[i] else None for i in range(n)]
+
+
 def extendSE(graph, seqs, minKmerCov, max_rounds=100000):
     """GraphUtils.extendSE(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6454-6565) for many sequences: first to the left,
     then to the right, each sequence is extended across branches by extendLeftSE / extendRightSE until the step returns nothing at the
