@@ -1098,6 +1098,61 @@ int rb_minimizers_next(int device, const char *seq, const int64_t *offsets, int6
 int rb_minimizer_set(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int w, int mode,
                      const uint64_t *stale, int64_t *moffsets, uint64_t *out);
 
+/* ---- preparation of raw long reads: text work, no graph ----
+ * What LongReadCorrectionWorker.run (R/RNABloom.java:3700-3779) does to a raw read before it makes a segment, for n host reads in one call:
+ *   1. reverse_complement != 0: SeqUtils.reverseComplement (R/util/SeqUtils.java:1120-1152: A C G T U -> T G C A A, every other byte, lower
+ *      case included, -> N).  The result is "the finder's read"; its length is the raw length, and length < min_len ends here: RB_PREP_SHORT.
+ *   2. polya != 0 (minPolyATailLengthRequired > 0): PolyATailFinder.findPolyATail (R/util/PolyATailFinder.java:319-338 over findPolyASeed
+ *      :201-277, letters A a) and, unless strand_specific, findPolyTHead (:476-495 over findPolyTSeed :355-432, letters T t), with the finder's
+ *      seed_length, min_identity, max_gap and window = max(seed_length, window) (setWindow).  Float32 as the reference: a seed window passes when
+ *      count / (float) seed_length >= min_identity, two regions join when prev.end + max_gap >= best.start or the float32 share of the letter
+ *      between them >= min_identity.  Both quirks of the refinement are kept: a tail region that starts at the search start walks down while
+ *      seq[start] is an A, so it ends ON the other letter (or at 0); findPolyTSeed opens its region one letter longer than the seed.
+ *   3. the five-way rule (:3715-3766).  Stranded: cut at tail.end and hasPolyA only if tail.end < length.  Else tail only: cut if tail.end <
+ *      length, hasPolyA either way; head only: cut from head.start, reverse-complement (the map of 1., once more), hasPolyA; both: keep
+ *      [head.end, tail.start) if head.end < tail.start, hasPolyA stays false.  The result is "the transformed read".
+ *   4. SeqUtils.trimLowComplexityRegions(transformed, lc_window, lc_min_length) (:839-902): with numWindows = len / lc_window >= 5 the windows
+ *      start at offset = (len % lc_window) / 2, a window is low by isLowComplexityLong (:585-659: only upper-case A C G T U count, U as T;
+ *      thresholds round(len * 0.89f), round(len * 0.89f / 2.0f), round(len * 0.89f / 3.0f) in float32 with Math.round), and if numLow * lc_window
+ *      >= lc_min_length the runs of complex windows are the segments — a run from window 0 starts at letter 0, a run open at the end runs to
+ *      len —, else the whole read is one segment.  With fewer windows: no segment if isLowComplexityLongWindowed (:661-682: windows of 50, with 4
+ *      or more of them low when numLow >= floor(0.75 * numWindows), else isLowComplexityLong of the whole), otherwise the whole read.
+ *   5. more than one segment clears hasPolyA (:3777-3779).
+ * recs[i], 16 ints: status (RB_PREP_SHORT: nothing else is set but -1 in the four region fields; RB_PREP_LOW_COMPLEXITY: no segment, the
+ * worker emits the transformed read flagged low-complexity; RB_PREP_SEGMENTS); flags (RB_PREP_REVCOMP the transformed read runs against the
+ * input: exactly one of the argument and the head rule turned it; RB_PREP_MAPPED_TWICE both did: it runs with the input but its letters went
+ * through the complement map twice, U -> T and every byte outside ACGTU -> N; RB_PREP_HAS_POLYA after 5.; RB_PREP_TAIL_FOUND / HEAD_FOUND a
+ * region is not null; RB_PREP_CUT_FIRED; which of the three complexity routes ran: RB_PREP_ROUTE_WINDOWS, _WINDOWED (windows of 50), _WHOLE);
+ * kept_begin, kept_end: the input letters the transformed read is made of, in input coordinates; tail_start, tail_end, head_start, head_end in
+ * the coordinates of the finder's read, -1 for null; n_windows, n_low, offset of the route that ran (_WHOLE: 0, 1 if low, 0); n_segments; the
+ * seed searches the tail chain and the head chain made; 0, 0.
+ * Segments: [begin, end) pairs in the transformed read's coordinates, n_segments of them at out_segs + 2 * seg_offsets[i].  seg_offsets (n + 1)
+ * is an INPUT, the caller's layout as in rb_graph_paired_kmer_segments: every read needs room for max(1, (len / lc_window + 1) / 2) segments.
+ * Slots a read does not fill are not touched.  out_seq (may be NULL): the transformed read of every read that is not RB_PREP_SHORT, kept_end -
+ * kept_begin bytes at out_seq + offsets[i] — a caller takes its segments as substrings without a host pass.  kernel_ms (may be NULL) receives
+ * the time from the first to the last kernel of every piece, summed, by events.
+ * One kernel, a wavefront per read: the finder's scans are ballots over the positions of a search range, the complexity pass has the lanes
+ * across a window's letters with the window's 84 counters in LDS; nothing is staged, so a read of any length (up to 2^30) works.  The call works
+ * in pieces of 64 M letters (RB_QUERY_PIECE counts letters here); results do not depend on the cuts.  Device memory of a piece: 1 byte a letter
+ * (2 with out_seq), 16 bytes a read and 8 a segment slot.
+ * Refused (RB_ERR_INVALID, before anything is written): null p; n < 0; null offsets / seg_offsets / recs / out_segs (n > 0), seq where there is
+ * text; min_len < 0; seed_length < 1; min_identity not in (0, 1]; max_gap outside 0 .. 2^30; window < 0; lc_window outside 1 .. 1024;
+ * lc_min_length < 0; decreasing offsets; a read of more than 2^30 letters; a read's room below the bound.  n == 0 succeeds and touches nothing. */
+enum { RB_PREP_SHORT = 0, RB_PREP_LOW_COMPLEXITY = 1, RB_PREP_SEGMENTS = 2 };                   /* rb_prep_rec.status */
+enum { RB_PREP_REVCOMP = 1, RB_PREP_HAS_POLYA = 2, RB_PREP_TAIL_FOUND = 4, RB_PREP_HEAD_FOUND = 8, RB_PREP_CUT_FIRED = 16,
+       RB_PREP_ROUTE_WINDOWS = 32, RB_PREP_ROUTE_WINDOWED = 64, RB_PREP_ROUTE_WHOLE = 128, RB_PREP_MAPPED_TWICE = 256 };   /* rb_prep_rec.flags */
+#define RB_PREP_MAX_LC_WINDOW 1024
+typedef struct rb_prep_params {
+    int32_t min_len, reverse_complement, strand_specific, polya, seed_length, max_gap, window, lc_window, lc_min_length;
+    float min_identity;
+} rb_prep_params;
+typedef struct rb_prep_rec {            /* 64 bytes */
+    int32_t status, flags, kept_begin, kept_end, tail_start, tail_end, head_start, head_end;
+    int32_t n_windows, n_low, offset, n_segments, tail_searches, head_searches, reserved[2];
+} rb_prep_rec;
+int rb_long_prepare(int device, const char *seq, const int64_t *offsets, int64_t n, const rb_prep_params *p, const int64_t *seg_offsets,
+                    rb_prep_rec *recs, int32_t *out_segs, char *out_seq, double *kernel_ms);
+
 /* ---- input formats ----
  * FASTQ text -> the buffers rb_graph_add_reads / rb_batch_create_ascii take.  FastqReader.nextWithoutName
  * R/io/FastqReader.java:140-186: four lines per record, line 1 starts with '@', line 3 with '+' (else RB_ERR_INVALID with

@@ -212,6 +212,18 @@ public final class NativeGraph {
      *  written, 2: trimmed to nothing).  Read-only. */
     public static native void correctLong(long h, ByteBuffer seq, long[] offsets, int n, int[] params, float maxCovGradient, float percentIdentity,
                                           long[] outOffsets, ByteBuffer out, int[] recs);
+    /** What LongReadCorrectionWorker.run does to n raw reads before its first graph call (rb_long_prepare, R/RNABloom.java:3705-3779): the
+     *  reverse complement where asked, PolyATailFinder.findPolyATail / findPolyTHead and the five-way rule that cuts and turns the read,
+     *  SeqUtils.trimLowComplexityRegions, hasPolyA.  No graph handle: text work on `device`.  params: k (shorter reads are discarded),
+     *  reverseComplement, strandSpecific, minPolyATailLengthRequired > 0 (0 / 1), the finder's seedLength, maxGap and window, the window and the
+     *  minimum length of trimLowComplexityRegions (100, 500).  segOffsets (n + 1) is the caller's layout of `segs`, 2 ints a slot: read i needs
+     *  room for max(1, (length / window + 1) / 2) segments.  recs holds 16 ints per read — status (0 too short, 1 low complexity: no segment,
+     *  2 segments), flags (1 the transformed read runs against the input, 2 hasPolyA, 4 / 8 a tail / a head was found, 16 the cut fired,
+     *  32 / 64 / 128 the complexity route, 256 turned twice), the input letters kept [begin, end), tail and head as [start, end) or -1, the
+     *  windows, the low ones, the offset, the number of segments, the seed searches of both chains, 0, 0 (include/rb_capi.h).  out (may be null)
+     *  receives the transformed read of read i at offsets[i]: its segments are substrings of it. */
+    public static native void longPrepare(int device, ByteBuffer seq, long[] offsets, int n, int[] params, float minIdentity, long[] segOffsets,
+                                          int[] recs, int[] segs, ByteBuffer out);
     /** GraphUtils.correctErrorsPE (rb_graph_correct_pairs, R/util/GraphUtils.java:4051-4182) of n read pairs, every round inside the call; with
      *  rseq, roffsets, routOffsets and rout all null, GraphUtils.correctErrorsSE (:3998-4049) of n reads.  params: errorCorrectionIterations,
      *  lookahead, maxIndelSize; fparams: maxCovGradient, covFPR, minCovThreshold, percentIdentity, minKmerCov.  loutOffsets / routOffsets (n + 1)

@@ -593,6 +593,32 @@ void FN(correctLong)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offse
     lr(e, offsets, po, JNI_ABORT); lr(e, outOffsets, poo, JNI_ABORT); ir(e, recs, rc16, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_long_prepare: params holds the nine ints of rb_prep_params in its order; a record (rb_prep_rec, 64 bytes) is 16 ints to Java; segs holds 2 ints
+ * per slot at 2 * segOffsets[i]; out == null: no transformed text */
+void FN(longPrepare)(JNIEnv *e, jclass c, jint device, jobject seq, jlongArray offsets, jint n, jintArray params, jfloat minIdentity,
+                     jlongArray segOffsets, jintArray recs, jintArray segs, jobject out) {
+    (void)c;
+    if (n < 0 || !params || (*e)->GetArrayLength(e, params) < 9 ||
+        (n > 0 && (!offsets || !segOffsets || !recs || !segs || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, segOffsets) <= n ||
+                   (*e)->GetArrayLength(e, recs) / 16 < n))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "longPrepare: an array is too short for n reads");
+        return;
+    }
+    jint *pp = ia(e, params);
+    rb_prep_params p = {pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], pp[6], pp[7], pp[8], minIdentity};
+    ir(e, params, pp, JNI_ABORT);
+    jlong *po = la(e, offsets), *so = la(e, segOffsets);
+    if (n > 0 && (*e)->GetArrayLength(e, segs) / 2 < so[n]) {
+        lr(e, offsets, po, JNI_ABORT); lr(e, segOffsets, so, JNI_ABORT);
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "longPrepare: segs is shorter than segOffsets says");
+        return;
+    }
+    jint *rc16 = ia(e, recs), *sg = ia(e, segs);
+    int rc = rb_long_prepare(device, (const char *)direct(e, seq), (const int64_t *)po, n, &p, (const int64_t *)so, (rb_prep_rec *)rc16, (int32_t *)sg,
+                             (char *)direct(e, out), NULL);
+    lr(e, offsets, po, JNI_ABORT); lr(e, segOffsets, so, JNI_ABORT); ir(e, recs, rc16, 0); ir(e, segs, sg, 0);
+    if (rc) throw_rc(e, rc);
+}
 /* rb_graph_correct_pairs: params holds iterations, lookahead, max_indel_size; fparams max_cov_gradient, cov_fpr, min_cov_threshold, percent_identity,
  * min_kmer_cov; a record (rb_pairc_rec, 64 bytes) is 16 ints to Java.  rseq, roffsets, routOffsets and rout all null: the single form */
 void FN(correctPairs)(JNIEnv *e, jclass c, jlong h, jobject lseq, jlongArray loffsets, jobject rseq, jlongArray roffsets, jint n, jintArray params,

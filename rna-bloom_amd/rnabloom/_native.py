@@ -49,6 +49,14 @@ EXTL_MAX_ROOM = 1 << 24
 PAIRC_UNCHANGED, PAIRC_CORRECTED, PAIRC_NOT_JUDGED = range(3)
 PAIRC_END_ALL, PAIRC_END_NO_CHANGE, PAIRC_END_LOW, PAIRC_END_NO_KMER, PAIRC_END_LOST_KMERS = range(5)
 PAIRC_LEFT, PAIRC_RIGHT, PAIRC_LEFT_OVERFLOW, PAIRC_RIGHT_OVERFLOW = 1, 2, 4, 8
+# rb_long_prepare: rb_prep_rec.status, rb_prep_rec.flags; the record's fields (64 bytes; a numpy dtype is made of them)
+PREP_SHORT, PREP_LOW_COMPLEXITY, PREP_SEGMENTS = range(3)
+PREP_REVCOMP, PREP_HAS_POLYA, PREP_TAIL_FOUND, PREP_HEAD_FOUND, PREP_CUT_FIRED, PREP_ROUTE_WINDOWS, PREP_ROUTE_WINDOWED, PREP_ROUTE_WHOLE, \
+    PREP_MAPPED_TWICE = 1, 2, 4, 8, 16, 32, 64, 128, 256
+PREP_REC_FIELDS = [("status", "<i4"), ("flags", "<i4"), ("kept_begin", "<i4"), ("kept_end", "<i4"), ("tail_start", "<i4"), ("tail_end", "<i4"),
+                   ("head_start", "<i4"), ("head_end", "<i4"), ("n_windows", "<i4"), ("n_low", "<i4"), ("offset", "<i4"), ("n_segments", "<i4"),
+                   ("tail_searches", "<i4"), ("head_searches", "<i4"), ("reserved", "<i4", (2,))]
+PREP_MAX_LC_WINDOW = 1024
 PAIRC_REC_FIELDS = [("status", "<i4"), ("end", "<i4"), ("rounds_run", "<i4"), ("flags", "<i4"), ("left_len", "<i4"), ("right_len", "<i4"),
                     ("thr_first", "<u4"), ("thr_last", "<u4"), ("found_first", "<i4"), ("left_changed", "<i4"), ("right_changed", "<i4"),
                     ("gaps_replaced", "<i4"), ("gaps_trimmed", "<i4"), ("gaps_kept", "<i4"), ("mismatches", "<i4"), ("reserved", "<i4")]
@@ -118,6 +126,15 @@ class LongParams(C.Structure):
 
 
 assert C.sizeof(LongParams) == 36
+
+
+class PrepParams(C.Structure):
+    _fields_ = [("min_len", C.c_int32), ("reverse_complement", C.c_int32), ("strand_specific", C.c_int32), ("polya", C.c_int32),
+                ("seed_length", C.c_int32), ("max_gap", C.c_int32), ("window", C.c_int32), ("lc_window", C.c_int32),
+                ("lc_min_length", C.c_int32), ("min_identity", C.c_float)]
+
+
+assert C.sizeof(PrepParams) == 40
 
 
 class Profile(C.Structure):
@@ -194,6 +211,7 @@ SYMBOLS = [
     ("rb_kmer_pair_hashes", _i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("rb_minimizers_next", _i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("rb_minimizer_set", _i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("rb_long_prepare", _i32, [_i32, _vp, _vp, _i64, C.POINTER(PrepParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     ("rb_fastq_split", _i32, [_vp, _sz, _i32, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     ("rb_gunzip", _i32, [_vp, _sz, _i32, _vp, _sz, C.POINTER(_sz)]),
     ("rb_batch_create_fastq", _i32, [_i32, _vp, _sz, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),

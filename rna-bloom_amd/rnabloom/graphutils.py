@@ -1,6 +1,7 @@
 """Host mirror of the part of rnabloom.util.GraphUtils that sits directly on the neighbour-extension loop, batched over
 many k-mer pairs: the graph work (every getMaxCovSuccessor / getMaxCovPredecessor step) runs in two rb_graph_walk calls
 per batch; what is left on the host is the bookkeeping of R/util/GraphUtils.java:1591-1675."""
+import ctypes as C
 import math
 
 LOW_COMPLEXITY_THRESHOLD_SHORT_SEQ = 0.95          # R/util/SeqUtils.java:61
@@ -95,6 +96,7 @@ def getMaxCoveragePaths(graph, lefts, rights, bound, minKmerCov=1.0):
 import numpy as np
 
 from . import _native as N
+from .graph import _ptr
 
 
 def _combine(a, b):
@@ -498,6 +500,13 @@ def correctLongReads(graph, seqs, trimArtifact=True, **params):
     the seven-argument trimReverseComplementArtifact (mode TRIM_LONG, maxEdgeClip 150, the call's maxCovGradient), whose result is taken only
     if it is not empty and shorter (a sequence that call does not judge — a letter outside ACGTU — stays as it is); assembleValidKmers.
     Returns, per sequence, the list of strings the worker would put out: [] for a segment it discards."""
+    return correctLongReadsKept(graph, seqs, trimArtifact, **params)[0]
+
+
+def correctLongReadsKept(graph, seqs, trimArtifact=True, **params):
+    """correctLongReads with what the worker's `kept` needs beside the strings (R/RNABloom.java:3804-3839): per sequence, whether the corrected
+    list was not empty — the worker counts the read as kept then, even where assembleValidKmers makes no string of it (every k-mer has
+    count 0 and a letter outside ACGTU).  Returns (strings, kept)."""
     corrected = correctLongSequenceWindowed(graph, seqs, **params)
     alive = [i for i, t in enumerate(corrected) if t]
     texts = [corrected[i] for i in alive]
@@ -508,4 +517,108 @@ def correctLongReads(graph, seqs, trimArtifact=True, **params):
     out = [[] for _ in seqs]
     for i, segs in zip(alive, assembleValidKmers(graph, texts)):
         out[i] = segs
-    return out
+    return out, [bool(t) for t in corrected]
+
+
+# ---- the long-read worker from the raw read on (R/RNABloom.java:3700-3859) ----
+# rb_prep_params under the reference's names; the worker's values: the finder's ONT profile with seedLength = minPolyATail and window =
+# maxTipLength + minPolyATail (R/RNABloom.java:248-251), trimLowComplexityRegions(seq, 100, 500) (:3768)
+PREP_DEFAULTS = dict(reverseComplement=False, strandSpecific=False, minPolyATailLengthRequired=1, seedLength=12, minIdentity=0.9, maxGap=4,
+                     window=100, lcWindow=100, lcMinLength=500)
+PREP_DTYPE = np.dtype(N.PREP_REC_FIELDS)
+assert PREP_DTYPE.itemsize == 64
+
+
+def prepParams(k, **params):
+    unknown = set(params) - set(PREP_DEFAULTS)
+    if unknown:
+        raise TypeError("prepareLongReads: unknown parameter(s) %s" % sorted(unknown))
+    a = dict(PREP_DEFAULTS, **params)
+    return N.PrepParams(k, int(bool(a["reverseComplement"])), int(bool(a["strandSpecific"])), int(a["minPolyATailLengthRequired"] > 0),
+                        a["seedLength"], a["maxGap"], a["window"], a["lcWindow"], a["lcMinLength"], a["minIdentity"])
+
+
+def prepSegmentRoom(offsets, lcWindow):
+    """the layout rb_long_prepare asks for: seg_offsets (n + 1) with room for max(1, (len / lcWindow + 1) / 2) segments a read"""
+    lens = np.diff(np.asarray(offsets, np.int64))
+    so = np.zeros(lens.size + 1, np.int64)
+    np.cumsum(np.maximum(1, (lens // lcWindow + 1) // 2), out=so[1:])
+    return so
+
+
+def prepareLongFlat(seq, offsets, k, device=0, wantText=True, kernelMs=None, **params):
+    """rb_long_prepare on flat host text: read i is seq[offsets[i]:offsets[i + 1]] (uint8).  Returns (recs — PREP_DTYPE —, seg_offsets, segs —
+    an (slots, 2) int32 array, recs[i]["n_segments"] rows filled from seg_offsets[i] —, out — the transformed reads at `offsets`, or None).
+    kernelMs: a one-element float64 array that receives the kernels' time."""
+    seq = np.ascontiguousarray(seq, np.uint8)
+    off = np.ascontiguousarray(offsets, np.int64)
+    n = off.size - 1
+    p = prepParams(k, **params)
+    so = prepSegmentRoom(off, max(1, p.lc_window))
+    recs = np.zeros(n, PREP_DTYPE)
+    segs = np.zeros((int(so[-1]), 2), np.int32)
+    out = np.zeros(seq.size, np.uint8) if wantText else None
+    ms = None if kernelMs is None else kernelMs.ctypes.data_as(C.POINTER(C.c_double))
+    N.check(N.lib.rb_long_prepare(device, _ptr(seq), _ptr(off), n, C.byref(p), _ptr(so), _ptr(recs), _ptr(segs), _ptr(out), ms))
+    return recs, so, segs, out
+
+
+def prepareLongReads(reads, k, device=0, **params):
+    """What LongReadCorrectionWorker.run does to a raw read before its first graph call (R/RNABloom.java:3705-3779), for many reads in one
+    rb_long_prepare call: the reverse complement where asked, the poly-A tail and poly-T head and the five-way rule that cuts and turns the
+    read, trimLowComplexityRegions, hasPolyA.  k: reads shorter than k are discarded.  params: PREP_DEFAULTS' keys.  Returns (recs, segments,
+    texts): the records (PREP_DTYPE), per read the list of its segments as bytes ([] for a read that is too short or of low complexity), and
+    the transformed read (None for a read that is too short) — what the worker emits for a read of low complexity."""
+    reads = [r.encode() if isinstance(r, str) else bytes(r) for r in reads]
+    lens = np.fromiter((len(r) for r in reads), np.int64, len(reads))
+    off = np.zeros(len(reads) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    seq = np.frombuffer(b"".join(reads), np.uint8) if len(reads) else np.zeros(0, np.uint8)
+    recs, so, segs, out = prepareLongFlat(seq, off, k, device, True, **params)
+    raw = out.tobytes()
+    segments, texts = [], []
+    for i, rc in enumerate(recs):
+        if int(rc["status"]) == N.PREP_SHORT:
+            segments.append([]); texts.append(None)
+            continue
+        t = raw[off[i]:off[i] + int(rc["kept_end"]) - int(rc["kept_begin"])]
+        texts.append(t)
+        segments.append([t[b:e] for b, e in segs[so[i]:so[i] + int(rc["n_segments"])].tolist()])
+    return recs, segments, texts
+
+
+def correctLongReadsFromRaw(graph, names, reads, minKmerCov=1, trimArtifact=True, prep=None, **params):
+    """LongReadCorrectionWorker.run (R/RNABloom.java:3700-3859) for a batch of raw reads: prepareLongReads with the graph's k and strandedness
+    as strandSpecific (prep: its other parameters), then correctLongReads on the segments — twice at the most, since trimLowCovEdges = minKmerCov
+    > 1 and not hasPolyA (:3791) is per read and rb_graph_correct_long takes it per call —, then the worker's naming: _s<sid> for a read cut
+    into several segments, _p<partID> for a segment that comes back in several parts, which also clears hasPolyA (:3823-3836).  params: the
+    other keys of graph.LONG_DEFAULTS.  Returns (sequences, kept, discarded): the tuples (name, seq, length, score, isRepeat, hasPolyA) of
+    Sequence2 in the worker's order — a read of low complexity is emitted as it is with isRepeat true and score 0 — and the worker's counts."""
+    names = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    prep = dict(prep or {})
+    prep.setdefault("strandSpecific", bool(graph.stranded))
+    recs, segments, texts = prepareLongReads(reads, graph.k, graph.device, **prep)
+    polya = (recs["flags"] & N.PREP_HAS_POLYA) != 0
+    where = [(i, j) for i, segs in enumerate(segments) for j in range(len(segs))]
+    parts, alive = {}, {}
+    for trim in (False, True):
+        group = [(i, j) for i, j in where if (minKmerCov > 1 and not polya[i]) == trim]
+        if group:
+            got, live = correctLongReadsKept(graph, [segments[i][j] for i, j in group], trimArtifact, minKmerCov=minKmerCov, trimLowCovEdges=trim,
+                                             **params)
+            parts.update(zip(group, got))
+            alive.update(zip(group, live))
+    out, kept = [], 0
+    for i, (name, rc) in enumerate(zip(names, recs)):
+        if int(rc["status"]) == N.PREP_LOW_COMPLEXITY:
+            out.append((name, texts[i], len(texts[i]), 0.0, True, False))
+        any_kept = False
+        for j in range(len(segments[i])):
+            seg_name = name + (b"_s%d" % (j + 1) if len(segments[i]) > 1 else b"")
+            ps = parts[(i, j)]
+            has = bool(polya[i]) and len(ps) == 1
+            for q, s in enumerate(ps):
+                out.append((seg_name + (b"_p%d" % (q + 1) if len(ps) > 1 else b""), s, len(s), float(len(s)), False, has))
+            any_kept = any_kept or alive[(i, j)]              # (:3839: kept once the corrected list is not empty, whatever assembleValidKmers makes of it)
+        kept += any_kept
+    return out, kept, len(names) - kept
