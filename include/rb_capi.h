@@ -1153,6 +1153,50 @@ typedef struct rb_prep_rec {            /* 64 bytes */
 int rb_long_prepare(int device, const char *seq, const int64_t *offsets, int64_t n, const rb_prep_params *p, const int64_t *seg_offsets,
                     rb_prep_rec *recs, int32_t *out_segs, char *out_seq, double *kernel_ms);
 
+/* ---- subsampling of long reads: the accept / reject loop of SeqSubsampler on the device ----
+ * SeqSubsampler.strobemerBased (R/util/SeqSubsampler.java:339-481, the loop body :374-460) and kmerBased (:120-337, the loop bodies :150-226
+ * stranded and :233-318 canonical) for n_reads host reads, judged IN ARRAY ORDER against the counting filter of `cbf`, which the call reads AND
+ * writes; the handle is taken exclusively.  The filter's state and the handle's op ordinal carry from one call to the next, so a library cut
+ * into several calls gives the bytes of one call.  Per read:
+ *   1. its elements are hashed.  RB_SUB_STROBEMER: StrobeHashIterator(3, k, wmin, wmax).getInterval(i) — hash, start = i, end — as rb_strobemers;
+ *      start() fails for numKmers <= 2 * wmax (or fewer than k letters) and the read is KEPT (:456-460).  RB_SUB_KMER: the k-mer pairs at shift
+ *      k + 1 as rb_kmer_pair_hashes (canonical != 0: min of the forward and the reverse pair, :266-268) for i in [start, end), start / end as
+ *      :167-175 with tooShort = length < 3 * max_edge_clip; start() fails for fewer than k letters and the read is DROPPED; end - start < 0
+ *      throws in the reference (new boolean[negative]) and is reported as RB_SUB_NOT_JUDGED, dropped, nothing incremented.
+ *   2. seen[i] = cbf.getCount(hash_i) >= max_multiplicity (CountingBloomFilter.getCount :235-251).
+ *   3. the scan.  Strobemer mode :394-434 with maxEdgeClip = max(max_edge_clip, wmax): the namInterval fold (ComparableInterval.merge succeeds
+ *      iff IntervalUtils.getOverlap > 0), its four breaks and the tail test.  k-mer mode :187-195 / :273-281: a run of 2k + 1 unseen pairs.
+ *   4. a kept read increments every DISTINCT hash of a set once (CountingBloomFilter.increment :170-194): strobemer mode the hashes with
+ *      !seen[i] (:441-453); k-mer mode ALL pair hashes at gaps 1, 2 and 0 over the three ranges of :204-217 (:290-309).  The reference leaves
+ *      the order of one read's increments open (parallelStream over a HashSet); here it is fixed: the distinct hashes are incremented as if one
+ *      after the other in order of FIRST OCCURRENCE (strobemers by i; pairs in the gap-1 list, then gap-2, then gap-0, each by i), the j-th
+ *      increment of the call drawing rng31(seed, ordinal0 + j, 0), and the op ordinal advances by the number of increments — what a loop of
+ *      rb_graph_apply(RB_OP_ADD_COUNT_ONLY) of one hash does.  Any serial order is a legal execution of the reference.
+ * out_keep[i]: 1 kept, 0 dropped.  out_recs (may be NULL), 8 ints a read in this order: status (RB_SUB_*); the reference line that decided
+ * (RB_SUB_LINE_*); the deciding index (-1 where no element decided); strobemer mode namInterval.start and namInterval.end (-1, -1 when null),
+ * k-mer mode `start` and missingChainLen when the loop ended; the number of elements (strobemers, or end - start); how many are unseen; the
+ * distinct hashes incremented.  totals (may be NULL), 4 values: reads kept, increments, reads not judged, nanoseconds in the walker kernel
+ * (by events, summed over the pieces).
+ * Hashing of a piece is the sketch kernels of rb_strobemers / rb_kmer_pair_hashes with the results left on the device; then ONE launch of ONE
+ * workgroup walks the piece's reads one after the other: all lanes look the counts up, the scan is a prefix maximum plus a first-index
+ * reduction, the distinct hashes are picked in an open-addressing set (in LDS up to RB_SUB_LDS_ELEMS elements of a read, in device scratch
+ * beyond), increments that share no counter with another increment of the read are applied by all lanes at once and the others by one lane in
+ * the defined order.  Pieces of 16 M letters (RB_QUERY_PIECE counts letters here); results do not depend on the cuts.
+ * Refused (RB_ERR_INVALID): null cbf / p / out_keep, a shard handle, no counting filter, k outside the handle's, mode outside 0 .. 1, strobemer
+ * mode with wmin < 1 or wmax < wmin, max_multiplicity < 1, max_edge_clip < 0 or above 2^28, decreasing offsets, a read of more than 2^28 letters. */
+enum { RB_SUB_STROBEMER = 0, RB_SUB_KMER = 1 };                                                   /* rb_subsample_params.mode */
+enum { RB_SUB_DROPPED = 0, RB_SUB_KEPT_SCAN = 1, RB_SUB_KEPT_TAIL = 2, RB_SUB_KEPT_START_FAILED = 3, RB_SUB_NOT_JUDGED = 4 };   /* status */
+enum { RB_SUB_LINE_SEEN_BEYOND_EDGE = 402, RB_SUB_LINE_MERGE_FAILED = 408, RB_SUB_LINE_UNSEEN_BEYOND_EDGE = 414, RB_SUB_LINE_GAP = 421,
+       RB_SUB_LINE_TAIL = 429, RB_SUB_LINE_START_FAILED = 456,                                    /* strobemer mode */
+       RB_SUB_LINE_KMER_START_FAILED = 153, RB_SUB_LINE_KMER_RANGE = 178, RB_SUB_LINE_KMER_CHAIN = 191, RB_SUB_LINE_KMER_NO_CHAIN = 197,
+       RB_SUB_LINE_KMER_START_FAILED_C = 236, RB_SUB_LINE_KMER_RANGE_C = 263, RB_SUB_LINE_KMER_CHAIN_C = 277, RB_SUB_LINE_KMER_NO_CHAIN_C = 283 };
+#define RB_SUB_LDS_ELEMS 2048
+typedef struct rb_subsample_params {
+    int32_t mode, k, wmin, wmax, canonical, max_multiplicity, max_edge_clip, reserved;
+} rb_subsample_params;
+int rb_subsample_reads(rb_graph *cbf, const rb_subsample_params *p, const char *seq, const int64_t *offsets, int64_t n_reads,
+                       uint8_t *out_keep, int32_t *out_recs, int64_t *totals);
+
 /* ---- input formats ----
  * FASTQ text -> the buffers rb_graph_add_reads / rb_batch_create_ascii take.  FastqReader.nextWithoutName
  * R/io/FastqReader.java:140-186: four lines per record, line 1 starts with '@', line 3 with '+' (else RB_ERR_INVALID with

@@ -212,6 +212,14 @@ public final class NativeGraph {
      *  written, 2: trimmed to nothing).  Read-only. */
     public static native void correctLong(long h, ByteBuffer seq, long[] offsets, int n, int[] params, float maxCovGradient, float percentIdentity,
                                           long[] outOffsets, ByteBuffer out, int[] recs);
+    /** The accept / reject loop of SeqSubsampler.strobemerBased / kmerBased (rb_subsample_reads, R/util/SeqSubsampler.java:374-460, :150-226,
+     *  :233-318) over n reads IN ARRAY ORDER against the counting filter of handle h, which the call reads and writes; the filter and the op
+     *  ordinal carry from call to call.  params: mode (0 strobemers, 1 k-mer pairs), k, wMin, wMax, canonical (k-mer mode, !stranded),
+     *  maxMultiplicity, maxEdgeClip.  keep: a byte per read (1 kept); recs (may be null): 8 ints a read — status, the reference line that
+     *  decided, the deciding index, namInterval.start, namInterval.end (k-mer mode: start, missingChainLen), elements, unseen, distinct hashes
+     *  incremented; totals (may be null): kept, increments, not judged, nanoseconds in the walker.  One read's distinct hashes are incremented
+     *  in order of first occurrence: one of the orders the reference's parallelStream may take. */
+    public static native void subsampleReads(long h, int[] params, ByteBuffer seq, long[] offsets, int n, byte[] keep, int[] recs, long[] totals);
     /** What LongReadCorrectionWorker.run does to n raw reads before its first graph call (rb_long_prepare, R/RNABloom.java:3705-3779): the
      *  reverse complement where asked, PolyATailFinder.findPolyATail / findPolyTHead and the five-way rule that cuts and turns the read,
      *  SeqUtils.trimLowComplexityRegions, hasPolyA.  No graph handle: text work on `device`.  params: k (shorter reads are discarded),

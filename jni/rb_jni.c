@@ -593,6 +593,30 @@ void FN(correctLong)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offse
     lr(e, offsets, po, JNI_ABORT); lr(e, outOffsets, poo, JNI_ABORT); ir(e, recs, rc16, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_subsample_reads: params holds the seven ints of rb_subsample_params in its order (mode, k, wmin, wmax, canonical, maxMultiplicity, maxEdgeClip);
+ * keep: a byte per read; recs: 8 ints a read, or null; totals: 4 longs, or null */
+void FN(subsampleReads)(JNIEnv *e, jclass c, jlong h, jintArray params, jobject seq, jlongArray offsets, jint n, jbyteArray keep, jintArray recs,
+                        jlongArray totals) {
+    (void)c;
+    if (n < 0 || !params || (*e)->GetArrayLength(e, params) < 7 || !offsets || (*e)->GetArrayLength(e, offsets) < n + 1 || !keep ||
+        (*e)->GetArrayLength(e, keep) < n || (recs && (*e)->GetArrayLength(e, recs) / 8 < n) || (totals && (*e)->GetArrayLength(e, totals) < 4)) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "subsampleReads: an array is too short for n reads");
+        return;
+    }
+    jint *pp = ia(e, params);
+    rb_subsample_params p = {pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], pp[6], 0};
+    ir(e, params, pp, JNI_ABORT);
+    jlong *po = la(e, offsets), *pt = totals ? la(e, totals) : NULL;
+    jint *pr = recs ? ia(e, recs) : NULL;
+    jbyte *pk = (*e)->GetByteArrayElements(e, keep, NULL);
+    int rc = rb_subsample_reads(G(h), &p, (const char *)direct(e, seq), (const int64_t *)po, n, (uint8_t *)pk, (int32_t *)pr, (int64_t *)pt);
+    (*e)->ReleaseByteArrayElements(e, keep, pk, 0);
+    lr(e, offsets, po, JNI_ABORT);
+    if (recs) ir(e, recs, pr, 0);
+    if (totals) lr(e, totals, pt, 0);
+    if (rc) throw_rc(e, rc);
+}
+
 /* rb_long_prepare: params holds the nine ints of rb_prep_params in its order; a record (rb_prep_rec, 64 bytes) is 16 ints to Java; segs holds 2 ints
  * per slot at 2 * segOffsets[i]; out == null: no transformed text */
 void FN(longPrepare)(JNIEnv *e, jclass c, jint device, jobject seq, jlongArray offsets, jint n, jintArray params, jfloat minIdentity,

@@ -69,4 +69,11 @@ struct FastqChunk { rb_batch *b = nullptr; size_t consumed = 0; int64_t records 
 FastqChunk fastq_batch_create(int device, const char *text, size_t n, bool final, int min_base_qual, bool use_qual, hipStream_t st, DevPool *pool = nullptr);
 // FASTA text (FastaReader.next semantics) the same way; *ended: an empty line in header position ended the iteration
 FastqChunk fasta_batch_create(int device, const char *text, size_t n, bool final, hipStream_t st, bool *ended, DevPool *pool = nullptr);
+
+// the sketch kernels of rb_strobemers / rb_kmer_pair_hashes with their results left on the device (rb_sketch.hip; rb_subsample.hip walks them).
+// Both return with the device idle.  soffsets / koff: n_reads + 1 element offsets on the host.
+void sketch_strobemers_device(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int n, int wmin, int wmax,
+                              int64_t *soffsets, DevBuf &d_oh, DevBuf &d_oe);
+void sketch_kmer_hashes_device(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, bool need_r, std::vector<int64_t> &koff,
+                               DevBuf &d_f, DevBuf &d_r);
 }  // namespace rb

@@ -863,3 +863,44 @@ int rb_minimizer_set(int device, const char *seq, const int64_t *offsets, int64_
 }
 
 }  // extern "C"
+
+// ---- the same kernels with the results left on the device (rb_subsample.hip: no hash crosses the link) ----
+namespace rb {
+
+// rb_strobemers of n_reads reads: soffsets (n_reads + 1, host) is filled; the hashes and getInterval's ends stay in d_oh / d_oe, in read order
+void sketch_strobemers_device(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, int n, int wmin, int wmax,
+                              int64_t *soffsets, DevBuf &d_oh, DevBuf &d_oe) {
+    DevBuf d_koff, d_h, d_soff, d_os, d_tiles;
+    std::vector<int64_t> koff;
+    soffsets[0] = 0;
+    for (int64_t i = 0; i < n_reads; ++i) {
+        int64_t l = offsets[i + 1] - offsets[i], nk = l >= k ? l - k + 1 : 0;
+        soffsets[i + 1] = soffsets[i] + ((nk > (int64_t)wmax * (n - 1)) ? nk - (int64_t)wmax * (n - 2) - wmin : 0);   // StrobeHashIterator.java:53-57
+    }
+    const int64_t total = soffsets[n_reads];
+    if (!total) return;
+    hash_all(device, seq, offsets, n_reads, k, 0, koff, d_koff, d_h);
+    d_soff.reserve(((size_t)n_reads + 1) * 8); d_oh.reserve((size_t)total * 8); d_os.reserve((size_t)total * 4); d_oe.reserve((size_t)total * 4);
+    RB_HIP(hipMemcpy(d_soff.p, soffsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice));
+    const size_t lds = ((size_t)SK_TILE + (size_t)wmax * (size_t)(n - 1)) * 16;
+    if (lds > SK_LDS_MAX || n > RB_MAX_STROBES || sk_force_simple())
+        hipLaunchKernelGGL(k_strobemers, dim3(blocks_for(total)), dim3(TPB), 0, 0, d_h.as<uint64_t>(), d_koff.as<int64_t>(), d_soff.as<int64_t>(),
+                           n_reads, total, k, n, wmin, wmax, d_oh.as<uint64_t>(), d_os.as<int32_t>(), d_oe.as<int32_t>());
+    else {
+        uint32_t nt = 0;
+        make_tiles(soffsets, n_reads, d_tiles, &nt);
+        hipLaunchKernelGGL(k_randstrobes_tile, dim3(nt), dim3(SK_TPB), lds, 0, d_h.as<uint64_t>(), (const uint64_t *)nullptr, d_koff.as<int64_t>(),
+                           d_soff.as<int64_t>(), d_tiles.as<SkTile>(), n, wmin, wmax, 0, k, d_oh.as<uint64_t>(), (int32_t *)nullptr, d_os.as<int32_t>(), d_oe.as<int32_t>());
+    }
+    RB_HIP(hipGetLastError());
+    RB_HIP(hipDeviceSynchronize());           // the k-mer hashes and the tiles are released on return
+}
+
+// the all-window hashes rb_kmer_pair_hashes combines: koff (n_reads + 1, host), the forward hashes in d_f and, where asked, the reverse ones in d_r
+void sketch_kmer_hashes_device(int device, const char *seq, const int64_t *offsets, int64_t n_reads, int k, bool need_r, std::vector<int64_t> &koff,
+                               DevBuf &d_f, DevBuf &d_r) {
+    DevBuf d_koff;
+    hash_fr(device, seq, offsets, n_reads, k, need_r, koff, d_koff, d_f, d_r);
+}
+
+}  // namespace rb

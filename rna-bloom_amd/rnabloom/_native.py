@@ -57,6 +57,16 @@ PREP_REC_FIELDS = [("status", "<i4"), ("flags", "<i4"), ("kept_begin", "<i4"), (
                    ("head_start", "<i4"), ("head_end", "<i4"), ("n_windows", "<i4"), ("n_low", "<i4"), ("offset", "<i4"), ("n_segments", "<i4"),
                    ("tail_searches", "<i4"), ("head_searches", "<i4"), ("reserved", "<i4", (2,))]
 PREP_MAX_LC_WINDOW = 1024
+# rb_subsample_reads: rb_subsample_params.mode; the record's status; the reference line that decided (R/util/SeqSubsampler.java); the record's
+# eight ints in order (k-mer mode: nam_start is `start`, nam_end the missingChainLen the loop ended with)
+SUB_STROBEMER, SUB_KMER = 0, 1
+SUB_DROPPED, SUB_KEPT_SCAN, SUB_KEPT_TAIL, SUB_KEPT_START_FAILED, SUB_NOT_JUDGED = range(5)
+SUB_LINE_SEEN_BEYOND_EDGE, SUB_LINE_MERGE_FAILED, SUB_LINE_UNSEEN_BEYOND_EDGE, SUB_LINE_GAP, SUB_LINE_TAIL, SUB_LINE_START_FAILED = \
+    402, 408, 414, 421, 429, 456
+SUB_LINE_KMER_START_FAILED, SUB_LINE_KMER_RANGE, SUB_LINE_KMER_CHAIN, SUB_LINE_KMER_NO_CHAIN = 153, 178, 191, 197
+SUB_LINE_KMER_START_FAILED_C, SUB_LINE_KMER_RANGE_C, SUB_LINE_KMER_CHAIN_C, SUB_LINE_KMER_NO_CHAIN_C = 236, 263, 277, 283
+SUB_REC_FIELDS = ("status", "line", "index", "nam_start", "nam_end", "elements", "unseen", "incremented")
+SUB_LDS_ELEMS = 2048
 PAIRC_REC_FIELDS = [("status", "<i4"), ("end", "<i4"), ("rounds_run", "<i4"), ("flags", "<i4"), ("left_len", "<i4"), ("right_len", "<i4"),
                     ("thr_first", "<u4"), ("thr_last", "<u4"), ("found_first", "<i4"), ("left_changed", "<i4"), ("right_changed", "<i4"),
                     ("gaps_replaced", "<i4"), ("gaps_trimmed", "<i4"), ("gaps_kept", "<i4"), ("mismatches", "<i4"), ("reserved", "<i4")]
@@ -137,6 +147,14 @@ class PrepParams(C.Structure):
 assert C.sizeof(PrepParams) == 40
 
 
+class SubsampleParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("wmin", C.c_int32), ("wmax", C.c_int32), ("canonical", C.c_int32),
+                ("max_multiplicity", C.c_int32), ("max_edge_clip", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SubsampleParams) == 32
+
+
 class Profile(C.Structure):
     _fields_ = [("n", C.c_int32), ("name", C.c_char_p * PROF_MAX), ("ms", C.c_double * PROF_MAX),
                 ("launches", C.c_int64 * PROF_MAX)]
@@ -212,6 +230,7 @@ SYMBOLS = [
     ("rb_minimizers_next", _i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("rb_minimizer_set", _i32, [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     ("rb_long_prepare", _i32, [_i32, _vp, _vp, _i64, C.POINTER(PrepParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    ("rb_subsample_reads", _i32, [_vp, C.POINTER(SubsampleParams), _vp, _vp, _i64, _vp, _vp, _vp]),
     ("rb_fastq_split", _i32, [_vp, _sz, _i32, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     ("rb_gunzip", _i32, [_vp, _sz, _i32, _vp, _sz, C.POINTER(_sz)]),
     ("rb_batch_create_fastq", _i32, [_i32, _vp, _sz, _i32, _i32, _i32, C.POINTER(_vp), C.POINTER(_sz)]),
