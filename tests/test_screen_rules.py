@@ -87,12 +87,14 @@ def max_coverage_path(s, left, right, bound, lookahead, tags=None):
     """getMaxCoveragePath(graph, left, right, bound, lookahead, bf) (:1677-1776): the path as a list, or None"""
     left_set, left_path = set(), []
     best = left
-    for _ in range(bound):
+    for step in range(bound):
         best = s.greedy_once(best, 0, lookahead)
         if best is None:
             break
         if best == right:
-            if tags is not None: tags.add("path_from_the_left")
+            if tags is not None:
+                tags.add("path_from_the_left")
+                if step >= 64: tags.add("left_walk_arrives_after_64_steps")     # its 65th step or a later one: the walk's set held 64 k-mers and more
             return left_path
         if best in left_set:
             break
@@ -110,7 +112,9 @@ def max_coverage_path(s, left, right, bound, lookahead, tags=None):
             right_path.insert(0, best)
             for idx in range(len(left_path) - 1, -1, -1):
                 if left_path[idx] == best:
-                    if tags is not None: tags.add("paths_spliced")
+                    if tags is not None:
+                        tags.add("paths_spliced")                 # (ScPath.form == 3, met at entry idx of the left walk)
+                        if idx >= 64: tags.add("spliced_at_entry_64_or_beyond")
                     return left_path[:idx] + right_path
         elif best not in right_set:
             right_set.add(best); right_path.insert(0, best)
@@ -359,7 +363,10 @@ class ScreenWorld:
     TAIL = 20
     LONGEST_TAIL = 29
 
-    def __init__(self, k, stranded, seed, d=30, hashes=(2, 2, 2), gate_h=2, read_len=100, tile=10, seg=150, long_len=1300):
+    SIZES = (4_800_011, 4_800_011, 4_800_017)
+    GATE_SIZE = 1_200_007
+
+    def __init__(self, k, stranded, seed, d=30, hashes=(2, 2, 2), gate_h=2, read_len=100, tile=10, seg=150, long_len=1300, sizes=None, gate_size=None):
         from oracle import rbo
         rng = np.random.default_rng(seed)
         self.k, self.stranded, self.d, self.hashes, self.gate_h = k, stranded, d, hashes, gate_h
@@ -396,7 +403,7 @@ class ScreenWorld:
               ("chimera-then-snv", a1[60:seg + 60] + put(b1[seg:3 * seg - 20], k + 105, chr(other(b1[seg + k + 105])[0]))),
               ("five-thousand-bases", ((big + a1 + b1 + c1 + tandem + u + c2 + big[::-1]) * 2)[:5000]),
               ("one-kmer-assembled", a1[70:70 + k]), ("two-kmers-assembled", a1[70:71 + k]), ("three-kmers-assembled", a1[70:72 + k]),
-              ("one-kmer-not-assembled", u[70:70 + k]), ("branch-free", big[200:400])]
+              ("one-kmer-not-assembled", u[70:70 + k]), ("branch-free", big[200:max(400, k + 257)])]        # (200 letters, and no fewer than 58 k-mers)
         for n_k in (63, 64, 65):
             q.append(("kmers-%d" % n_k, big[300:300 + n_k + k - 1]))
             q.append(("chimera-kmers-%d" % n_k, a1[60:70 + k] + b1[seg:seg + n_k - 11]))    # 11 k-mers of gene A, then gene B (k = 25)
@@ -435,8 +442,8 @@ class ScreenWorld:
                     starts.append(len(tt) - read_len)
                 reads += [tt[a:a + read_len] for a in starts] * m
         self.reads = reads
-        self.sizes = (4_800_011, 4_800_011, 4_800_017)
-        self.gate_size = 1_200_007
+        self.sizes = tuple(sizes or self.SIZES)
+        self.gate_size = gate_size or self.GATE_SIZE
         self.og = rbo.Graph(*self.sizes, *hashes, k, stranded, True, 5)
         self.og.set_read_pair_distance(d)
         self.packed = rbo.pack_reads(reads, [b"I" * len(s_) for s_ in reads])
