@@ -820,6 +820,34 @@ typedef struct rb_repr_rec {            /* 48 bytes */
 } rb_repr_rec;
 int rb_graph_represented(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
                          int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out);
+/* The in-order represented-then-add loop of the transcript stage for n host sequences: TranscriptWriter.write (R/RNABloom.java:1639-1720) —
+ * `if (!represented(transcriptKmers, graph, screeningBf, …)) { for (Kmer kmer : transcriptKmers) screeningBf.add(kmer.getHash()); … }` — and
+ * GraphUtils.reduceRedundancy (R/util/GraphUtils.java:652-699), the same loop over a FASTA sorted by length.  For i = 0 .. n - 1 in list order
+ * sequence i is judged exactly as rb_graph_represented judges it, but against the gate AS IT STANDS THEN: the gate at the start of the call
+ * plus the k-mers of every earlier kept sequence of this call.  Sequential across sequences, wide inside one: per piece the getKmers rows of
+ * all sequences are made side by side, then ONE workgroup walks the piece's sequences in order in ONE launch — all its lanes fill the
+ * sequence's gate bits, one wavefront runs the represented body, all lanes add a kept sequence's k-mers (DESIGN.md §5 "Represented, then add").
+ *   out[12 i ..]: rb_repr_rec, the same 12 ints as rb_graph_represented writes.  A record that is judged and false (flags == 0) keeps the
+ *   sequence: keep[i] = 1, and getHash() of every k-mer of it (the forward hash on a stranded graph, else the signed minimum of the two
+ *   strands') is added to the gate's dbgbf through the gate's own num_hash functions (BloomFilter.add, R/bloom/BloomFilter.java:133-141);
+ *   median[i] (where median is given) = getMedianKmerCoverage of its counts (R/util/GraphUtils.java:229-247: the float32 mean of the two middle
+ *   values for an even number), the writer's `c=` value.  Otherwise keep[i] = 0, nothing is added and median[i] = 0.  Sequences flagged
+ *   RB_SCREEN_NO_KMER or RB_SCREEN_BAD_LETTER add nothing and the walk goes on (the reference's worker never hands the writer an empty list;
+ *   odd letters are the caller's business, as everywhere).
+ *   The stop rule: the walk STOPS at the first RB_SCREEN_OVER_BUDGET sequence, since every later answer would depend on a decision the
+ *   library refuses to guess.  That sequence's record says over budget, *n_done is its index, and every later record is the blank record
+ *   with RB_SCREEN_NOT_REACHED, keep 0, median 0.  Without such a stop *n_done == n.  The caller decides the stopped sequence itself and
+ *   calls again on the rest: the gate carries the state, so one call, three calls and any cut of the list leave the same records, keep
+ *   flags and gate bytes — as do the pieces (RB_QUERY_PIECE), whatever their size.
+ * g is read-only (shared lock); the gate is WRITTEN (unique lock), the two taken in address order as rb_graph_screen_fragments takes its
+ * two.  Scratch as rb_graph_represented with the walk rows of ONE wavefront, and 5 more bytes per sequence.  Profile entry
+ * "represented_then_add" (getKmers and the walker of every piece).
+ * Refused (RB_ERR_INVALID, no output byte written, no filter changed): everything rb_graph_represented refuses; gate == g; with n > 0 a null
+ * keep or n_done.  n == 0 succeeds and touches nothing. */
+enum { RB_SCREEN_NOT_REACHED = 64 };                                                                                             /* rb_repr_rec.flags: not judged, behind an over-budget stop */
+int rb_graph_represented_then_add(rb_graph *g, rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                                  int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out, uint8_t *keep,
+                                  float *median /* may be NULL */, int64_t *n_done);
 /* GraphUtils.trimReverseComplementArtifact for n host sequences, the last per-sequence step of the transcript worker (R/RNABloom.java:1914), of
  * the fragment worker (:2206) and of the long-read corrector (:3806).  Each of the three overloads is pure and returns a contiguous sub-list of
  * the k-mers it was given, so the answer is a range [begin, end) of the sequence's k-mers (the trimmed text is the letters begin .. end + k - 2,

@@ -197,6 +197,16 @@ public final class NativeGraph {
      *  hasDepth* excused, the form of the last path (0 none, 1 from the left, 2 from the right, 3 spliced), 0.  Read-only on both handles. */
     public static native void represented(long h, long gateHandle, ByteBuffer seq, long[] offsets, int n, int lookahead, int maxIndelSize,
                                           int maxEdgeClipLength, float percentIdentity, long maxVisits, int[] recs);
+    /** The in-order represented-then-add loop of TranscriptWriter.write (rb_graph_represented_then_add; R/RNABloom.java:1639-1720) and of
+     *  GraphUtils.reduceRedundancy (R/util/GraphUtils.java:652-699) for n sequences in list order: sequence i is judged as represented judges
+     *  it, but against gateHandle's dbgbf — the writer's screeningBf, which this call WRITES — as every earlier kept sequence of the call
+     *  left it.  recs as represented's; keep[i] = 1 where the sequence is judged and not represented: the hash of each of its k-mers has
+     *  been added to the gate, and median[i] (median may be null) is its getMedianKmerCoverage, the header's c= value; 0 elsewhere.
+     *  Returns n, or the index of the first sequence whose depth search ran out of its budget (flags 32): the walk stops there, the records
+     *  behind it are blank with flags 64 (not reached), and the caller decides that sequence itself and calls again on the rest. */
+    public static native long representedThenAdd(long h, long gateHandle, ByteBuffer seq, long[] offsets, int n, int lookahead, int maxIndelSize,
+                                                 int maxEdgeClipLength, float percentIdentity, long maxVisits, int[] recs, byte[] keep,
+                                                 float[] median);
     /** GraphUtils.trimReverseComplementArtifact (rb_graph_trim_rc_artifacts) of n sequences: mode 0 the (kmers, graph, stranded) overload
      *  (R/util/GraphUtils.java:8588-8661), 1 the one with maxEdgeClip (:7918-8057), 2 the one with maxEdgeClip and maxCovGradient (:7762-7916);
      *  the graph's own strandedness is the reference's `stranded`.  recs holds 16 ints per sequence — flags (1: a line of the reference cut,

@@ -560,6 +560,26 @@ void FN(represented)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlon
     lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc12, 0);
     if (rc) throw_rc(e, rc);
 }
+/* rb_graph_represented_then_add: records as represented's; keep a byte and median a float per sequence (median may be null); returns n_done */
+jlong FN(representedThenAdd)(JNIEnv *e, jclass c, jlong h, jlong gate, jobject seq, jlongArray offsets, jint n, jint lookahead, jint maxIndelSize,
+                             jint maxEdgeClipLength, jfloat percentIdentity, jlong maxVisits, jintArray recs, jbyteArray keep, jfloatArray median) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!offsets || !recs || !keep || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, recs) / 12 < n ||
+                            (*e)->GetArrayLength(e, keep) < n || (median && (*e)->GetArrayLength(e, median) < n)))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "representedThenAdd: an array is too short for n sequences");
+        return 0;
+    }
+    jlong *po = la(e, offsets);
+    jint *rc12 = ia(e, recs);
+    jbyte *pk = ba(e, keep);
+    jfloat *pm = fa(e, median);
+    int64_t done = n;
+    int rc = rb_graph_represented_then_add(G(h), gate ? G(gate) : NULL, (const char *)direct(e, seq), (const int64_t *)po, n, lookahead, maxIndelSize,
+                                           maxEdgeClipLength, percentIdentity, maxVisits, (rb_repr_rec *)rc12, (uint8_t *)pk, pm, &done);
+    lr(e, offsets, po, JNI_ABORT); ir(e, recs, rc12, 0); br(e, keep, pk, 0); fr(e, median, pm, 0);
+    if (rc) throw_rc(e, rc);
+    return (jlong)done;
+}
 /* rb_graph_trim_rc_artifacts: a record (rb_trim_rec, 64 bytes) is 16 ints to Java: flags, begin, end, mode, then why, i0, i1, i2, i3 of pass 0 and of pass 1, 0, 0 */
 void FN(trimArtifacts)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jint mode, jint maxEdgeClip, jfloat maxCovGradient,
                        jintArray recs) {

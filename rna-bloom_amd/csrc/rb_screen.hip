@@ -499,20 +499,25 @@ __device__ bool sc_identity_ok(const ScArgs &a, const ScSeq &sq, S s, int slen, 
     return !(ce_identity(d, slen, tlen) < a.percent_identity);
 }
 
-// represented of sequence r of the piece, by one wavefront
-__device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, int *lds_row, int *dev_row, uint32_t lane) {
+// represented of sequence r of the piece, by one wavefront: the record's flags.  FILLED: the sequence's gate bits stand in a.gbit already
+// (k_represented_walk fills them with its whole workgroup), else the wavefront fills them first.
+template <bool FILLED = false>
+__device__ int sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLevel *dfs, int *lds_row, int *dev_row, uint32_t lane) {
     const int64_t k0 = a.kof[r];
     const int nk = (int)(a.kof[r + 1] - k0), k = a.k, clip = a.max_depth, max_indel = a.max_indel;
     if (nk == 0 || wave_bad_letter(a.valid + a.woff[r], nk + a.k - 1, lane)) {
-        if (lane == 0) a.reprs[r] = repr_blank(nk == 0 ? RB_SCREEN_NO_KMER : RB_SCREEN_BAD_LETTER);
-        return;
+        const int flags = nk == 0 ? RB_SCREEN_NO_KMER : RB_SCREEN_BAD_LETTER;
+        if (lane == 0) a.reprs[r] = repr_blank(flags);
+        return flags;
     }
     const ScSeq sq{reinterpret_cast<const uint32_t *>(a.codes + a.woff[r]), a.F + k0, a.R + k0, a.cnt + k0, a.gbit + k0, nk, a.stranded};
-    for (int i = (int)lane; i < nk; i += 64) {
-        const uint64_t f = sq.F[i];
-        a.gbit[k0 + i] = (uint8_t)bits_lookup(a.gate.bits, a.gate.mod, a.gate.num_hash, a.kmul, a.stranded ? f : smin(f, sq.R[i]));
+    if constexpr (!FILLED) {
+        for (int i = (int)lane; i < nk; i += 64) {
+            const uint64_t f = sq.F[i];
+            a.gbit[k0 + i] = (uint8_t)bits_lookup(a.gate.bits, a.gate.mod, a.gate.num_hash, a.kmul, a.stranded ? f : smin(f, sq.R[i]));
+        }
+        wave_fence();
     }
-    wave_fence();
     rb_repr_rec rec = repr_blank(0);
     rec.why = RB_REPR_WHY_TRUE;
     auto decide = [&](int why, int left, int right, int expected, int found, int d) {
@@ -529,7 +534,7 @@ __device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLeve
         if (start > 0 && last < 0) {                             // check left edge kmers (:745-753)
             int v = 1, d = -1;
             if (start < clip) v = sc_has_depth(a, sq, rw, 1, false, 0, clip - start, lane);
-            if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return; }
+            if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return RB_SCREEN_OVER_BUDGET; }
             if (v == 0) ++rec.tips_skipped;
             else {
                 const int n = sc_greedy_walk(a, sq, rw, dfs, 1, start, start, lane);
@@ -570,7 +575,7 @@ __device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLeve
         const int expected = nk - last - 1;
         int v = 1, d = -1;
         if (expected < clip) v = sc_has_depth(a, sq, rw, 0, false, nk - 1, clip - expected, lane);
-        if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return; }
+        if (v < 0) { if (lane == 0) a.reprs[r] = repr_blank(RB_SCREEN_OVER_BUDGET); return RB_SCREEN_OVER_BUDGET; }
         if (v == 0) ++rec.tips_skipped;
         else {
             const int n = sc_greedy_walk(a, sq, rw, dfs, 0, last, expected, lane);
@@ -583,6 +588,7 @@ __device__ void sc_repr_one(const ScArgs &a, int64_t r, const ScRows &rw, ScLeve
     }
     if (open) rec.flags = RB_REPR_REPRESENTED;
     if (lane == 0) a.reprs[r] = rec;
+    return rec.flags;
 }
 
 // as k_screen; the alignment's row is the wavefront's LDS row, or — longer than LEV_LDS columns — the ints at lev_off of its scratch slot
@@ -597,6 +603,72 @@ __global__ void __launch_bounds__(SC_TPB) k_represented(ScArgs a, uint8_t *scrat
         sc_repr_one(a, r, rw, s_dfs[wv], s_row[wv], reinterpret_cast<int *>(mine + lev_off), lane);
         wave_fence();
     }
+}
+
+// ---- represented, then add: TranscriptWriter.write (R/RNABloom.java:1639-1720), GraphUtils.reduceRedundancy (R/util/GraphUtils.java:652-699) ----
+// The loop is sequential ACROSS sequences — a sequence is judged against the gate as every earlier kept sequence left it — and wide INSIDE
+// one: nk gate look-ups before the verdict, nk x num_hash bit sets behind a verdict of "not represented".  So ONE workgroup walks the piece's
+// sequences one after the other in ONE launch (DESIGN.md §5 "Represented, then add"):
+//   the fill     a lane per k-mer, all wavefronts: a.gbit[i] = gate.lookup(getHash(k-mer i)); sc_repr_one<true> takes the bits as filled;
+//   the verdict  wavefront 0 alone: the represented body as k_represented runs it, walk rows in the one scratch slot, DFS and alignment rows
+//                in LDS; kept (flags == 0): getMedianKmerCoverage of the counts; keep, median and the record by lane 0;
+//   the add      a lane per (k-mer, hash function), all wavefronts: an atomic OR of agent scope each (BloomFilter.add, R/bloom/BloomFilter.java:133-137).
+// The walker reads gate bits it set a moment earlier, by plain loads (the body's, unchanged).  Visibility, the fence form: the ORs are done in
+// L2; behind them EVERY wavefront executes __threadfence() — its acquire half drops the lines of the gate that this CU's vector L1 holds from
+// before the ORs — and the workgroup meets at __syncthreads() before the next sequence's first gate load.  The gate reaches the kernel as a
+// plain pointer: no __restrict__, no promise of invariance, so no gate load is hoisted over the fence or sent down the scalar path.  The
+// other form (every gate load a relaxed atomic of agent scope, as rb_subsample.hip reads its counters) would put a load policy into every walk
+// and search of the body for the sake of this one kernel; the fence costs a few microseconds per KEPT sequence and nothing per represented one.
+// One workgroup waits on nobody: no flags, no spins.  The walk stops at the first sequence that is over its budget; *stop is its index in
+// the piece, or pn.
+constexpr int RW_TPB = 256;               // the fill and the add are short (a transcript's k-mers); the verdict is one wavefront's whatever the width
+
+__global__ void __launch_bounds__(RW_TPB) k_represented_walk(ScArgs a, uint32_t *gate_bits, uint8_t *scratch, size_t lev_off, uint8_t *keep, float *median,
+                                                             int64_t *stop) {
+    __shared__ ScLevel s_dfs[4 * SC_LEVELS];
+    __shared__ int s_row[LEV_LDS];
+    __shared__ int s_flags;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const ScRows rw(scratch, a.cap, a.k);
+    const uint32_t H = (uint32_t)a.gate.num_hash;
+    int64_t r = 0;
+    for (; r < a.pn; ++r) {
+        const int64_t k0 = a.kof[r];
+        const int nk = (int)(a.kof[r + 1] - k0);
+        const uint64_t *F = a.F + k0, *R = a.R + k0;
+        // ---- the fill ----
+        for (int i = (int)tid; i < nk; i += RW_TPB) {
+            const uint64_t f = F[i];
+            a.gbit[k0 + i] = (uint8_t)bits_lookup(a.gate.bits, a.gate.mod, a.gate.num_hash, a.kmul, a.stranded ? f : smin(f, R[i]));
+        }
+        __syncthreads();
+        // ---- the verdict ----
+        if (tid < 64u) {
+            const int flags = sc_repr_one<true>(a, r, rw, s_dfs, s_row, reinterpret_cast<int *>(scratch + lev_off), lane);
+            float med = 0.0f;
+            if (flags == 0) {
+                const ScSeq sq{nullptr, F, R, a.cnt + k0, a.gbit + k0, nk, a.stranded};
+                med = sc_median(sq, 0, nk, lane);
+            }
+            if (lane == 0u) { keep[r] = flags == 0 ? 1 : 0; median[r] = med; s_flags = flags; }
+        }
+        __syncthreads();
+        const int flags = s_flags;
+        if (flags & RB_SCREEN_OVER_BUDGET) break;                // the stop rule: every later answer would hang on this one
+        // ---- the add ----
+        if (flags == 0) {
+            const uint32_t total = (uint32_t)nk * H;             // nk <= 2^24 (SC_MAX_ROW), H <= RB_MAX_HASH
+            for (uint32_t e = tid; e < total; e += RW_TPB) {
+                const uint32_t i = e / H, j = e - i * H;
+                const uint64_t f = F[i];
+                const uint64_t b = index_of(multi_hash(a.stranded ? f : smin(f, R[i]), j, a.kmul), a.gate.mod);
+                __hip_atomic_fetch_or(gate_bits + (b >> 5), 1u << (uint32_t)(b & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __threadfence();
+        }
+        __syncthreads();
+    }
+    if (tid == 0u) *stop = r;
 }
 
 // What the two calls share once their arguments are checked: the pieces (rb_pieces.hpp), each with its getKmers rows, gate bits, records and the
@@ -683,9 +755,9 @@ void screen_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64
                });
 }
 
-void represented_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
-                      int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out) {
-    const char *who = "rb_graph_represented";
+// what rb_graph_represented and rb_graph_represented_then_add refuse alike, before either looks at n ...
+void repr_refuse(const char *who, const rb_graph *g, const rb_graph *gate, int lookahead, int max_indel, int max_edge_clip, float percent_identity,
+                 int64_t max_visits, int64_t n) {
     RB_REQUIRE(g && gate, "%s: null handle", who);
     RB_REQUIRE(!g->shard, "%s: not available on a shard handle", who);
     RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
@@ -697,14 +769,16 @@ void represented_call(rb_graph *g, const rb_graph *gate, const char *seq, const 
     RB_REQUIRE(std::isfinite(percent_identity), "%s: percent_identity is not finite", who);
     RB_REQUIRE(max_visits >= 0, "%s: max_visits = %lld", who, (long long)max_visits);
     RB_REQUIRE(n >= 0, "%s: n = %lld", who, (long long)n);
-    if (n == 0) return;
-    RB_REQUIRE(offsets && out, "%s: null argument", who);
+}
+// ... and with n > 0: the sequences' k-mer offsets into ko, the kernel's arguments into a; returns the ints of a wavefront's alignment row in
+// device scratch (0: the row stays in LDS)
+size_t repr_args(const char *who, const rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel, int max_edge_clip,
+                 float percent_identity, int64_t max_visits, std::vector<int64_t> &ko, ScArgs &a) {
     const int k = g->k;
-    std::vector<int64_t> ko((size_t)n + 1);
+    ko.resize((size_t)n + 1);
     kmer_offsets(offsets, n, k, ko.data(), who);
     RB_REQUIRE(offsets[n] == offsets[0] || seq, "%s: null sequence text", who);
     const int64_t visits = max_visits ? max_visits : RB_SCREEN_DEFAULT_VISITS, longest = longest_list(ko, n);
-    ScArgs a{};
     a.what = 0; a.lookahead = lookahead; a.max_depth = max_edge_clip; a.max_indel = max_indel; a.percent_identity = percent_identity;
     a.max_visits = (int)std::min<int64_t>(visits, INT32_MAX);
     // a walk row: an edge walk is bounded by a stretch of the sequence, a gap's path by max(2k - 1, d + k) + max_indel (a gap narrower than k
@@ -715,11 +789,88 @@ void represented_call(rb_graph *g, const rb_graph *gate, const char *seq, const 
     a.cap = (int)cap;
     a.recs = nullptr;
     const size_t letters = (size_t)(longest ? longest + k - 1 : 0);
-    screen_run(g, gate, seq, offsets, n, who, "represented", a, ko, repr_blank(RB_SCREEN_NO_KMER), letters > (size_t)LEV_LDS ? letters : 0, out,
+    return letters > (size_t)LEV_LDS ? letters : 0;
+}
+
+void represented_call(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                      int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out) {
+    const char *who = "rb_graph_represented";
+    repr_refuse(who, g, gate, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, n);
+    if (n == 0) return;
+    RB_REQUIRE(offsets && out, "%s: null argument", who);
+    std::vector<int64_t> ko;
+    ScArgs a{};
+    const size_t lev_cols = repr_args(who, g, seq, offsets, n, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, ko, a);
+    screen_run(g, gate, seq, offsets, n, who, "represented", a, ko, repr_blank(RB_SCREEN_NO_KMER), lev_cols, out,
                [](ScArgs &a, rb_repr_rec *recs, unsigned blocks, hipStream_t s, uint8_t *rows, size_t row_bytes, size_t lev_off) {
                    a.reprs = recs;
                    hipLaunchKernelGGL(k_represented, dim3(blocks), dim3(SC_TPB), 0, s, a, rows, row_bytes, lev_off);
                });
+}
+
+// rb_graph_represented_then_add: the pieces as screen_run cuts them, one k_represented_walk a piece, in order.  The gate is written: unique
+// lock on it, shared lock on g (the lease), in address order.  The piece loop ends at a piece whose walker stopped; the records behind the
+// stop are filled here.
+void represented_then_add_call(rb_graph *g, rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                               int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out, uint8_t *keep, float *median,
+                               int64_t *n_done) {
+    const char *who = "rb_graph_represented_then_add";
+    repr_refuse(who, g, gate, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, n);
+    RB_REQUIRE(gate != g, "%s: the gate is written and the graph is read: they must be two handles", who);
+    if (n == 0) return;
+    RB_REQUIRE(offsets && out && keep && n_done, "%s: null argument", who);
+    std::vector<int64_t> ko;
+    ScArgs a{};
+    const size_t lev_cols = repr_args(who, g, seq, offsets, n, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, ko, a);
+    WriteLock gate_lk;
+    if (gate < g) gate_lk = WriteLock(gate->rw);
+    RB_HIP(hipSetDevice(g->p.device));
+    HostPin pin_r(out, (size_t)n * sizeof(rb_repr_rec));
+    QueryLease q(g);
+    if (gate > g) gate_lk = WriteLock(gate->rw);
+    RB_REQUIRE(g->dbg.bits && g->cbf, "%s: dbgbf or the counting filter has been destroyed", who);
+    RB_REQUIRE(gate->dbg.bits, "%s: the gate's filter has been destroyed", who);
+    RB_HIP(hipStreamSynchronize(gate->stream));                 // (whatever the gate's own calls left in flight)
+    for (int64_t i = 0; i < n; ++i) { out[i] = repr_blank(RB_SCREEN_NO_KMER); keep[i] = 0; }
+    if (median) std::fill(median, median + n, 0.0f);
+    *n_done = n;
+    if (ko[(size_t)n] == 0) return;
+    hipStream_t s = q.c->st;
+    const int k = g->k;
+    const size_t lev_off = sc_row_bytes(a.cap, k), row_bytes = lev_off + up16(lev_cols * sizeof(int));
+    int64_t stopped = -1;                                        // the call's index of the sequence the walk stopped at
+    for_each_host_piece(g, s, seq, offsets, ko.data(), n, "represented_then_add", [&](HostPiece &pc) {
+        if (stopped >= 0) return;
+        const int64_t ra = pc.ra, pn = pc.pn, pt = pc.pt;
+        // b3: counts, gate bits, records, keep flags, medians, the stop index, the one wavefront's rows
+        const size_t o_g = up16((size_t)pt * 4), o_rec = up16(o_g + (size_t)pt), o_keep = up16(o_rec + (size_t)pn * sizeof(rb_repr_rec)),
+                     o_med = up16(o_keep + (size_t)pn), o_stop = up16(o_med + (size_t)pn * 4), o_row = o_stop + 16;
+        q.c->b3.reserve(o_row + row_bytes + 16);
+        uint8_t *base3 = q.c->b3.as<uint8_t>();
+        a.fv = g->view(0, 0);
+        a.gate = ScGate{gate->dbg.bits, gate->dbg.mod, gate->dbg.num_hash};
+        a.kmul = kmul_of(k);
+        a.stranded = (int)g->stranded; a.k = k; a.read_d = g->read_d;
+        a.gbit = base3 + o_g;
+        a.reprs = reinterpret_cast<rb_repr_rec *>(base3 + o_rec);
+        PieceRows(g, *q.c, pc).into(a);
+        hipLaunchKernelGGL(k_represented_walk, dim3(1), dim3(RW_TPB), 0, s, a, gate->dbg.bits, base3 + o_row, lev_off, base3 + o_keep,
+                           reinterpret_cast<float *>(base3 + o_med), reinterpret_cast<int64_t *>(base3 + o_stop));
+        RB_HIP(hipGetLastError());
+        pc.kernels_end();
+        int64_t stop = pn;
+        RB_HIP(hipMemcpyAsync(out + ra, a.reprs, (size_t)pn * sizeof(rb_repr_rec), hipMemcpyDeviceToHost, s));
+        RB_HIP(hipMemcpyAsync(keep + ra, base3 + o_keep, (size_t)pn, hipMemcpyDeviceToHost, s));
+        if (median) RB_HIP(hipMemcpyAsync(median + ra, base3 + o_med, (size_t)pn * 4, hipMemcpyDeviceToHost, s));
+        RB_HIP(hipMemcpyAsync(&stop, base3 + o_stop, 8, hipMemcpyDeviceToHost, s));
+        pc.finish();                                             // the next piece is walked only if this one came to its end
+        if (stop < pn) stopped = ra + stop;
+    });
+    if (stopped >= 0) {
+        *n_done = stopped;
+        for (int64_t i = stopped + 1; i < n; ++i) { out[i] = repr_blank(RB_SCREEN_NOT_REACHED); keep[i] = 0; }
+        if (median) std::fill(median + stopped + 1, median + n, 0.0f);
+    }
 }
 
 }  // namespace
@@ -732,5 +883,12 @@ int rb_graph_screen_fragments(rb_graph *g, const rb_graph *gate, const char *seq
 int rb_graph_represented(rb_graph *g, const rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
                          int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out) {
     return guarded([&] { represented_call(g, gate, seq, offsets, n, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, out); });
+}
+int rb_graph_represented_then_add(rb_graph *g, rb_graph *gate, const char *seq, const int64_t *offsets, int64_t n, int lookahead, int max_indel,
+                                  int max_edge_clip, float percent_identity, int64_t max_visits, rb_repr_rec *out, uint8_t *keep, float *median,
+                                  int64_t *n_done) {
+    return guarded([&] {
+        represented_then_add_call(g, gate, seq, offsets, n, lookahead, max_indel, max_edge_clip, percent_identity, max_visits, out, keep, median, n_done);
+    });
 }
 }  // extern "C"

@@ -27,6 +27,7 @@ BLUNT_WHY_NO_ARM, BLUNT_WHY_LEFT_RANGE, BLUNT_WHY_RIGHT_RANGE, BLUNT_WHY_LEFT_FA
 SCREEN_DEFAULT_VISITS = 65536
 # rb_graph_represented: rb_repr_rec.flags bit 0 (its not-judged bits are SCREEN_BAD_LETTER / SCREEN_NO_KMER / SCREEN_OVER_BUDGET), why, path_form
 REPR_REPRESENTED = 1
+SCREEN_NOT_REACHED = 64         # rb_graph_represented_then_add: a sequence behind an over-budget stop (the next not-judged bit)
 REPR_WHY_TRUE, REPR_WHY_NO_RUN, REPR_WHY_LEFT_LENGTH, REPR_WHY_LEFT_IDENTITY, REPR_WHY_WIDE_GAP, REPR_WHY_NO_PATH, REPR_WHY_PATH_LENGTH, \
     REPR_WHY_PATH_IDENTITY, REPR_WHY_RIGHT_LENGTH, REPR_WHY_RIGHT_IDENTITY = range(10)
 REPR_PATH_NONE, REPR_PATH_LEFT, REPR_PATH_RIGHT, REPR_PATH_SPLICED = range(4)
@@ -205,6 +206,7 @@ SYMBOLS = [
     ("rb_graph_connect_segments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),
     ("rb_graph_represented", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp]),
+    ("rb_graph_represented_then_add", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, C.c_float, _i64, _vp, _vp, _vp, _vp]),
     ("rb_graph_trim_rc_artifacts", _i32, [_vp, _vp, _vp, _i64, _i32, _i32, C.c_float, _vp]),
     ("rb_graph_correct_long", _i32, [_vp, _vp, _vp, _i64, C.POINTER(LongParams), _vp, _vp, _vp]),
     ("rb_graph_neighbors", _i32, [_vp, _vp, _vp, _vp, _sz, _i32, _vp, _vp, _vp]),

@@ -920,6 +920,34 @@ class BloomFilterDeBruijnGraph:
         seq, off = _pack(seqs)
         return self.representedFlat(seq, off, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits)
 
+    SCREEN_NOT_REACHED = N.SCREEN_NOT_REACHED
+
+    def representedThenAddFlat(self, seq, offsets, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits=0, wantMedian=True):
+        """rb_graph_represented_then_add on flat host text: the in-order loop of TranscriptWriter.write (R/RNABloom.java:1639-1720) and
+        GraphUtils.reduceRedundancy (R/util/GraphUtils.java:652-699).  Sequence i = seq[offsets[i]:offsets[i + 1]] is judged as representedFlat
+        judges it, but against bf as it stands THEN; the k-mers of a sequence that is judged and not represented are added to bf — which
+        this call WRITES — before sequence i + 1 is looked at.  Returns (records, keep, median, n_done): the REPR_DTYPE records, keep[i] = 1
+        for a sequence whose k-mers were added, its getMedianKmerCoverage (0 elsewhere; None with wantMedian=False), and n_done = the
+        number of sequences when the walk came to its end, or the index of the SCREEN_OVER_BUDGET sequence it stopped at: the records
+        behind that one are blank with SCREEN_NOT_REACHED, and the caller decides it and calls again on the rest."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        recs = np.zeros(n, self.REPR_DTYPE)
+        keep = np.zeros(n, np.uint8)
+        median = np.zeros(n, np.float32) if wantMedian else None
+        done = C.c_int64(n)
+        check(lib.rb_graph_represented_then_add(self.h, bf._g.h if bf is not None else None, _ptr(seq), _ptr(off), n, lookahead, maxIndelSize,
+                                                maxEdgeClipLength, percentIdentity, maxVisits, _ptr(recs), _ptr(keep),
+                                                _ptr(median) if wantMedian else None, C.byref(done)))
+        return recs, keep, median, int(done.value)
+
+    def representedThenAdd(self, seqs, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits=0):
+        """representedThenAddFlat over strings (or bytes): (records, keep, median, n_done)"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        return self.representedThenAddFlat(seq, off, bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits)
+
     TRIM_DTYPE = np.dtype([("flags", "<i4"), ("begin", "<i4"), ("end", "<i4"), ("mode", "<i4"),
                            ("pass", [("why", "<i4"), ("i0", "<i4"), ("i1", "<i4"), ("i2", "<i4"), ("i3", "<i4")], (2,)), ("reserved", "<i4", (2,))])
     TRIM_HASHES, TRIM_EDGE, TRIM_LONG = N.TRIM_HASHES, N.TRIM_EDGE, N.TRIM_LONG

@@ -460,6 +460,82 @@ def trimReverseComplementArtifact(graph, seqs, mode, maxEdgeClip=0, maxCovGradie
     return out
 
 
+def _keep_out(i, seq):
+    """writeTranscripts' default decision for a sequence the walk stopped at: report it, keep it out"""
+    import sys
+    print("writeTranscripts: sequence %d (%d letters) is over the depth search's budget and is left out" % (i, len(seq)), file=sys.stderr)
+    return False
+
+
+def writeTranscripts(graph, bf, seqs, lookahead, maxIndelSize, maxTipLength, percentIdentity, maxVisits=0, decide=_keep_out):
+    """The decisions of TranscriptWriter.write (R/RNABloom.java:1639-1720) for a list of transcripts in the order the writer would be handed
+    them, in rb_graph_represented_then_add calls: bf is the writer's screeningBf and is written.  Returns (kept, records): kept holds, in
+    order, (index, l, c) for every sequence the writer would write — its index in seqs, `l=` its length, `c=` the "%.1f" of
+    getMedianKmerCoverage — and records the REPR_DTYPE record of every sequence.  The poly-A regexes and the FASTA stay with the caller.
+    A sequence that is over the budget of a depth search stops the walk; decide(index, sequence) -> bool says whether the writer keeps it (its
+    k-mers then go into bf through bf.add, its `c=` comes from graph.getKmers), and the walk resumes behind it.  The default reports it and
+    keeps it out."""
+    seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    recs = np.zeros(len(seqs), graph.REPR_DTYPE)
+    kept, at = [], 0
+    while at < len(seqs):
+        r, keep, median, done = graph.representedThenAdd(seqs[at:], bf, lookahead, maxIndelSize, maxTipLength, percentIdentity, maxVisits)
+        upto = min(done + 1, len(r))                         # the records the call judged, the stopped one included
+        recs[at:at + upto] = r[:upto]
+        kept += [(at + i, len(seqs[at + i]), "%.1f" % float(median[i])) for i in np.flatnonzero(keep[:upto])]
+        if done == len(r):
+            break
+        i = at + done
+        if decide(i, seqs[i]):
+            _, f, rv, cnt = graph.getKmers([seqs[i]])
+            bf.add(f if graph.stranded else np.where(rv.view(np.int64) < f.view(np.int64), rv, f))
+            kept.append((i, len(seqs[i]), "%.1f" % _median_f32(cnt)))
+        at = i + 1
+    return kept, recs
+
+
+def _median_f32(counts):
+    """getMedianKmerCoverage (R/util/GraphUtils.java:229-247): the middle count, or the float32 mean of the two middle ones"""
+    c = np.sort(np.asarray(counts, np.float32))
+    n = c.size
+    return float(c[n // 2]) if n % 2 else float((c[n // 2] + c[n // 2 - 1]) / np.float32(2))
+
+
+def reduceRedundancy(graph, bf, seqs, lookahead, maxIndelSize, maxTipLength, percentIdentity, maxVisits=0):
+    """GraphUtils.reduceRedundancy (R/util/GraphUtils.java:652-699) without its files: the sequences sorted by length, longest first
+    (BitSequence.compareTo; Collections.sort is stable), then the represented-then-add loop in one rb_graph_represented_then_add call; bf is
+    written.  Returns (kept, removed): kept holds (cid, l, sequence) for every sequence the reference writes as ">cid l=<l>", in its order,
+    and removed = seqs.size() - cid.  A sequence over the budget of a depth search raises ValueError (the reference's search has no budget)."""
+    seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    order = sorted(range(len(seqs)), key=lambda i: -len(seqs[i]))
+    ordered = [seqs[i] for i in order]
+    _, keep, _, done = graph.representedThenAdd(ordered, bf, lookahead, maxIndelSize, maxTipLength, percentIdentity, maxVisits)
+    if done != len(ordered):
+        raise ValueError("reduceRedundancy: sequence %d of the sorted list is over the depth search's budget" % done)
+    kept = [(cid + 1, len(ordered[i]), ordered[i]) for cid, i in enumerate(np.flatnonzero(keep))]
+    return kept, len(seqs) - len(kept)
+
+
+def representedThenAddComposed(graph, bf, seqs, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits=0):
+    """The route a caller took before rb_graph_represented_then_add: graph.represented of ONE sequence, then bf.add of a kept sequence's
+    hashes, sequence after sequence — a launch and two copies each.  Kept for the tests and tools/represented_then_add_bench.py.  Returns
+    (records, keep, n_done) with the stop rule of the one call."""
+    seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    recs = np.zeros(len(seqs), graph.REPR_DTYPE)
+    keep = np.zeros(len(seqs), np.uint8)
+    for i, s in enumerate(seqs):
+        recs[i] = graph.represented([s], bf, lookahead, maxIndelSize, maxEdgeClipLength, percentIdentity, maxVisits)[0]
+        flags = int(recs[i]["flags"])
+        if flags & N.SCREEN_OVER_BUDGET:
+            recs[i + 1:] = np.array((N.SCREEN_NOT_REACHED, -1, -1, -1, -1, -1, -1, 0, 0, 0, 0, 0), graph.REPR_DTYPE)
+            return recs, keep, i
+        if flags == 0:
+            _, f, r, _ = graph.getKmers([s])
+            bf.add(f if graph.stranded else np.where(r.view(np.int64) < f.view(np.int64), r, f))
+            keep[i] = 1
+    return recs, keep, len(seqs)
+
+
 def correctLongSequenceWindowed(graph, seqs, **params):
     """GraphUtils.correctLongSequenceWindowed (R/util/GraphUtils.java:3087-3185) for many sequences in one rb_graph_correct_long call (and a
     second one for the few that outgrew their room).  params: graph.LONG_DEFAULTS' keys, named as the reference's arguments.  Returns, per
