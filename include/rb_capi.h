@@ -601,6 +601,53 @@ typedef struct rb_extend_loop_rec {     /* 64 bytes */
 } rb_extend_loop_rec;
 int rb_graph_extend_loop(rb_graph *g, int which, const char *seq, const int64_t *offsets, int64_t n, const uint8_t *phase /* may be NULL */,
                          float min_kmer_cov, int room, int64_t *out_offsets, char *out_seq, rb_extend_loop_rec *recs);
+/* Naive extension of fragments — GraphUtils.naiveExtend(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6935-6957), which the
+ * FragmentAssembler runs on every connected fragment when extendFragments is on (R/RNABloom.java:2214) — for n host sequences in ONE call: a
+ * wavefront per sequence runs both walks on the device.  The call is read-only.  Sequence i is seq[offsets[i], offsets[i+1]), kmers = getKmers of
+ * it; m = min_kmer_cov.  The conventions are rb_graph_extend_loop's wherever they apply.
+ *   First naiveExtendLeft(kmers[0], terminators = the set of kmers) (:6959-7012), then naiveExtendRight(kmers[last], terminators = the set of
+ *   kmers and the left extension) (:6780-6833).  A step, with `best` the k-mer the walk stands on — what rb_graph_naive_extend's mode 0 does, in
+ *   this order: no neighbour with graph.getCount >= m ends the walk (END_NO_NEIGHBOUR) before the back-branch test; any variant of best in the base
+ *   about to leave with count >= 1 ends it (END_BACK_BRANCH); two or more neighbours with count >= m end it (END_SEVERAL); the only candidate a
+ *   member of the terminators or added before by this walk ends it, and the candidate is not added (END_MEMBER); else it is added and becomes
+ *   best.  maxTipLength is no argument: it only feeds Kmer.hasDepthLeft / hasDepthRight, which never consult the graph (R/graph/Kmer.java:407-486;
+ *   see rb_graph_naive_extend).  Membership is Kmer.equals, the k bases: hashes are compared first and every hit is confirmed on the bases.
+ *   Letters: the device judges sequences of upper-case A C G T only.  A sequence with fewer than k letters is NOT_JUDGED / WHY_NO_KMER, any other
+ *   with another byte NOT_JUDGED / WHY_LETTER: it comes back as it went in (out_len its length, both hits -1, every other field 0).
+ *   Room: the reference's walks have no bound; `room` is the most letters (= k-mers) a call may add on EACH side of a sequence.  A walk that has
+ *   added `room` k-mers and would add another ends with END_ROOM (after the membership test, so a walk that ends at exactly `room` k-mers for
+ *   another reason says that reason) and the status is RB_NFRAG_ROOM; after a left END_ROOM the right side is not run (END_NOT_RUN).  Resume with
+ *   the returned text: phase[i] = 0 (or phase == NULL) runs both sides, phase[i] = 1 the right side only (left_end = END_NOT_RUN).  Chained calls
+ *   return what one call with ample room returns: the reference tests terminators.contains(best) || usedKmers.contains(best), and the k-mers of
+ *   the returned text are exactly that union; a walk restarted from the text's outermost k-mer starts in the state the loop was in.  left_ext /
+ *   right_ext add up over the calls.
+ *   Output: out_offsets (host, n + 1) is the capacity layout len_i + 2 * room, filled from the lengths alone; out_seq == NULL is a size query: nothing
+ *   else is touched, nothing is launched.  Else out_seq[out_offsets[i] ..] holds out_len letters — the original ones as they were, added ones
+ *   upper-case A C G T — and zeros behind them.  recs[i]: left_ext / right_ext the k-mers (= letters) added on each side, left_end / right_end how
+ *   each walk ended, left_hit / right_hit for END_MEMBER the lowest index in the k-mer list of the RETURNED text of a k-mer equal to the
+ *   candidate that ended the walk (below left_ext: the left extension; from left_ext + the fragment's k-mers on: the right extension), else -1.
+ *   The counts of the added k-mers are not returned (rb_graph_read_coverage of the text has them).
+ * The call works in pieces cut by capacity k-mers, len_i + 2 * room - k + 1 (RB_QUERY_PIECE, 16 M by default); results do not depend on the cuts.
+ * Device scratch of a piece: 2 bytes per capacity letter, 64 + 1 + 16 per sequence, and — only where a sequence's k-mers + 2 room exceed 1024, the
+ * terminator table a wavefront keeps in LDS — 16 bytes times the next power of two of that number for each of at most 4096 wavefronts (fewer
+ * where that would exceed 1 GB).  A sequence of more than 2^24 k-mers is refused.  It leases a query context (re-entrant on one handle).  With
+ * rb_graph_profile_enable on the kernel's device time is added to the profile entry "naive_extend_fragments".
+ * Refused (RB_ERR_INVALID, nothing launched): a null handle; a shard handle; a destroyed dbgbf or counting filter; a min_kmer_cov that is not finite
+ * or is negative; room < 1 or room > 2^24; n < 0; with n > 0: a null offsets / out_offsets (or recs, unless out_seq is NULL too), a null seq where
+ * there is text, decreasing offsets, a phase byte above 1.  n == 0 succeeds and touches nothing. */
+enum { RB_NFRAG_DONE = 0, RB_NFRAG_ROOM = 1, RB_NFRAG_NOT_JUDGED = 2 };                                                          /* rb_naive_frag_rec.status */
+enum { RB_NFRAG_WHY_NONE = 0, RB_NFRAG_WHY_NO_KMER = 1, RB_NFRAG_WHY_LETTER = 2 };                                               /* rb_naive_frag_rec.why (NOT_JUDGED) */
+enum { RB_NFRAG_END_NOT_RUN = 0, RB_NFRAG_END_NO_NEIGHBOUR = 1, RB_NFRAG_END_BACK_BRANCH = 2, RB_NFRAG_END_SEVERAL = 3, RB_NFRAG_END_MEMBER = 4,
+       RB_NFRAG_END_ROOM = 5 };                                                                                                  /* left_end, right_end */
+typedef struct rb_naive_frag_rec {      /* 64 bytes */
+    int32_t status, why;
+    int32_t left_ext, right_ext, out_len /* letters */;
+    int32_t left_end, right_end;
+    int32_t left_hit, right_hit;
+    int32_t pad[7];
+} rb_naive_frag_rec;
+int rb_graph_naive_extend_fragments(rb_graph *g, const char *seq, const int64_t *offsets, int64_t n, const uint8_t *phase /* may be NULL */,
+                                    float min_kmer_cov, int room, int64_t *out_offsets, char *out_seq, rb_naive_frag_rec *recs);
 /* Joining of read pairs through the graph — GraphUtils.join (R/util/GraphUtils.java:892-1147), the second half of overlapAndConnect (:5065-5090) that
  * the FragmentAssembler runs on every pair GraphUtils.overlap returned null for (R/RNABloom.java:2148).  A wavefront per pair on the device; the call
  * is read-only.  Pair i is lseq[loffsets[i], loffsets[i+1]) and rseq[roffsets[i], roffsets[i+1]); each read's k-mer list is getKmers(String)'s

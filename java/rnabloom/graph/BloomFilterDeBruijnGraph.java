@@ -540,6 +540,41 @@ public class BloomFilterDeBruijnGraph {
     }
 
     /**
+     * GraphUtils.naiveExtend(kmers, graph, maxTipLength, minKmerCov) (src/rnabloom/util/GraphUtils.java:6935-6957) for a batch of fragments in ONE
+     * native call: the left walk with the fragment's k-mers as terminators and the right walk with those and the left extension run on the device,
+     * a wavefront per fragment, and nothing is written to the graph.  room is the most letters the call adds on each side of a fragment.  Returns,
+     * per fragment, the string the extended list spells — the fragment itself where it is not judged (fewer than k letters, a letter other than
+     * upper-case A C G T: records[16 i] == 2).  A fragment whose records[16 i] is 1 ran out of room: call again with the returned string, and with
+     * phase 1 where records[16 i + 5] is not 5.  records (optional, 16 * seqs.length ints) receives the records of
+     * NativeGraph.naiveExtendFragments.
+     */
+    public String[] naiveExtendFragments(String[] seqs, float minKmerCov, int room, int[] records) {
+        return naiveExtendFragments(seqs, minKmerCov, room, null, records);
+    }
+
+    /** ... with a phase per fragment (null: all 0): 0 runs both walks, 1 the right one only */
+    public String[] naiveExtendFragments(String[] seqs, float minKmerCov, int room, byte[] phase, int[] records) {
+        final int n = seqs.length;
+        if (phase != null && phase.length < n) throw new IllegalArgumentException("naiveExtendFragments: phase holds " + phase.length + " bytes, " + n + " are needed");
+        if (records != null && records.length < 16L * n) throw new IllegalArgumentException("naiveExtendFragments: records holds " + records.length + " ints, " + 16L * n + " are needed");
+        if (16L * n > Integer.MAX_VALUE) throw new IllegalArgumentException("naiveExtendFragments: " + n + " fragments' records do not fit one array: smaller batches");
+        final long[] off = new long[n + 1], outOff = new long[n + 1];
+        for (int i = 0; i < n; ++i) off[i + 1] = off[i] + seqs[i].length();
+        if (off[n] > Integer.MAX_VALUE) throw new IllegalArgumentException("naiveExtendFragments: more than 2 GB of text in one batch");
+        final ByteBuffer text = ByteBuffer.allocateDirect(Math.max((int) off[n], 1));
+        for (String s : seqs) for (int i = 0; i < s.length(); ++i) text.put((byte) s.charAt(i));
+        final int[] rec = records != null ? records : new int[16 * n];
+        final int cap = NativeGraph.naiveExtendFragments(handle, text, off, n, phase, minKmerCov, room, outOff, null, null);
+        final ByteBuffer out = ByteBuffer.allocateDirect(Math.max(cap, 1));
+        NativeGraph.naiveExtendFragments(handle, text, off, n, phase, minKmerCov, room, outOff, out, rec);
+        final byte[] b = new byte[cap];
+        out.get(b, 0, cap);
+        final String[] res = new String[n];
+        for (int i = 0; i < n; ++i) res[i] = new String(b, (int) outOff[i], rec[16 * i + 4], java.nio.charset.StandardCharsets.ISO_8859_1);
+        return res;
+    }
+
+    /**
      * GraphUtils.connect(ArrayList, graph, lookahead) (src/rnabloom/util/GraphUtils.java:4836-4872) for a batch of reads in ONE native call: every
      * masked stretch of every read is bridged by the six-argument getMaxCoveragePath on the device, a wavefront per gap, and the longest connected
      * run of each read is returned; nothing is written to the graph.  segments.get(i) is read i's list from SeqUtils.filterFastq / filterFasta.

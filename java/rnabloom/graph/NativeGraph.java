@@ -168,6 +168,18 @@ public final class NativeGraph {
      *  outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
     public static native int extendLoop(long h, int which, ByteBuffer seq, long[] offsets, int n, byte[] phase, float minKmerCov, int room,
                                         long[] outOffsets, ByteBuffer outSeq, int[] recs);
+    /** Naive extension of n fragments on the device (rb_graph_naive_extend_fragments; GraphUtils.naiveExtend(kmers, graph, maxTipLength, minKmerCov),
+     *  R/util/GraphUtils.java:6935-6957): every sequence — upper-case A C G T, at least k letters — is walked to the left from its first k-mer with
+     *  its own k-mers as terminators, then to the right from its last k-mer with its k-mers and the left extension as terminators.  room (1 .. 2^24)
+     *  is the most letters a call adds on each side; outOffsets[n + 1] is filled with the capacity layout length + 2 room; outSeq == null sizes the
+     *  output only.  Else recs holds 16 ints per sequence — status (0 done, 1 out of room: call again with the returned text and phase 0 after a left
+     *  end 5, phase 1 after a right end 5; 2 not judged), why (1 fewer than k letters, 2 a letter other than upper-case A C G T), k-mers added left
+     *  and right, the length of the text, how the left and the right walk ended (0 not run, 1 no neighbour, 2 a back branch, 3 several neighbours, 4
+     *  the candidate is a k-mer of the text, 5 out of room), for an end 4 the lowest index of that k-mer in the returned text's k-mer list on either
+     *  side (else -1), seven zeros — and the text is recs[16 i + 4] bytes at outSeq + outOffsets[i].  phase (may be null: all 0): 0 both walks, 1
+     *  the right one only.  Read-only.  Returns outOffsets[n]; IllegalArgumentException when that is more than an int holds (cut the batch). */
+    public static native int naiveExtendFragments(long h, ByteBuffer seq, long[] offsets, int n, byte[] phase, float minKmerCov, int room,
+                                                  long[] outOffsets, ByteBuffer outSeq, int[] recs);
     /** Connection of the segment lists of n reads through the graph (rb_graph_connect_segments; GraphUtils.connect(ArrayList, graph, lookahead),
      *  R/util/GraphUtils.java:4836-4872): read i owns list entries [readSegs[i], readSegs[i + 1]), entry j is seq[segOffsets[j], segOffsets[j + 1]);
      *  entries with an odd index within a read are placeholders read by length only.  outOffsets[n + 1] is filled from the lengths alone; outSeq ==

@@ -496,6 +496,28 @@ jint FN(extendLoop)(JNIEnv *e, jclass c, jlong h, jint which, jobject seq, jlong
     if (rc) throw_rc(e, rc);
     return cap;
 }
+/* rb_graph_naive_extend_fragments: a record (rb_naive_frag_rec, 64 bytes) is 16 ints to Java: status, why, left_ext, right_ext, out_len, left_end, right_end,
+ * left_hit, right_hit, then seven zeros.  phase may be null.  outSeq == null (then recs may be null too) sizes the output: outOffsets is filled and
+ * outOffsets[n] returned */
+jint FN(naiveExtendFragments)(JNIEnv *e, jclass c, jlong h, jobject seq, jlongArray offsets, jint n, jbyteArray phase, jfloat minKmerCov, jint room,
+                              jlongArray outOffsets, jobject outSeq, jintArray recs) {
+    (void)c;
+    if (n < 0 || (n > 0 && (!offsets || !outOffsets || (*e)->GetArrayLength(e, offsets) <= n || (*e)->GetArrayLength(e, outOffsets) <= n ||
+                            (phase && (*e)->GetArrayLength(e, phase) < n) || (outSeq && (!recs || (*e)->GetArrayLength(e, recs) / 16 < n))))) {
+        (*e)->ThrowNew(e, (*e)->FindClass(e, "java/lang/IllegalArgumentException"), "naiveExtendFragments: an array is too short for n sequences");
+        return 0;
+    }
+    jlong *o = la(e, offsets), *oo = la(e, outOffsets);
+    jbyte *ph = ba(e, phase);
+    jint *rc16 = ia(e, recs);
+    int rc = rb_graph_naive_extend_fragments(G(h), (const char *)direct(e, seq), (const int64_t *)o, n, (const uint8_t *)ph, minKmerCov, room, (int64_t *)oo,
+                                             outSeq ? (char *)direct(e, outSeq) : 0, (rb_naive_frag_rec *)rc16);
+    if (rc == 0 && oo && n >= 0 && oo[n] > 0x7fffffffLL) rc = RB_ERR_INVALID;      /* the capacity layout does not fit the int this returns: smaller batches */
+    const jint cap = rc == 0 && oo && n >= 0 ? (jint)oo[n] : 0;
+    lr(e, offsets, o, JNI_ABORT); br(e, phase, ph, JNI_ABORT); lr(e, outOffsets, oo, 0); ir(e, recs, rc16, 0);
+    if (rc) throw_rc(e, rc);
+    return cap;
+}
 /* rb_graph_connect_segments: a read's record (rb_connect_rec, 32 bytes) is 8 ints to Java: outcome, why, gaps, connected, first_seg, last_seg, out_len, 0; a
  * gap's (rb_connect_gap_rec, 32 bytes; gapRecs may be null) 8 more: connected, how, l_end, r_end, l_added, r_added, index, path_len.  outSeq == null (then recs may
  * be null too) sizes the output: outOffsets is filled and outOffsets[n] returned */

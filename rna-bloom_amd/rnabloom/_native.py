@@ -46,6 +46,15 @@ EXTL_REC_FIELDS = [("status", "<i4"), ("why", "<i4"), ("left_ext", "<i4"), ("rig
                    ("right_end", "<i4"), ("left_rounds", "<i4"), ("right_rounds", "<i4"), ("steps", "<i4"), ("floor_drops", "<i4"),
                    ("used_passed", "<i4"), ("left_floor", "<f4"), ("right_floor", "<f4"), ("pad", "<i4", (2,))]
 EXTL_MAX_ROOM = 1 << 24
+# rb_graph_naive_extend_fragments: rb_naive_frag_rec.status, why, left_end / right_end; the record's fields (64 bytes); the most k-mers + 2 room
+# of a fragment whose terminator table stays in LDS (csrc/rb_naive_frag.hip NF_LDS_ENTRIES): beyond it the table is a row of device scratch
+NFRAG_DONE, NFRAG_ROOM, NFRAG_NOT_JUDGED = range(3)
+NFRAG_WHY_NONE, NFRAG_WHY_NO_KMER, NFRAG_WHY_LETTER = range(3)
+NFRAG_END_NOT_RUN, NFRAG_END_NO_NEIGHBOUR, NFRAG_END_BACK_BRANCH, NFRAG_END_SEVERAL, NFRAG_END_MEMBER, NFRAG_END_ROOM = range(6)
+NFRAG_REC_FIELDS = [("status", "<i4"), ("why", "<i4"), ("left_ext", "<i4"), ("right_ext", "<i4"), ("out_len", "<i4"), ("left_end", "<i4"),
+                    ("right_end", "<i4"), ("left_hit", "<i4"), ("right_hit", "<i4"), ("pad", "<i4", (7,))]
+NFRAG_MAX_ROOM = 1 << 24
+NAIVE_FRAG_LDS_ENTRIES = 1024
 # rb_graph_correct_pairs: rb_pairc_rec.status, end, flags; the record's fields (64 bytes; a numpy dtype is made of them)
 PAIRC_UNCHANGED, PAIRC_CORRECTED, PAIRC_NOT_JUDGED = range(3)
 PAIRC_END_ALL, PAIRC_END_NO_CHANGE, PAIRC_END_LOW, PAIRC_END_NO_KMER, PAIRC_END_LOST_KMERS = range(5)
@@ -202,6 +211,7 @@ SYMBOLS = [
     ("rb_graph_extend_se", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_pe", _i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     ("rb_graph_extend_loop", _i32, [_vp, _i32, _vp, _vp, _i64, _vp, C.c_float, _i32, _vp, _vp, _vp]),
+    ("rb_graph_naive_extend_fragments", _i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _i32, _vp, _vp, _vp]),
     ("rb_graph_join_pairs", _i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp]),
     ("rb_graph_connect_segments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _vp, _vp, _vp, _vp]),
     ("rb_graph_screen_fragments", _i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp]),

@@ -863,6 +863,39 @@ class BloomFilterDeBruijnGraph:
         out, oo, recs = self.extendLoopFlat(seq, off, which, minKmerCov, room, phase)
         return [out[oo[i]:oo[i] + rc["out_len"]].tobytes() for i, rc in enumerate(recs)], recs
 
+    NFRAG_DTYPE = np.dtype(N.NFRAG_REC_FIELDS)
+    NFRAG_DONE, NFRAG_ROOM, NFRAG_NOT_JUDGED = N.NFRAG_DONE, N.NFRAG_ROOM, N.NFRAG_NOT_JUDGED
+    NFRAG_STATUSES = ("done", "room", "not_judged")
+    NFRAG_WHYS = ("none", "no_kmer", "letter")
+    NFRAG_ENDS = ("not_run", "no_neighbour", "back_branch", "several", "member", "room")
+
+    def naiveExtendFragmentsFlat(self, seq, offsets, minKmerCov, room, phase=None):
+        """rb_graph_naive_extend_fragments on flat host text (GraphUtils.naiveExtend(kmers, graph, maxTipLength, minKmerCov),
+        R/util/GraphUtils.java:6935-6957): sequence i is seq[offsets[i]:offsets[i + 1]] (uint8); room is the most letters the call adds on each
+        side of a sequence; phase (uint8 per sequence, or None) 0 runs both walks, 1 the right one only.  Returns (out, out_offsets, recs): one
+        NFRAG_DTYPE record per sequence, its text at out[out_offsets[i]:out_offsets[i] + recs[i]["out_len"]].  Read-only."""
+        seq = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        ph = None if phase is None else np.ascontiguousarray(phase, dtype=np.uint8)
+        oo = np.zeros(n + 1, np.int64)
+        args = (self.h, _ptr(seq), _ptr(off), n, _ptr(ph), minKmerCov, room, _ptr(oo))
+        check(lib.rb_graph_naive_extend_fragments(*args, None, None))
+        out = np.zeros(max(1, int(oo[n])), np.uint8)
+        recs = np.zeros(n, self.NFRAG_DTYPE)
+        check(lib.rb_graph_naive_extend_fragments(*args, _ptr(out), _ptr(recs)))
+        return out, oo, recs
+
+    def naiveExtendFragments(self, seqs, minKmerCov, room, phase=None):
+        """GraphUtils.naiveExtend of each sequence's getKmers list on the device, in one call: (texts, recs).  The left walk's terminators are
+        the sequence's k-mers, the right walk's those and the left extension.  A sequence whose record says NFRAG_ROOM wants a further call with
+        the returned text (phase 1 where its right walk ran out of room), one that says NFRAG_NOT_JUDGED (fewer than k letters, a letter other
+        than upper-case A C G T) comes back as it went in: graphutils.naiveExtend does the first and reports the second."""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        seq, off = _pack(seqs)
+        out, oo, recs = self.naiveExtendFragmentsFlat(seq, off, minKmerCov, room, phase)
+        return [out[oo[i]:oo[i] + rc["out_len"]].tobytes() for i, rc in enumerate(recs)], recs
+
     SCREEN_DTYPE = np.dtype([("flags", "<i4"), ("chim_why", "<i4"), ("break_i", "<i4"), ("break_j", "<i4"), ("right_len", "<i4"), ("left_len", "<i4"),
                              ("blunt_why", "<i4"), ("boundary", "<i4")])
     SCREEN_BRANCH_FREE, SCREEN_CHIMERA, SCREEN_BLUNT_END = N.SCREEN_BRANCH_FREE, N.SCREEN_CHIMERA, N.SCREEN_BLUNT_END

@@ -340,6 +340,132 @@ def extendPEOnDevice(graph, seqs, minKmerCov, room=4096):
     return _extend_on_device(graph, seqs, minKmerCov, room, graph.EXTL_PE, extendPE)
 
 
+def naiveExtend(graph, seqs, maxTipLength, minKmerCov, room=256, keepNotJudged=False):
+    """GraphUtils.naiveExtend(kmers, graph, maxTipLength, minKmerCov) (R/util/GraphUtils.java:6935-6957) of each sequence's getKmers list on
+    the device (graph.naiveExtendFragments, rb_graph_naive_extend_fragments): the strings the extended lists spell.  maxTipLength is accepted and
+    unused, as in the reference's effect (Kmer.hasDepthLeft / hasDepthRight never consult the graph).  room is the most letters a call adds
+    on each side; a sequence that wants more is resumed with the returned text — both walks after a left walk ran out of room, the right walk
+    only (phase 1) after the right one did — until every sequence is done.  A sequence the device does not judge (fewer than k letters, a
+    letter other than upper-case A C G T) raises ValueError, or is returned as it is with keepNotJudged."""
+    texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    todo, phase = list(range(len(texts))), None
+    while todo:
+        got, recs = graph.naiveExtendFragments([texts[i] for i in todo], minKmerCov, room, phase)
+        nxt, phase = [], []
+        for i, t, rc in zip(todo, got, recs):
+            status = int(rc["status"])
+            if status == N.NFRAG_NOT_JUDGED:
+                if not keepNotJudged:
+                    raise ValueError("naiveExtend: sequence %d is not judged (%s)" % (i, graph.NFRAG_WHYS[int(rc["why"])]))
+                continue
+            texts[i] = t
+            if status == N.NFRAG_ROOM:
+                nxt.append(i)
+                phase.append(0 if int(rc["left_end"]) == N.NFRAG_END_ROOM else 1)
+        todo = nxt
+    return texts
+
+
+def naiveExtendComposed(graph, seqs, minKmerCov, cap):
+    """What ONE graph.naiveExtendFragments call with room = cap returns as texts, composed of two graph.naiveExtend calls (rb_graph_naive_extend,
+    mode 0) as a caller had to before rb_graph_naive_extend_fragments: the left walk from each sequence's first k-mer with the sequence as
+    terminators, then — for the sequences whose left walk did not fill its cap — the right walk from the last k-mer with the left extension +
+    the sequence as terminators.  Sequences of upper-case A C G T with at least k letters.  Serves the A/B
+    (tools/naive_extend_fragments_bench.py) and an equality test."""
+    k = graph.k
+    texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    if not texts:
+        return []
+    lext, lreason = graph.naiveExtend([t[:k] for t in texts], 1, mode=0, minKmerCov=minKmerCov, terminators=texts, cap=cap)
+    texts = [l[::-1] + t for l, t in zip(lext, texts)]                # (a left walk returns its bases in walking order)
+    go = [i for i, r in enumerate(lreason) if r != 6]                 # (6: the cap was reached — the new call's END_ROOM, behind which its right walk does not run)
+    if go:
+        rext, _ = graph.naiveExtend([texts[i][-k:] for i in go], 0, mode=0, minKmerCov=minKmerCov, terminators=[texts[i] for i in go], cap=cap)
+        for i, r in zip(go, rext):
+            texts[i] += r
+    return texts
+
+
+FRAG_KEPT, FRAG_INCONSISTENT, FRAG_SPURIOUS, FRAG_EMPTY, FRAG_NO_COMPLEX_KMER, FRAG_TOO_SHORT = range(6)
+FRAG_OUTCOMES = ("kept", "inconsistent", "spurious", "empty", "no_complex_kmer", "too_short")
+
+
+def finishFragments(graph, fragments, leftNk, rightNk, *, lookahead, minNumKmerPairs, maxTipLength, minKmerCov, extendFragments, trimArtifact,
+                    room=256):
+    """The second half of FragmentAssembler.run for connected read pairs (R/RNABloom.java:2182-2268): fragments[i] is the string the k-mers
+    overlapAndConnect returned spell (upper-case A C G T), leftNk[i] / rightNk[i] the numbers of k-mers of the pair's (corrected) reads.  One
+    batched device call per step over the fragments still alive:
+      1. :2186-2203  with readPairedKmerDistance < nk: breakWithReadPairedKmers(F, graph, lookahead) — the argument really is lookahead; not
+         exactly one range: dropped (FRAG_INCONSISTENT); range[0] >= leftNk or range[1] < nk - rightNk: dropped (FRAG_SPURIOUS); else cut to it.
+      2. :2205-2208  trimArtifact: trimReverseComplementArtifact with maxEdgeClip = maxTipLength.  An empty list is reported (FRAG_EMPTY) where
+         the reference would throw in kmers.get(0) of naiveExtend.
+      3. :2210-2234  preExtensionFragLen = nk + k - 1.  extendFragments: E = naiveExtend(F); the reference's `E.size() != preExtensionFragLen`
+         compares a k-mer count with a letter count, so it holds unless exactly k - 1 k-mers were added — restated as written.  Where it holds:
+         breakWithReadPairedKmers(E, graph, minNumKmerPairs), the whole-list form; exactly one range: F = E cut to it (adopted); else F stays.
+      4. :2237-2268  nk + k - 1 >= k + lookahead: minCov = the smallest count and hasComplexKmer = some k-mer graph.isRepeatKmer rejects, both
+         from the coverage record of the final text (min, n_complex > 0); no complex k-mer: dropped (FRAG_NO_COMPLEX_KMER); shorter: dropped
+         (FRAG_TOO_SHORT).
+    Returns, per fragment, (text or None, preExtensionFragLen or -1 where steps 1 and 2 dropped it, minCov as numpy.float32 or None, outcome,
+    adopted).  graph.addFragmentPairKmers of a kept fragment writes to the graph, and the unconnected pairs (:2269-2307) need no graph call: both
+    stay with the caller."""
+    from .graph import ReadBatch
+    k, d = graph.k, graph.getReadPairedKmerDistance()
+    n = len(fragments)
+    text = [f.encode() if isinstance(f, str) else bytes(f) for f in fragments]
+    outcome, pre, min_cov, adopted = [FRAG_KEPT] * n, [-1] * n, [None] * n, [False] * n
+    nk_of = lambda i: len(text[i]) - k + 1
+    cut = lambda t, r: t[r[0]:r[1] + k - 1]
+    alive = lambda: [i for i in range(n) if outcome[i] == FRAG_KEPT]
+    # 1
+    idx = [i for i in alive() if d < nk_of(i)]
+    if idx:
+        for i, ranges in zip(idx, graph.breakWithReadPairedKmers([text[i] for i in idx], lookahead)):
+            if len(ranges) != 1:
+                outcome[i] = FRAG_INCONSISTENT
+            elif ranges[0][0] >= leftNk[i] or ranges[0][1] < nk_of(i) - rightNk[i]:
+                outcome[i] = FRAG_SPURIOUS
+            else:
+                text[i] = cut(text[i], ranges[0])
+    # 2
+    idx = alive()
+    if trimArtifact and idx:
+        for i, t in zip(idx, trimReverseComplementArtifact(graph, [text[i] for i in idx], graph.TRIM_EDGE, maxEdgeClip=maxTipLength)):
+            if len(t) < k:
+                outcome[i] = FRAG_EMPTY
+            else:
+                text[i] = t
+    # 3
+    idx = alive()
+    for i in idx:
+        pre[i] = nk_of(i) + k - 1
+    if extendFragments and idx:
+        ext = naiveExtend(graph, [text[i] for i in idx], maxTipLength, minKmerCov, room)
+        # `extendedFragmentKmers.size() != preExtensionFragLen` (:2216): k-mers against letters, as written
+        was = [(i, e) for i, e in zip(idx, ext) if len(e) - k + 1 != pre[i]]
+        if was:
+            for (i, e), ranges in zip(was, graph.breakWithReadPairedKmers([e for _, e in was], minNumKmerPairs)):
+                if len(ranges) == 1:
+                    text[i], adopted[i] = cut(e, ranges[0]), True
+    # 4
+    idx = []
+    for i in alive():
+        if nk_of(i) + k - 1 >= k + lookahead:
+            idx.append(i)
+        else:
+            outcome[i] = FRAG_TOO_SHORT
+    if idx:
+        batch = ReadBatch.from_reads([text[i] for i in idx], device=graph.device)
+        try:
+            recs, _ = graph.coverageStats(batch, minKmerCov=minKmerCov)
+        finally:
+            batch.close()
+        for i, rc in zip(idx, recs):
+            min_cov[i] = np.float32(rc["min"])
+            if int(rc["n_complex"]) == 0:
+                outcome[i] = FRAG_NO_COMPLEX_KMER
+    return [(text[i] if outcome[i] == FRAG_KEPT else None, pre[i], min_cov[i], outcome[i], adopted[i]) for i in range(n)]
+
+
 def _extend_on_device(graph, seqs, minKmerCov, room, which, host_loop):
     k = graph.k
     texts = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
